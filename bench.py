@@ -17,6 +17,11 @@ f*F + 1 + r, stride N, and each frame's float3 image is summed on rank 0 by one 
 libkdpt (kdpt_comm_init / kdpt_render_frames; the communicator's unique id goes out over the process group).
 The gloo backend (ranks sharing a GPU, CPU rehearsals) hands each rank's frame shares out and reduces them here.
 
+A plain run sets up, warms up, times the steps, writes `--dump-outputs DIR` when asked and prints the result
+line.  `--full` adds what takes work of its own: the `roofline` block below (one untimed counting iteration,
+the PMC profile lookup) and the CPU baselines (`cpu_baseline`, `cpu_baseline_1core`; `--no-cpu-baseline`
+leaves them out).
+
 Roofline: the dominant kernel is k_trace (the KD traversal of the rays that meet the KD root box).  It is
 bound by VALU issue and latency, not HBM (its tree lives in LDS, its triangles in L2), so the
 roofline is VALU issue: peak = 256 CUs x 4 SIMDs x 1/2 wave64 VALU instruction per clock x 2.4 GHz.
@@ -70,7 +75,11 @@ def parse():
     ap.add_argument("--bare", action="store_true", help="traverseKDbare instead of the short-stack hybrid")
     ap.add_argument("--bounce-cap", type=int, default=8,
                     help="bounces per iteration (8 = the reference's `depth > 7`; 16 for the C5 stress config)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the k_trace roofline block (one untimed counting iteration, "
+                         "the PMC profile) and the CPU baselines; a plain run sets up, warms up, times the steps "
+                         "and prints the result line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--cpu-repeats", type=int, default=3, help="CPU-baseline repeats (median and spread)")
     ap.add_argument("--cpu-iters", type=int, default=8, help="iterations per repeat of the multi-thread CPU leg")
     ap.add_argument("--pipeline", type=int, default=8,
@@ -86,6 +95,11 @@ def parse():
                     help="kdpt_set_tuning knob for A/B runs (not for reported numbers)")
     ap.add_argument("--dump-image", default=None, help="rank 0 saves the sum of the timed frames' reduced float3 "
                     "images here (.npy; tests/test_gpu_sharded.py checks the N > 1 path with it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the timed steps computed as DIR/<name>.npy: image.npy (float32, H x W "
+                         "x 3: the image after the last timed step, i.e. the timed frames' reduced float3 images "
+                         "added in frame order; a fixed seeded sample of its values when it exceeds 64 MB) and "
+                         "segments.npy (float64: the path segments of the timed steps, all ranks)")
     ap.add_argument("--pmc-profile", default=None, help="profile JSON for the VALU roofline (default: "
                     "profiles/pmc_<scene>_<mesh>_<W>x<H>.json)")
     return ap.parse_args()
@@ -194,6 +208,23 @@ def valu_roofline(args, W, H, rays_per_launch, launch_ms, share):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, image, segments):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as <path>/<name>.npy.
+    The render is a pure function of the arguments (RNG seeded by global iteration), so two builds run with
+    the same arguments can be compared value for value."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    image = np.ascontiguousarray(image, dtype=np.float32)
+    if image.nbytes + 8 > DUMP_LIMIT_BYTES:  # the same values every run: indices drawn with a fixed seed
+        keep = np.sort(np.random.default_rng(0).choice(image.size, (DUMP_LIMIT_BYTES >> 1) // 4, replace=False))
+        image = image.reshape(-1)[keep]
+    np.save(os.path.join(path, "image.npy"), image)
+    np.save(os.path.join(path, "segments.npy"), np.array([segments], dtype=np.float64))
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -251,11 +282,12 @@ def main():
     if args.warmup:
         pt.render_frames(0, args.warmup, F, pipeline=args.pipeline, batch=args.batch)
         pt.synchronize()
-    # per-segment work counters from one untimed counting iteration of the timed range (informational)
-    first_timed, _ = frame_share(args.warmup, F, world, rank)
-    aabb, tri, hit = pt.count_iteration(first_timed)
-    aabb_prep, cand = pt.count_split()
-    cnt_stats = pt.stats()
+    if args.full:
+        # per-segment work counters from one untimed counting iteration of the timed range (informational)
+        first_timed, _ = frame_share(args.warmup, F, world, rank)
+        aabb, tri, hit = pt.count_iteration(first_timed)
+        aabb_prep, cand = pt.count_split()
+        cnt_stats = pt.stats()
     pt.reset()  # zero image and totals: the timed frames alone
     st0 = pt.stats()
     image = torch.zeros(3 * W * H, dtype=torch.float32) if gloo and rank == 0 else None
@@ -297,43 +329,50 @@ def main():
         dt = float(tmax[0])
         seg, rays, kernel_ms, launches = int(tsum[0]), int(tsum[1]), float(tsum[2]), int(tsum[3])
         ev_ms, ev_n = float(tsum[4]), int(tsum[5])
-    if rank == 0 and args.dump_image:
-        import numpy as np
-        np.save(args.dump_image, image.numpy() if gloo else pt.image().reshape(-1))
+    if rank == 0 and (args.dump_image or args.dump_outputs):
+        final = image.numpy() if gloo else pt.image().reshape(-1)
+        if args.dump_image:
+            import numpy as np
+            np.save(args.dump_image, final)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, final.reshape(H, W, 3), seg)
     if rank != 0:
         pt.close()
         if dist:
             dist.destroy_process_group()
         return
     iters = args.steps * F
-    avg_launch_ms = kernel_ms / max(1, launches)
-    rays_per_launch = rays / max(1, launches)
-    share = pt.trace_grid_share()
-    roof = valu_roofline(args, W, H, rays_per_launch, avg_launch_ms, share)
-    count_seg = max(1, sum(cnt_stats.seg_per_bounce[d] for d in range(32)))
-    alg_bytes = 76 * cand + 52 * (aabb - aabb_prep) + 36 * tri + 40 * hit  # SURVEY 8(d) model, k_trace's part
-    roof.update({
-        "launch_grid_share": round(share, 4), "avg_launch_ms": round(avg_launch_ms, 5), "launches": launches,
-        "avg_launch_ms_hip_events": round(ev_ms / ev_n, 5) if ev_n else None,
-        "rays_per_launch": round(rays_per_launch, 1),
-        "k_trace_ms_per_step": round(kernel_ms / max(1, args.steps * world), 4),
-        "k_trace_busy_share": round(kernel_ms * share / (dt * 1e3 * world), 4),
-        # every k_trace instruction of the timed region over its wall time and the whole chip: a lower bound on
-        # the kernel's issue rate that does not depend on launch spans (with more launches in flight than grid
-        # shares, busy share > 1, a launch's span includes waiting for CUs the other launches hold)
-        "chip_wide_achieved": (round(roof["valu_per_ray"] * rays / (dt * world) / 1e9, 2)
+    roof = None
+    if args.full:
+        avg_launch_ms = kernel_ms / max(1, launches)
+        rays_per_launch = rays / max(1, launches)
+        share = pt.trace_grid_share()
+        roof = valu_roofline(args, W, H, rays_per_launch, avg_launch_ms, share)
+        count_seg = max(1, sum(cnt_stats.seg_per_bounce[d] for d in range(32)))
+        alg_bytes = 76 * cand + 52 * (aabb - aabb_prep) + 36 * tri + 40 * hit  # SURVEY 8(d) model, k_trace's part
+        roof.update({
+            "launch_grid_share": round(share, 4), "avg_launch_ms": round(avg_launch_ms, 5), "launches": launches,
+            "avg_launch_ms_hip_events": round(ev_ms / ev_n, 5) if ev_n else None,
+            "rays_per_launch": round(rays_per_launch, 1),
+            "k_trace_ms_per_step": round(kernel_ms / max(1, args.steps * world), 4),
+            "k_trace_busy_share": round(kernel_ms * share / (dt * 1e3 * world), 4),
+            # every k_trace instruction of the timed region over its wall time and the whole chip: a lower bound on
+            # the kernel's issue rate that does not depend on launch spans (with more launches in flight than grid
+            # shares, busy share > 1, a launch's span includes waiting for CUs the other launches hold)
+            "chip_wide_achieved": (round(roof["valu_per_ray"] * rays / (dt * world) / 1e9, 2)
+                                   if roof.get("valu_per_ray") else None),
+            "chip_wide_frac": (round(roof["valu_per_ray"] * rays / (dt * world) / 1e9 / VALU_PEAK_GINST, 4)
                                if roof.get("valu_per_ray") else None),
-        "chip_wide_frac": (round(roof["valu_per_ray"] * rays / (dt * world) / 1e9 / VALU_PEAK_GINST, 4)
-                           if roof.get("valu_per_ray") else None),
-        "algorithmic": {"bytes_per_ray": round(alg_bytes / max(1, cand), 1),
-                        "GBps_per_launch": round(alg_bytes / max(1, cand) * rays_per_launch / (avg_launch_ms * 1e-3)
-                                                 / 1e9, 1) if avg_launch_ms > 0 else None,
-                        "note": "SURVEY 8(d) byte model of k_trace's work; most of these bytes are LDS/L2 hits, "
-                                "so it is not an HBM rate"},
-        "per_segment_counts": {"aabb": round(aabb / count_seg, 4), "tri": round(tri / count_seg, 4),
-                               "hit": round(hit / count_seg, 5), "aabb_before_k_trace": round(aabb_prep / count_seg, 4),
-                               "k_trace_share": round(cand / count_seg, 4)},
-    })
+            "algorithmic": {"bytes_per_ray": round(alg_bytes / max(1, cand), 1),
+                            "GBps_per_launch": round(alg_bytes / max(1, cand) * rays_per_launch / (avg_launch_ms * 1e-3)
+                                                     / 1e9, 1) if avg_launch_ms > 0 else None,
+                            "note": "SURVEY 8(d) byte model of k_trace's work; most of these bytes are LDS/L2 hits, "
+                                    "so it is not an HBM rate"},
+            "per_segment_counts": {"aabb": round(aabb / count_seg, 4), "tri": round(tri / count_seg, 4),
+                                   "hit": round(hit / count_seg, 5),
+                                   "aabb_before_k_trace": round(aabb_prep / count_seg, 4),
+                                   "k_trace_share": round(cand / count_seg, 4)},
+        })
     per_gpu = F / world
     out = {
         "metric": METRIC,
@@ -369,10 +408,10 @@ def main():
         "ms_per_iteration": round(dt * 1e3 * world / iters, 4),
         "segments_per_iteration": round(seg / iters, 1),
         "primary_rays_per_s": round(W * H * iters / dt, 1),
-        "roofline": roof,
+        **({"roofline": roof} if roof is not None else {}),
         "reference_980m_intersect_ms_per_iter": 79.4,
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
         # SURVEY 8(d) / BASELINE.md 3: the same oracle on one core as well
         out["cpu_baseline_1core"] = cpu_baseline(args, threads=1, iters=1)

@@ -7,7 +7,7 @@ mkdir -p gpurun_out/ab
 for r in $(seq 1 "$ROUNDS"); do
   for n in $NAMES; do
     log=gpurun_out/ab/${n}_$r.log
-    KDPT_LIBRARY=$PWD/ab/$n.so timeout -k 10 180 python -u bench.py --no-cpu-baseline --steps 20 --warmup 5 "$@" > "$log" 2>&1 \
+    KDPT_LIBRARY=$PWD/ab/$n.so timeout -k 10 180 python -u bench.py --full --no-cpu-baseline --steps 20 --warmup 5 "$@" > "$log" 2>&1 \
       || { echo "$n round $r failed"; tail -5 "$log"; exit 1; }
     python -c "
 import json; d=json.loads(open('$log').read().strip().splitlines()[-1])

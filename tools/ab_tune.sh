@@ -9,7 +9,7 @@ for r in $(seq 1 "$ROUNDS"); do
   for spec in "${SPECS[@]}"; do
     label=${spec%%=*}; args=${spec#*=}
     log=gpurun_out/ab_tune/${label}_$r.log
-    timeout -k 10 180 python -u bench.py --no-cpu-baseline --steps 20 --warmup 5 $args > "$log" 2>&1 \
+    timeout -k 10 180 python -u bench.py --full --no-cpu-baseline --steps 20 --warmup 5 $args > "$log" 2>&1 \
       || { echo "$label round $r failed"; tail -5 "$log"; exit 1; }
     python -c "
 import json; d=json.loads(open('$log').read().strip().splitlines()[-1])

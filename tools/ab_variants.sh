@@ -17,7 +17,7 @@ for r in $(seq 1 "$ROUNDS"); do
     IFS=, read -ra TL <<< "$tunes"
     for t in "${TL[@]}"; do [ -n "$t" ] && targs+=(--tune "$t"); done
     log=gpurun_out/ab/${name}_$r.log
-    KDPT_LIBRARY=$lib_path timeout -k 10 240 python -u bench.py --no-cpu-baseline "${targs[@]}" "$@" > "$log" 2>&1 \
+    KDPT_LIBRARY=$lib_path timeout -k 10 240 python -u bench.py --full --no-cpu-baseline "${targs[@]}" "$@" > "$log" 2>&1 \
       || { echo "$name round $r failed"; tail -5 "$log"; exit 1; }
     python -c "
 import json; d=json.loads(open('$log').read().strip().splitlines()[-1])

@@ -13,11 +13,11 @@
 #   dist1    bench.py under a one-rank RCCL process group (the library's ncclReduce per frame)
 #   columns  tools/reference_columns.py (the reference's brute / bbox / kd / short-stack table)
 TAG=${1:?tag}
-STEPS=${2:-"tests;bench:--steps 20 --warmup 5"}
-C5="--no-cpu-baseline --mesh icosphere_8 --res 1600 1600 --depth 16 --bounce-cap 16 --spp-per-step 64"
-C4="--scene cornell8 --no-cpu-baseline"
+STEPS=${2:-"tests;bench:--full --steps 20 --warmup 5"}
+C5="--full --no-cpu-baseline --mesh icosphere_8 --res 1600 1600 --depth 16 --bounce-cap 16 --spp-per-step 64"
+C4="--scene cornell8 --full --no-cpu-baseline"
 case "$STEPS" in
-  driver) STEPS="tests;smoke;bench:--steps 20 --warmup 5" ;;
+  driver) STEPS="tests;smoke;bench:--full --steps 20 --warmup 5" ;;
   c5) STEPS="bench:$C5 --steps 30 --warmup 3" ;;
   c4) STEPS="bench:$C4 --spp-per-step 32 --steps 160 --warmup 20;bench:$C4 --spp-per-step 256 --steps 20 --warmup 3;bench:$C4 --total-spp 256 --steps 20 --warmup 3" ;;
   trace) STEPS="sh:rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/$TAG/trace -o run -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline" ;;

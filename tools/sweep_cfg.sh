@@ -6,7 +6,7 @@ mkdir -p gpurun_out/sweep
 for cfg in "$@"; do
   name=${cfg%%|*}; args=${cfg#*|}
   log=gpurun_out/sweep/$name.log
-  timeout -k 10 180 python -u bench.py --no-cpu-baseline --steps 20 --warmup 5 $args > "$log" 2>&1 \
+  timeout -k 10 180 python -u bench.py --full --no-cpu-baseline --steps 20 --warmup 5 $args > "$log" 2>&1 \
     || { echo "$name failed"; tail -5 "$log"; exit 1; }
   python -c "
 import json; d=json.loads(open('$log').read().strip().splitlines()[-1])
