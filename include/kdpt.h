@@ -250,7 +250,8 @@ int kdpt_set_options(kdpt_ctx *ctx, const kdpt_options *opt);
  * are rebuilt for it), "reduce_spin_us" (0; > 0: a device spin of that many
  * microseconds on the reduce stream before every frame's reduce, emulating an ncclReduce that waits for a slower
  * peer -- a diagnostic of the frame pipeline; ctx = NULL sets it for contexts created later, e.g. the ones
- * kdpt_render_sharded creates), "sync_debug" (0).  ctx = NULL only (process defaults of the contexts created afterwards):
+ * kdpt_render_sharded creates), "sync_debug" (0), "cast_chunk" (1 << 20; the rays per chunk of kdpt_cast_rays, at
+ * least 64: its buffers are remade on the next call).  ctx = NULL only (process defaults of the contexts created afterwards):
  * "cluster_chord" (-1: normal cones of chord 0.02 before the Morton runs for meshes whose cull margin is
  * rigorous, Morton runs only otherwise; 0: Morton runs only; > 0: cones of that chord for every mesh -- the
  * cluster layout, same bits), "cu_mask_streams" (1: the context's streams are created with a mask of every CU,
@@ -315,6 +316,55 @@ int kdpt_render_frames(kdpt_ctx *ctx, int first_frame, int frames, int spp, int 
  * NULL) receives each frame's reduced image. */
 int kdpt_render_sharded(const kdpt_scene *scene, const kdpt_options *opt, int ndev, const int *devices,
                         int first_frame, int frames, int spp, int pipeline, int batch, int reduce, float *out);
+
+/* ---- Ray queries: closest hits for caller-supplied rays ----
+ * Record i is what pathTraceOneBounceKDbare (src/pathtrace.cu:1489-1662) computes for ray i before scatterRay:
+ * the analytic geoms, then the KD traversal the context's short_stack option selects (traverseKDbareShortHybrid
+ * or traverseKDbare), on the context's current tree route, cull and tuning knobs -- the hit the path tracer
+ * gets for the same ray, bit for bit.  Closest hit only, with the reference's semantics (its single-sided
+ * triangle test, the hybrid walk's skip line).  There is no t_max and no any-hit mode: the hybrid walk's
+ * visiting order depends on the hits found so far, so a bounded query would not equal "this hit, filtered".
+ *
+ * origins / directions: 3*n floats each; out: n records; each pointer may be host memory or memory of the
+ * context's device (told apart with hipPointerGetAttributes, as kdpt_write_pbo does).  n == 0 returns KDPT_OK
+ * and touches nothing; n < 0, a null pointer with n > 0 or an unknown flag bit is KDPT_ERR_ARG.
+ *
+ * Directions must be unit length: the cluster cull takes n . d as a cosine ("Cluster cull"), so
+ * this is a correctness condition.  With KDPT_CAST_NORMALIZE each direction first goes through the
+ * reference's glm::normalize (t is then along the unit direction).  Without it a direction is accepted only
+ * when |dot(d, d) - 1| <= 1e-6 in float arithmetic: every output of the float normalize passes (its three
+ * roundings keep the squared length within about 6e-7 of 1), nothing much longer or shorter than what the
+ * path tracer itself traces does, and the cull's margins hold for that range ("Ray queries").
+ * A ray with a non-finite origin or direction component, a zero direction, a direction whose normalisation is
+ * not finite or (without the flag) a non-unit direction is rejected: its record has kind KDPT_HIT_INVALID and
+ * it is never traced, whether the arrays live on the host or on the device.
+ *
+ * Synchronous: waits for the work already queued on the context (as kdpt_synchronize does), runs, and
+ * returns with `out` filled.  The accumulation image, kdpt_stats, the iteration counter, the pipeline slots
+ * and every buffer of the render path are left alone.  The rays go through in chunks of "cast_chunk" rays
+ * (kdpt_set_tuning; default 1 << 20, at least 64) whatever the image resolution; the query's buffers are
+ * allocated on first use.  KDPT_ERR_UNSUPPORTED for contexts with enable_kd = 0 or viz_kd = 1. */
+#define KDPT_HIT_INVALID  -1   /* the ray was rejected (see above); never traced */
+#define KDPT_HIT_NONE      0
+#define KDPT_HIT_GEOM      1   /* prim = index into scene->geoms */
+#define KDPT_HIT_TRIANGLE  2   /* prim = index into scene->tris (TriBare order) */
+typedef struct kdpt_ray_hit {  /* 40 bytes */
+    float t;          /* the reference's t_min of the winning hit; -1 when kind <= 0 */
+    int kind;
+    int prim;         /* -1 when kind <= 0 */
+    int material;     /* geoms[prim].materialid, or the triangle's objMaterialIdx; -1 when kind <= 0 */
+    float point[3];   /* intersect_point, as pathTraceOneBounceKDbare hands it to scatterRay; 0 when kind <= 0 */
+    float normal[3];  /* likewise the normal */
+} kdpt_ray_hit;
+
+#define KDPT_CAST_NORMALIZE 1  /* apply the reference's glm::normalize to each direction first */
+int kdpt_cast_rays(kdpt_ctx *ctx, const float *origins, const float *directions, long long n,
+                   int flags, kdpt_ray_hit *out);
+/* Since create/reset: the rays cast, those of them that reached the KD traversal kernel (their ray meets the
+ * KD root box; rejected rays never do), and the last kdpt_cast_rays' time on the device (hipEvents around its
+ * launches and staging copies on the context's stream). */
+int kdpt_cast_stats(kdpt_ctx *ctx, long long *rays, long long *traced, double *device_ms);
+
 int kdpt_destroy(kdpt_ctx *ctx);
 const char *kdpt_last_error(void);
 

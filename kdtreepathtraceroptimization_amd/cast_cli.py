@@ -1,0 +1,110 @@
+"""Ray queries from the command line: closest hits for a file of rays, or for the scene camera's rays.
+
+    python -m kdtreepathtraceroptimization_amd.cast_cli SCENE.txt [MESH.obj] --rays RAYS.npy --out HITS.npy
+    python -m kdtreepathtraceroptimization_amd.cast_cli SCENE.txt [MESH.obj] --camera --out BASE
+
+--rays takes an n x 6 float32 array (origin, direction per row) and writes the n hit records
+(runtime.RAY_HIT_DTYPE: t, kind, prim, material, point, normal) to --out.  --camera casts the scene camera's
+un-jittered pinhole rays (generateRayFromCamera, src/pathtrace.cu:315-397, without antialiasing and depth of
+field) and writes BASE.depth.npy (H x W float32, t; -1 where nothing is hit), BASE.normal.npy (H x W x 3) and
+BASE.prim.npy (H x W x 2 int32: kind, prim).  Rows are in the path tracer's pixel order (index = y W + x; the
+saved PNGs are that image flipped in x).  One JSON line reports the counts and the rate.
+
+Directions are normalised with the reference's glm::normalize unless --no-normalize is given; then a direction
+that is not unit length (|dot(d, d) - 1| > 1e-6) is rejected, like any ray with a non-finite component (kind -1).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+import time
+
+import numpy as np
+
+
+def camera_rays(camera_bytes: bytes):
+    """(origins, directions), each (W H, 3) float32: the pinhole ray of every pixel of a kdpt_camera (84 bytes,
+    runtime.Camera), index = y W + x, with the float32 operations of generateRayFromCamera in its order --
+    normalize(view - right * pixelLength.x * (x - W / 2) - up * pixelLength.y * (y - H / 2)) from the eye."""
+    from .runtime import Camera
+    cam = Camera.from_buffer_copy(camera_bytes)
+    f32 = np.float32
+    W, H = int(cam.resolution[0]), int(cam.resolution[1])
+    view, up, right = (np.array(v[:], f32) for v in (cam.view, cam.up, cam.right))
+    px, py = f32(cam.pixelLength[0]), f32(cam.pixelLength[1])
+    ys, xs = np.divmod(np.arange(W * H, dtype=np.int64), W)
+    fx = xs.astype(f32) - f32(W) * f32(0.5)
+    fy = ys.astype(f32) - f32(H) * f32(0.5)
+    a = (right * px)[None, :] * fx[:, None]  # (vec * float) * float
+    b = (up * py)[None, :] * fy[:, None]
+    v = (view[None, :] - a) - b
+    sq = v * v
+    inv = f32(1.0) / np.sqrt((sq[:, 0] + sq[:, 1]) + sq[:, 2])  # glm::normalize = x * inversesqrt(dot(x, x))
+    d = (v * inv[:, None]).astype(f32)
+    o = np.broadcast_to(np.array(cam.position[:], f32), (W * H, 3)).copy()
+    return o, d
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    ap = argparse.ArgumentParser(prog="python -m kdtreepathtraceroptimization_amd.cast_cli",
+                                 description="Closest hits of caller-supplied rays (kdpt_cast_rays) on MI355X.")
+    ap.add_argument("scene", help="scene text file (scenes/*.txt)")
+    ap.add_argument("mesh", nargs="?", default=None, help="optional OBJ mesh")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--rays", default=None, metavar="RAYS.npy", help="n x 6 float32: origin, direction per row")
+    src.add_argument("--camera", action="store_true", help="the scene camera's un-jittered pinhole rays")
+    ap.add_argument("--out", required=True, help="HITS.npy (--rays) or the base name of the passes (--camera)")
+    ap.add_argument("--res", type=int, nargs=2, default=None, metavar=("W", "H"), help="camera resolution override")
+    ap.add_argument("--bare", action="store_true", help="traverseKDbare instead of the short-stack hybrid")
+    ap.add_argument("--no-normalize", action="store_true", help="directions are unit length already")
+    ap.add_argument("--chunk", type=int, default=None, help="rays per chunk (knob cast_chunk)")
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--kd-build", choices=["gpu", "host"], default="gpu")
+    return ap.parse_args(argv)
+
+
+def main(argv=None) -> int:
+    a = parse_args(argv)
+    from .runtime import HIT_GEOM, HIT_INVALID, HIT_NONE, HIT_TRIANGLE, PathTracer, SceneData, default_options
+    if a.rays:
+        rays = np.load(a.rays)
+        if rays.ndim != 2 or rays.shape[1] != 6:
+            raise SystemExit(f"--rays: expected an n x 6 array, got shape {rays.shape}")
+        rays = np.ascontiguousarray(rays, np.float32)
+    sd = SceneData.from_files(a.scene, a.mesh, res=tuple(a.res) if a.res else None,
+                              kd_device=a.device if a.kd_build == "gpu" else None)
+    W, H = sd.resolution
+    if a.camera:
+        o, d = camera_rays(sd.camera_bytes())
+    else:
+        o, d = rays[:, :3], rays[:, 3:]
+    with PathTracer(sd, default_options(short_stack=0 if a.bare else 1), device=a.device) as pt:
+        if a.chunk:
+            pt.set_tuning("cast_chunk", a.chunk)
+        t0 = time.perf_counter()
+        hits = pt.cast_rays(o, d, normalize=not a.no_normalize)
+        dt = time.perf_counter() - t0
+        st = pt.cast_stats()
+    written = []
+    if a.camera:
+        np.save(a.out + ".depth.npy", hits["t"].reshape(H, W))
+        np.save(a.out + ".normal.npy", hits["normal"].reshape(H, W, 3))
+        np.save(a.out + ".prim.npy", np.stack([hits["kind"], hits["prim"]], -1).reshape(H, W, 2))
+        written = [a.out + s for s in (".depth.npy", ".normal.npy", ".prim.npy")]
+    else:
+        np.save(a.out, hits)
+        written = [a.out]
+    n = len(hits)
+    kind = hits["kind"]
+    print(json.dumps({"scene": a.scene, "mesh": a.mesh, "n": n, "traced": st.traced,
+                      "invalid": int(np.sum(kind == HIT_INVALID)),
+                      "hits": {"none": int(np.sum(kind == HIT_NONE)), "geom": int(np.sum(kind == HIT_GEOM)),
+                               "triangle": int(np.sum(kind == HIT_TRIANGLE))},
+                      "seconds": round(dt, 4), "device_ms": round(st.device_ms, 4),
+                      "mrays_per_s": round(n / dt / 1e6, 3) if dt > 0 else None, "written": written}), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

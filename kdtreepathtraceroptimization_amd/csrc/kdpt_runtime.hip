@@ -1598,6 +1598,106 @@ __global__ void k_unpack(PathBuf src, const int* counts, int depth, kdpt_path_se
   out[i] = s;
 }
 
+// ---------------------------------------------------------------------------
+// Ray queries (kdpt_cast_rays): caller-supplied rays through the intersect stage of the path tracer, one
+// chunk at a time -- k_cast_prep (validation + the stage's first part, geoms_core), k_trace (unchanged, a batch
+// of one "iteration" at depth 0 over the query's own queue) and k_cast_resolve (the hit code turned into a
+// kdpt_ray_hit with the calls shade_one makes).  No PathSegment, iteration number or image is involved.
+// ---------------------------------------------------------------------------
+struct CastArgs {
+  DevScene S;
+  const float* o;  // the chunk's origins and directions (3 n floats each), device memory
+  const float* d;
+  int n;
+  int normalize;   // KDPT_CAST_NORMALIZE
+  float4* cray;    // the query's own candidate queue and hit records (one chunk)
+  int2* hits;
+  int* cand;
+  int* cnt;        // [0] k_trace's work counter, [1] the chunk's candidate count
+  unsigned long long* tt;  // [0..1] k_trace's launch record (TraceArgs::trace_t), [2] candidates summed over the call
+  kdpt_ray_hit* out;
+};
+constexpr int CAST_REJECTED = (int)0x80000000;  // hits[i].y of a rejected ray (objMaterialIdx never takes it)
+
+// The chunk's ray i as it is traced: false = rejected (a non-finite component, a zero direction or one whose
+// normalisation is not finite, or a direction that is not unit length: |dot(d, d) - 1| > 1e-6 in float).
+__device__ __attribute__((always_inline)) inline bool cast_load(const CastArgs& A, int i, f3& o, f3& d) {
+  o = mk3(A.o[3 * (size_t)i], A.o[3 * (size_t)i + 1], A.o[3 * (size_t)i + 2]);
+  d = mk3(A.d[3 * (size_t)i], A.d[3 * (size_t)i + 1], A.d[3 * (size_t)i + 2]);
+  bool ok = fabsf(o.x) < FLT_INFV && fabsf(o.y) < FLT_INFV && fabsf(o.z) < FLT_INFV && fabsf(d.x) < FLT_INFV &&
+            fabsf(d.y) < FLT_INFV && fabsf(d.z) < FLT_INFV;
+  if (A.normalize) d = normalize(d);  // glm::normalize, as the camera and the scatter form their directions
+  ok = ok && fabsf(d.x) < FLT_INFV && fabsf(d.y) < FLT_INFV && fabsf(d.z) < FLT_INFV;
+  return ok && fabsf(dot(d, d) - 1.0f) <= 1e-6f;
+}
+
+// One lane per ray of the chunk; zeroes the work counter and the launch record of the k_trace that follows
+// (as gen_rays_body does for an iteration).  The candidate count is zero on entry: k_cast_resolve of the
+// previous chunk (or the call's fill on the context's stream) left it so.
+__global__ __launch_bounds__(GEN_BLOCK) void k_cast_prep(CastArgs A) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0) {
+    A.cnt[0] = 0;
+    A.tt[0] = ~0ull;
+    A.tt[1] = 0ull;
+  }
+  f3 o = mk3(0, 0, 0), d = mk3(0, 0, 1);
+  bool live = false;
+  if (i < A.n) {
+    live = cast_load(A, i, o, d);
+    if (!live) A.hits[i] = make_int2(-1, CAST_REJECTED);
+  }
+  geoms_core<GEN_BLOCK>(A.S, live, i, o, d, A.cray, A.hits, A.cand, A.cnt + 1, nullptr);
+}
+
+// (code, objMaterialIdx) + the ray -> kdpt_ray_hit: t, point and normal recomputed exactly as shade_one
+// recomputes them for scatterRay.  A triangle's code indexes tv0 / tn0, the TriBare order of scene->tris (the
+// clustered routes carry that index in e1.w).
+template <bool HYBRID>
+__global__ __launch_bounds__(256) void k_cast_resolve(CastArgs A) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0) {  // k_trace is done with the chunk's candidate count: add it up, and zero it for the next chunk
+    A.tt[2] += (unsigned long long)A.cnt[1];
+    A.cnt[1] = 0;
+  }
+  if (i >= A.n) return;
+  const DevScene& S = A.S;
+  const int2 hr = A.hits[i];
+  f3 o, d;
+  (void)cast_load(A, i, o, d);
+  float t = -1.0f;
+  int kind = hr.y == CAST_REJECTED ? KDPT_HIT_INVALID : KDPT_HIT_NONE, prim = -1, mid = -1;
+  f3 ip = mk3(0, 0, 0), nrm = mk3(0, 0, 0);
+  if (hr.x < -1) {  // triangle: the traversal's final recomputation, repeated
+    const int k = -hr.x - 2;
+    float bx, by, bzk;
+    tri_test_v(TriData{S.tv0[k], S.te1[k], S.te2[k]}, o, d, bx, by, bzk);
+    t = tri_hit_t_n<HYBRID>(S.tn0[k], S.tn1[k], S.tn2[k], o, d, bx, by, bzk, ip, nrm);
+    kind = KDPT_HIT_TRIANGLE;
+    prim = k;
+    mid = hr.y;
+  } else if (hr.x >= 0) {
+    const DevGeom& G = S.geoms[hr.x];
+    Ray ray;
+    ray.origin = o;
+    ray.direction = d;
+    ray.isinside = false;
+    ray.sdepth = 0.0f;
+    t = G.type == 1 ? boxIntersectionTest(G, ray, ip, nrm) : sphereIntersectionTest(G, ray, ip, nrm);
+    kind = KDPT_HIT_GEOM;
+    prim = hr.x;
+    mid = G.materialid;
+  }
+  kdpt_ray_hit r;
+  r.t = t;
+  r.kind = kind;
+  r.prim = prim;
+  r.material = mid;
+  r.point[0] = ip.x; r.point[1] = ip.y; r.point[2] = ip.z;
+  r.normal[0] = nrm.x; r.normal[1] = nrm.y; r.normal[2] = nrm.z;
+  A.out[i] = r;
+}
+
 __global__ void k_selftest_math(const float* x, int n, float* so, float* co) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) { so[i] = kdpt_sinf(x[i]); co[i] = kdpt_cosf(x[i]); }
@@ -1773,6 +1873,21 @@ struct kdpt_ctx {
   hipStream_t reduce_stream = nullptr;  // the frames' reduces and image adds, beside the accumulation stream
   double reduce_spin_us = 0;  // "reduce_spin_us" knob: a device spin before every frame's reduce (a slow peer)
   std::vector<void*> host_reg;  // pageable host `out` ranges pinned for kdpt_render_frames (released at synchronize)
+  // ray queries (kdpt_cast_rays): buffers of one chunk, made on first use and remade when "cast_chunk" changes --
+  // the input and output staging buffers (host arrays go through them), the query's own candidate queue, hit
+  // records and counters (CastArgs); nothing here is shared with the render path
+  int cast_chunk = 1 << 20;     // "cast_chunk" knob: rays per chunk
+  int cast_alloc = 0;           // the chunk size the buffers below were made for (0: none yet)
+  float* cast_in = nullptr;     // [6 chunk] origins, then directions
+  kdpt_ray_hit* cast_out = nullptr;  // [chunk]
+  float4* cast_cray = nullptr;  // [2 chunk]
+  int* cast_cand = nullptr;     // [chunk]
+  int2* cast_hits = nullptr;    // [chunk]
+  int* cast_cnt = nullptr;      // [2]
+  unsigned long long* cast_tt = nullptr;  // [3]
+  hipEvent_t cast_ev[2] = {nullptr, nullptr};
+  long long cast_rays = 0, cast_traced = 0;  // since create/reset (kdpt_cast_stats)
+  double cast_ms = 0;                        // the last call's device time
 };
 
 namespace {
@@ -1817,6 +1932,7 @@ int dupload(kdpt_ctx* c, T** p, const T* src, size_t n) {
 int launch_iteration(kdpt_ctx* c, int iter, int stop_depth, bool count);
 void release_comm(kdpt_ctx* c);  // (multi-GPU section, end of file)
 void unregister_host(kdpt_ctx* c);
+void free_cast_buffers(kdpt_ctx* c);  // (ray queries, end of file)
 int launch_batch(kdpt_ctx* const* cs, const int* iters, int nb, hipStream_t st, int stop_depth, bool count,
                  std::vector<hipEvent_t>* bev);
 
@@ -2775,6 +2891,11 @@ int kdpt_set_tuning(kdpt_ctx* c, const char* name, double value) {
   }
   if (!c || !name) return fail(KDPT_ERR_ARG, "null arg");
   if (c->parent) return fail(KDPT_ERR_ARG, "not a top-level context");
+  if (std::string(name) == "cast_chunk") {  // kdpt_cast_rays' chunk; its buffers are remade by the next call
+    if (!(value >= 64.0 && value <= (double)(1 << 26))) return fail(KDPT_ERR_ARG, "cast_chunk must be in 64 .. 2^26");
+    c->cast_chunk = (int)value;
+    return KDPT_OK;
+  }
   HIP_TRY(hipSetDevice(c->device));
   // pipeline slots copy the knobs when they are made: drop them so the next kdpt_trace_iterations
   // makes new ones
@@ -2888,6 +3009,8 @@ int kdpt_reset(kdpt_ctx* c) {
   HIP_TRY(hipStreamSynchronize(c->stream));
   memset(&c->stats, 0, sizeof c->stats);
   c->stats.intersect_grid_share = 1.0f;
+  c->cast_rays = c->cast_traced = 0;
+  c->cast_ms = 0;
   return KDPT_OK;
 }
 
@@ -3221,6 +3344,9 @@ int kdpt_destroy(kdpt_ctx* c) {
   if (c->reduce_stream) (void)hipStreamDestroy(c->reduce_stream);
   for (void* p : c->allocs) (void)hipFree(p);
   if (c->pbo_staging) (void)hipFree(c->pbo_staging);
+  free_cast_buffers(c);
+  for (auto e : c->cast_ev)
+    if (e) (void)hipEventDestroy(e);
   if (c->h_counts) (void)hipHostFree(c->h_counts);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -4079,4 +4205,143 @@ int kdpt_render_sharded(const kdpt_scene* scene, const kdpt_options* opt, int nd
   for (int i = 0; i < ndev; i++)
     if ((rc = kdpt_synchronize(cs[i]))) return cleanup(rc);
   return cleanup(KDPT_OK);
+}
+
+// ---------------------------------------------------------------------------
+// Ray queries (include/kdpt.h "Ray queries"; kernels: k_cast_prep, k_trace, k_cast_resolve)
+// ---------------------------------------------------------------------------
+namespace {
+
+void free_cast_buffers(kdpt_ctx* c) {
+  void* const bufs[] = {c->cast_in, c->cast_out, c->cast_cray, c->cast_cand, c->cast_hits, c->cast_cnt, c->cast_tt};
+  for (void* p : bufs)
+    if (p) (void)hipFree(p);
+  c->cast_in = nullptr;
+  c->cast_out = nullptr;
+  c->cast_cray = nullptr;
+  c->cast_cand = nullptr;
+  c->cast_hits = nullptr;
+  c->cast_cnt = nullptr;
+  c->cast_tt = nullptr;
+  c->cast_alloc = 0;
+}
+
+// The query's buffers for chunks of c->cast_chunk rays (nothing is queued on the context: the caller has
+// synchronised, so the old ones can go).
+int cast_buffers(kdpt_ctx* c) {
+  if (c->cast_alloc == c->cast_chunk) return KDPT_OK;
+  free_cast_buffers(c);
+  const size_t m = (size_t)c->cast_chunk;
+  if (hipMalloc((void**)&c->cast_in, sizeof(float) * 6 * m) != hipSuccess ||
+      hipMalloc((void**)&c->cast_out, sizeof(kdpt_ray_hit) * m) != hipSuccess ||
+      hipMalloc((void**)&c->cast_cray, sizeof(float4) * 2 * m) != hipSuccess ||
+      hipMalloc((void**)&c->cast_cand, sizeof(int) * m) != hipSuccess ||
+      hipMalloc((void**)&c->cast_hits, sizeof(int2) * m) != hipSuccess ||
+      hipMalloc((void**)&c->cast_cnt, sizeof(int) * 2) != hipSuccess ||
+      hipMalloc((void**)&c->cast_tt, sizeof(unsigned long long) * 3) != hipSuccess) {
+    (void)hipGetLastError();
+    free_cast_buffers(c);
+    return fail(KDPT_ERR_HIP, "kdpt_cast_rays: cannot allocate the buffers of a " + std::to_string(m) +
+                                  "-ray chunk (knob cast_chunk)");
+  }
+  for (auto& e : c->cast_ev)
+    if (!e) HIP_TRY(hipEventCreate(&e));
+  c->cast_alloc = c->cast_chunk;
+  return KDPT_OK;
+}
+
+// Is p memory of the context's device (as kdpt_write_pbo tells its pbo apart)?
+bool on_context_device(const kdpt_ctx* c, const void* p) {
+  hipPointerAttribute_t attr{};
+  const bool dev = hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeDevice &&
+                   attr.device == c->device;
+  (void)hipGetLastError();  // a plain host pointer is an error for hipPointerGetAttributes on some runtimes
+  return dev;
+}
+
+}  // namespace
+
+int kdpt_cast_rays(kdpt_ctx* c, const float* origins, const float* directions, long long n, int flags,
+                   kdpt_ray_hit* out) {
+  if (n < 0) return fail(KDPT_ERR_ARG, "kdpt_cast_rays: n must be >= 0");
+  if (flags & ~KDPT_CAST_NORMALIZE) return fail(KDPT_ERR_ARG, "kdpt_cast_rays: unknown bit in flags");
+  if (!c) return fail(KDPT_ERR_ARG, "kdpt_cast_rays: null ctx");
+  if (n > 0 && !origins) return fail(KDPT_ERR_ARG, "kdpt_cast_rays: null origins");
+  if (n > 0 && !directions) return fail(KDPT_ERR_ARG, "kdpt_cast_rays: null directions");
+  if (n > 0 && !out) return fail(KDPT_ERR_ARG, "kdpt_cast_rays: null out");
+  if (c->parent) return fail(KDPT_ERR_ARG, "kdpt_cast_rays: not a top-level context");
+  if (c->brute || c->viz)
+    return fail(KDPT_ERR_UNSUPPORTED, "kdpt_cast_rays: the context runs the brute-force or box-view intersect kernel "
+                                      "(enable_kd = 0 / viz_kd = 1); ray queries need the KD traversal");
+  if (n == 0) return KDPT_OK;
+  int rc = kdpt_synchronize(c);  // everything queued on the context first
+  if (rc) return rc;
+  if ((rc = cast_buffers(c))) return rc;
+  const hipStream_t st = c->stream;
+  const bool o_dev = on_context_device(c, origins), d_dev = on_context_device(c, directions),
+             out_dev = on_context_device(c, out);
+  const int chunk = c->cast_alloc;
+  HIP_TRY(hipMemsetAsync(c->cast_cnt, 0, sizeof(int) * 2, st));
+  HIP_TRY(hipMemsetAsync(c->cast_tt, 0, sizeof(unsigned long long) * 3, st));
+  HIP_TRY(hipEventRecord(c->cast_ev[0], st));
+  CastArgs a;
+  a.S = c->S;
+  a.normalize = (flags & KDPT_CAST_NORMALIZE) ? 1 : 0;
+  a.cray = c->cast_cray;
+  a.hits = c->cast_hits;
+  a.cand = c->cast_cand;
+  a.cnt = c->cast_cnt;
+  a.tt = c->cast_tt;
+  TraceArgs t;
+  t.S = c->S;
+  t.nb = 1;
+  t.prof_steps = 0;
+  for (int b = 0; b < MAXB; b++) t.it[b] = TraceIter{c->cast_cand, c->cast_cnt + 1, c->cast_cray, c->cast_hits};
+  t.work = c->cast_cnt;
+  t.depth = 0;
+  t.counters = c->counters;
+  t.trace_t = c->cast_tt;
+  for (long long off = 0; off < n; off += chunk) {
+    const int m = (int)std::min<long long>(chunk, n - off);
+    a.n = m;
+    a.o = origins + 3 * off;
+    a.d = directions + 3 * off;
+    if (!o_dev) {
+      HIP_TRY(hipMemcpyAsync(c->cast_in, a.o, sizeof(float) * 3 * (size_t)m, hipMemcpyHostToDevice, st));
+      a.o = c->cast_in;
+    }
+    if (!d_dev) {
+      HIP_TRY(hipMemcpyAsync(c->cast_in + 3 * (size_t)chunk, a.d, sizeof(float) * 3 * (size_t)m,
+                             hipMemcpyHostToDevice, st));
+      a.d = c->cast_in + 3 * (size_t)chunk;
+    }
+    a.out = out_dev ? out + off : c->cast_out;
+    hipLaunchKernelGGL(k_cast_prep, dim3((m + GEN_BLOCK - 1) / GEN_BLOCK), dim3(GEN_BLOCK), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    launch_trace(c, t, false, st);
+    HIP_TRY(hipGetLastError());
+    if (c->opt.short_stack) hipLaunchKernelGGL(k_cast_resolve<true>, dim3((m + 255) / 256), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_cast_resolve<false>, dim3((m + 255) / 256), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    if (!out_dev)
+      HIP_TRY(hipMemcpyAsync(out + off, c->cast_out, sizeof(kdpt_ray_hit) * (size_t)m, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(hipEventRecord(c->cast_ev[1], st));
+  unsigned long long traced = 0;
+  HIP_TRY(hipMemcpyAsync(&traced, c->cast_tt + 2, sizeof traced, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  float ms = 0;
+  HIP_TRY(hipEventElapsedTime(&ms, c->cast_ev[0], c->cast_ev[1]));
+  c->cast_ms = ms;
+  c->cast_rays += n;
+  c->cast_traced += (long long)traced;
+  return check_fault(c);
+}
+
+int kdpt_cast_stats(kdpt_ctx* c, long long* rays, long long* traced, double* device_ms) {
+  if (!c) return fail(KDPT_ERR_ARG, "kdpt_cast_stats: null ctx");
+  if (rays) *rays = c->cast_rays;
+  if (traced) *traced = c->cast_traced;
+  if (device_ms) *device_ms = c->cast_ms;
+  return KDPT_OK;
 }

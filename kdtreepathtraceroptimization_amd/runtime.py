@@ -14,7 +14,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -103,6 +103,23 @@ class SceneDesc(C.Structure):
                 ("shape_materials", C.POINTER(Material)), ("kd_max_depth", C.c_int)]
 
 
+class RayHit(C.Structure):  # kdpt_ray_hit: one record of kdpt_cast_rays
+    _fields_ = [("t", C.c_float), ("kind", C.c_int), ("prim", C.c_int), ("material", C.c_int),
+                ("point", C.c_float * 3), ("normal", C.c_float * 3)]
+
+
+HIT_INVALID, HIT_NONE, HIT_GEOM, HIT_TRIANGLE = -1, 0, 1, 2  # kdpt_ray_hit.kind (KDPT_HIT_*)
+CAST_NORMALIZE = 1  # kdpt_cast_rays flag (KDPT_CAST_NORMALIZE)
+RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("kind", "<i4"), ("prim", "<i4"), ("material", "<i4"),
+                          ("point", "<f4", 3), ("normal", "<f4", 3)])
+assert C.sizeof(RayHit) == 40 and RAY_HIT_DTYPE.itemsize == 40
+
+
+class CastStats(NamedTuple):  # kdpt_cast_stats
+    rays: int         # rays cast since create/reset
+    traced: int       # ... of which reached the KD traversal kernel
+    device_ms: float  # the last cast's device time
+
 assert C.sizeof(Geom) == 236 and C.sizeof(Material) == 56 and C.sizeof(Camera) == 84
 assert C.sizeof(NodeBare) == 64 and C.sizeof(TriBare) == 76 and C.sizeof(PathSegment) == 56
 
@@ -115,7 +132,7 @@ EXPORTS = [
     "kdpt_write_hdr", "kdpt_free", "kdpt_set_tuning", "kdpt_selftest_glm", "kdpt_set_options", "kdpt_scene_build_device",
     "kdpt_scene_kd_build_ms", "kdpt_build_kd_device", "kdpt_scene_load_device", "kdpt_trace_config",
     "kdpt_cull_margin", "kdpt_comm_unique_id", "kdpt_comm_init", "kdpt_render_frames", "kdpt_render_sharded",
-    "kdpt_comm_library", "kdpt_cull_masks",
+    "kdpt_comm_library", "kdpt_cull_masks", "kdpt_cast_rays", "kdpt_cast_stats",
 ]
 
 REDUCE_RCCL, REDUCE_COPY = 0, 1  # kdpt_render_sharded's reduce (KDPT_REDUCE_*)
@@ -209,6 +226,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.kdpt_selftest_glm.argtypes = [C.c_int, P(C.c_float), C.c_int, P(C.c_float)]
     if hasattr(lib, "kdpt_set_tuning"):  # absent from older builds used in A/B runs
         lib.kdpt_set_tuning.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
+    if hasattr(lib, "kdpt_cast_rays"):  # absent from older builds used in A/B runs
+        lib.kdpt_cast_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]
+        lib.kdpt_cast_stats.argtypes = [C.c_void_p, P(C.c_longlong), P(C.c_longlong), P(C.c_double)]
     _lib = lib
     return lib
 
@@ -463,8 +483,37 @@ class PathTracer:
         self.opt = options
 
     def set_tuning(self, name: str, value: float):
-        """kdpt_set_tuning: an explicit A/B or diagnostic knob (the library reads no environment)."""
+        """kdpt_set_tuning: an explicit A/B or diagnostic knob (the library reads no environment); the names
+        are listed at kdpt_set_tuning in include/kdpt.h, e.g. "cast_chunk" (rays per chunk of cast_rays,
+        default 1 << 20, at least 64)."""
         _check(self.lib.kdpt_set_tuning(self._ctx, name.encode(), float(value)), f"kdpt_set_tuning({name})")
+
+    def cast_rays(self, origins, directions, normalize: bool = True) -> np.ndarray:
+        """kdpt_cast_rays on host arrays: the closest hit of each ray (origins, directions: n x 3 float32), as a
+        RAY_HIT_DTYPE array of n records -- what the path tracer's intersect stage computes for that ray.
+        normalize=True applies the reference's glm::normalize to each direction; otherwise directions must be
+        unit length (|dot(d, d) - 1| <= 1e-6) or the ray is rejected (kind HIT_INVALID)."""
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError(f"{len(o)} origins but {len(d)} directions")
+        out = np.empty(len(o), dtype=RAY_HIT_DTYPE)
+        self.cast_rays_ptr(o.ctypes.data, d.ctypes.data, len(o), out.ctypes.data, normalize=normalize)
+        return out
+
+    def cast_rays_ptr(self, origins_ptr: int, directions_ptr: int, n: int, out_ptr: int, normalize: bool = True):
+        """kdpt_cast_rays on raw pointers, each host memory or memory of the context's device (e.g. a torch
+        tensor's data_ptr()): 3 n floats, 3 n floats, n 40-byte records.  Synchronous."""
+        _check(self.lib.kdpt_cast_rays(self._ctx, C.c_void_p(int(origins_ptr)), C.c_void_p(int(directions_ptr)),
+                                       int(n), CAST_NORMALIZE if normalize else 0, C.c_void_p(int(out_ptr))),
+               "kdpt_cast_rays")
+
+    def cast_stats(self) -> "CastStats":
+        """kdpt_cast_stats: rays cast and rays that reached the KD traversal kernel since create/reset, and the
+        last cast's device time in ms."""
+        r, t, ms = C.c_longlong(), C.c_longlong(), C.c_double()
+        _check(self.lib.kdpt_cast_stats(self._ctx, C.byref(r), C.byref(t), C.byref(ms)), "kdpt_cast_stats")
+        return CastStats(int(r.value), int(t.value), float(ms.value))
 
     def reset(self):
         _check(self.lib.kdpt_reset(self._ctx), "kdpt_reset")
