@@ -1761,10 +1761,52 @@ __global__ void k_selftest_fresnel(const float* c, int n, float R0, float* f) {
 // ---------------------------------------------------------------------------
 // Context
 // ---------------------------------------------------------------------------
+// One iteration's working set (alloc_iter / free_iter).  The context has one for the one-at-a-time entry points
+// and B per pipeline group; everything an iteration shares with the others (scene, options, knobs, counters)
+// stays in the context.
+struct IterState {
+  std::vector<void*> allocs;  // the device memory below
+  PathBuf buf[2]{};
+  int cur = 0;
+  int* counts = nullptr;  // [cap + 2] live paths per bounce, [1] fault word, then [cap] work counters, ...
+  int* fault = nullptr;
+  int* work = nullptr;
+  int* ccount = nullptr;    // [cap] walking survivors per bounce
+  int* tickets = nullptr;   // [cap] k_shade_fused's tile tickets
+  int* ccount0 = nullptr;   // [2] bounce-0 candidate counters of k_gen_geoms_b (alternating uses)
+  int gen_parity = 0;       // which of them the next use counts into
+  int* cc0_cur = nullptr;   // this use's (bounce 0 reads it instead of ccount[0])
+  int2* hits = nullptr;     // [npix] hit code + objMaterialIdx from the intersect kernel
+  float4* cray = nullptr;   // [2 npix] the candidates' rays in queue order (k_geoms / shading -> k_trace)
+  int* cand = nullptr;      // [npix] paths whose ray meets the KD root box (k_geoms -> k_trace)
+  int2* prep = nullptr;     // [npix] next bounce's geoms record + walk flag (k_shade -> k_scatter)
+  int* tile_counts = nullptr;
+  int* tile_off = nullptr;
+  int* tile_ccounts = nullptr;  // [ntiles] walking survivors per tile, and their offsets
+  int* tile_coff = nullptr;
+  unsigned long long* lb = nullptr;       // [cap][ntiles] k_shade_fused's look-back records
+  unsigned long long* trace_t = nullptr;  // per-bounce intersect launch record
+  int* h_counts = nullptr;  // pinned
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  std::vector<hipEvent_t> bounce_ev;
+  // where the iteration's light goes: the context's image, or a pipeline state's own partial image, which
+  // k_gen_rays zeroes first (zero_partial); and where its segment count is added
+  float* image = nullptr;
+  bool zero_partial = false;
+  unsigned long long* total_segments = nullptr;
+};
+
+// A pipeline group: `batch` iterations at a time in lockstep on the group's own stream; acc_ev: its last
+// batch's add into the target done.
+struct IterGroup {
+  hipStream_t stream = nullptr;
+  hipEvent_t acc_ev = nullptr;
+  std::vector<std::unique_ptr<IterState>> its;
+};
+
 struct kdpt_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
-  bool owns_stream = true;  // false: a pipeline group member, running on its group leader's stream
   kdpt_options opt{};
   kdpt_camera cam{};
   int traceDepth = 0;
@@ -1774,23 +1816,11 @@ struct kdpt_ctx {
   // owned device memory
   std::vector<void*> allocs;
   uchar4* pbo_staging = nullptr;  // kdpt_write_pbo into host memory
-  PathBuf buf[2]{};
-  int cur = 0;
+  IterState solo;         // kdpt_trace_iteration[_async], kdpt_debug_paths, kdpt_count_iteration; into `image`
   float* image = nullptr;
   bool image_external = false;
-  int* counts = nullptr;  // [cap + 2] live paths per bounce, [cap + 2] fault flag, then [cap] work counters
-  int* work = nullptr;
-  int2* hits = nullptr;   // [npix] hit code + objMaterialIdx from the intersect kernel
-  float4* cray = nullptr;   // [2 npix] the candidates' rays in queue order (k_geoms / shading -> k_trace)
-  int* cand = nullptr;      // [npix] paths whose ray meets the KD root box (k_geoms -> k_trace)
-  int2* prep = nullptr;     // [npix] next bounce's geoms record + walk flag (k_shade -> k_scatter)
-  int* tile_ccounts = nullptr;  // [ntiles] walking survivors per tile, and their offsets
-  int* tile_coff = nullptr;
-  int* ccount = nullptr;    // [cap] their number per bounce (inside the counts allocation)
-  int* tickets = nullptr;   // [cap] k_shade_fused's tile tickets (inside the counts allocation)
-  unsigned long long* lb = nullptr;  // [cap][ntiles] k_shade_fused's look-back records
   int tree_mode = 0;      // TreeMode
-  int trace_grid = 0;     // persistent intersect workgroups
+  int trace_grid = 0;     // persistent intersect workgroups (a pipelined call's launches take a share of them)
   int full_trace_grid = 0;  // the occupancy-derived grid (trace_grid before a "trace_grid_frac" knob)
   bool grid_env = false;  // trace_grid fixed by the "trace_grid_frac" tuning knob
   bool force_global_tree = false;  // "tree_global" tuning knob: keep the tree in HBM/L2
@@ -1808,49 +1838,30 @@ struct kdpt_ctx {
   std::unique_ptr<ClusterSet> mask_cs;  // the clusters the masks were built from ("cull_mask_n" rebuilds)
   int tree_format = 0;             // "tree_format" knob: 16 / 32 = LDS node records of that size only
   size_t tree_lds = 0;    // dynamic LDS bytes of the intersect kernel (TREE_LDS)
-  int* tile_counts = nullptr;
-  int* tile_off = nullptr;
-  int* tile_kcounts = nullptr;  // trace-order class counts per tile [TRACE_KEYS][ntiles]
-  int* tile_koff = nullptr;
-  int* perm = nullptr;          // trace order of the next bounce
-  bool trace_order = true;      // KDPT_TRACE_ORDER=0 disables (identity order)
   bool no_fuse = false;         // "shade_fused" = 0: k_shade + k_scan + k_scatter instead of k_shade_fused
   bool shade_batch = true;      // "shade_batch": a batch's fused shading in one launch (k_shade_fused_b)
   bool gen_geoms = true;        // "gen_geoms": camera rays + bounce-0 k_geoms in one launch (k_gen_geoms_b)
-  int* ccount0 = nullptr;       // [2] bounce-0 candidate counters of k_gen_geoms_b (alternating uses)
-  int gen_parity = 0;           // which of them the next use counts into
-  int* cc0_cur = nullptr;       // this use's (bounce 0 reads it instead of ccount[0])
-  bool zero_partial = false;    // k_gen_rays zeroes `image` (a pipeline slot's per-iteration partial image)
   int chunk_width[3] = {16, 64, 64};
   Counters* counters = nullptr;
   Counters last_profile{};
   unsigned long long* total_segments = nullptr;  // device running total (async use)
-  unsigned long long* trace_t = nullptr;         // per-bounce intersect launch record (per slot)
   unsigned long long* trace_total = nullptr;     // [3] device-clock intersect ticks, launches, rays (shared)
   double wall_khz = 100000.0;                    // s_memrealtime frequency
-  int* h_counts = nullptr;  // pinned
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  std::vector<hipEvent_t> bounce_ev;
   kdpt_stats stats{};
-  bool count_mode = false;
   bool sync_debug = false;  // "sync_debug" = 1: synchronise and log after every launch
-  // Pipelined iterations (kdpt_trace_iterations): extra slots, each a context sharing this one's
-  // scene upload but owning its per-iteration buffers, stream and partial image; the partial
-  // images are added into `image` in iteration order, each batch's add on the batch's own stream after the
-  // previous batch's add (acc_ev / acc_last: the chain).
-  kdpt_ctx* parent = nullptr;
-  std::vector<kdpt_ctx*> slots;
-  int slot_batch = 1;
-  int next_group = 0;  // the slot group the next batch goes to
+  // Pipelined iterations (kdpt_trace_iterations): groups of `group_batch` iteration states, each state with a
+  // partial image of its own; the partial images are added into `image` in iteration order, each batch's add
+  // on its group's stream after the previous batch's add (acc_ev / acc_last: the chain).
+  std::vector<IterGroup> groups;
+  int group_batch = 1;
+  int next_group = 0;  // the group the next batch goes to
   bool profile_batches = false;
   bool profile_steps = false;  // "profile_batches" = 2
-  std::vector<hipEvent_t> acc_ev;  // per slot group: its last batch's add into the target done
-  hipEvent_t acc_last = nullptr;   // the most recent add (one of acc_ev): the next add follows it
+  hipEvent_t acc_last = nullptr;   // the most recent add (a group's acc_ev): the next add follows it
   hipEvent_t img_last = nullptr;   // the most recent frame reduce + image add (one of frame_ev)
   // intersect-kernel timing (testing_mode) of every iteration, read back at synchronisation
   std::vector<std::vector<hipEvent_t>> pending_ev;  // per launched iteration: 2 events per bounce
   std::vector<hipEvent_t> free_ev;
-  std::vector<hipEvent_t>* rec_ev = nullptr;  // when set, launch_iteration records the bounce events here
   double intersect_ms_total = 0;
   long long intersect_launches_total = 0;
   // enable_kd = 0: brute-force intersect kernel over the OBJ triangles in file order
@@ -1912,8 +1923,8 @@ int create_stream(kdpt_ctx* c, hipStream_t* st) {
   return KDPT_OK;
 }
 
-template <typename T>
-int dalloc(kdpt_ctx* c, T** p, size_t n) {
+template <typename Owner, typename T>  // a context or an iteration state
+int dalloc(Owner* c, T** p, size_t n) {
   void* q = nullptr;
   HIP_TRY(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
   c->allocs.push_back(q);
@@ -1933,8 +1944,8 @@ int launch_iteration(kdpt_ctx* c, int iter, int stop_depth, bool count);
 void release_comm(kdpt_ctx* c);  // (multi-GPU section, end of file)
 void unregister_host(kdpt_ctx* c);
 void free_cast_buffers(kdpt_ctx* c);  // (ray queries, end of file)
-int launch_batch(kdpt_ctx* const* cs, const int* iters, int nb, hipStream_t st, int stop_depth, bool count,
-                 std::vector<hipEvent_t>* bev);
+int launch_batch(kdpt_ctx* c, IterState* const* its, const int* iters, int nb, hipStream_t st, int trace_grid,
+                 int stop_depth, bool count, std::vector<hipEvent_t>* bev);
 
 // Work queued on the context's own stream that reads or writes `image` must follow the pipelined
 // accumulation (kdpt_trace_iterations adds partial images on the batch streams without a host sync) and the
@@ -1946,140 +1957,108 @@ int join_accum(kdpt_ctx* c) {
 }
 
 
-// stats.segments / seg_per_bounce / bounces of the iteration whose counts are in h_counts
+// stats.segments / seg_per_bounce / bounces of the iteration whose counts are in the solo state's h_counts
 int segments_from_counts(kdpt_ctx* c) {
+  const int* h_counts = c->solo.h_counts;
   long long seg = 0;
   int bounces = 0;
   for (int d = 0; d < 32; d++) c->stats.seg_per_bounce[d] = 0;
   for (int d = 0; d < c->cap; d++) {
-    const int nd = c->h_counts[d];
-    if (d > 0 && c->h_counts[d] <= 0) break;  // the reference stops once num_paths <= 0
+    const int nd = h_counts[d];
+    if (d > 0 && h_counts[d] <= 0) break;  // the reference stops once num_paths <= 0
     seg += nd;
     if (d < 32) c->stats.seg_per_bounce[d] = nd;
     bounces = d + 1;
-    if (c->opt.compaction && c->h_counts[d + 1] <= 0) break;
+    if (c->opt.compaction && h_counts[d + 1] <= 0) break;
   }
   c->stats.segments = seg;
   c->stats.bounces = bounces;
   return bounces;
 }
 
-// Per-iteration device state: two path buffers, hit records, trace order, tile counts/offsets,
-// live counts + fault word + work counters.  (The scene, image and counters live elsewhere.)
-// The zero fills go on the context's own stream and are waited for: every kernel of the context runs on a
-// non-blocking stream, which does not order itself after the null stream, so a plain hipMemset there could
+void free_iter(IterState* it) {
+  for (void* p : it->allocs) (void)hipFree(p);
+  if (it->h_counts) (void)hipHostFree(it->h_counts);
+  if (it->ev0) (void)hipEventDestroy(it->ev0);
+  if (it->ev1) (void)hipEventDestroy(it->ev1);
+  for (auto e : it->bounce_ev)
+    if (e) (void)hipEventDestroy(e);
+  *it = IterState{};
+}
+
+// Per-iteration device state: two path buffers, hit records, candidate queue, tile counts/offsets,
+// live counts + fault word + work counters, and the events.  (The scene, image and counters live elsewhere.)
+// The zero fills go on the stream st the state will run on and are waited for: every kernel of the context runs
+// on a non-blocking stream, which does not order itself after the null stream, so a plain hipMemset there could
 // land after the first iteration's camera-ray kernel had set its path count (that iteration would vanish).
-int alloc_iteration_buffers(kdpt_ctx* c) {
+// partial: with a partial image of its own (a pipeline state); else the caller points `image` at its target.
+// A failed allocation leaves what was made to free_iter.
+int alloc_iter(kdpt_ctx* c, IterState* it, hipStream_t st, bool partial) {
   int rc;
+  const size_t npix = (size_t)c->npix, ntiles = (size_t)c->ntiles, cap = (size_t)c->cap;
   for (int b = 0; b < 2; b++) {
-    if ((rc = dalloc(c, &c->buf[b].p0, c->npix)) || (rc = dalloc(c, &c->buf[b].p1, c->npix)) ||
-        (rc = dalloc(c, &c->buf[b].p2, c->npix)) || (rc = dalloc(c, &c->buf[b].pm, c->npix)))
+    if ((rc = dalloc(it, &it->buf[b].p0, npix)) || (rc = dalloc(it, &it->buf[b].p1, npix)) ||
+        (rc = dalloc(it, &it->buf[b].p2, npix)) || (rc = dalloc(it, &it->buf[b].pm, npix)))
       return rc;
-    HIP_TRY(hipMemsetAsync(c->buf[b].pm, 0, sizeof(int) * c->npix, c->stream));
+    HIP_TRY(hipMemsetAsync(it->buf[b].pm, 0, sizeof(int) * npix, st));
   }
   // counts[0..cap+1]: live paths per bounce (rewritten every iteration); counts[cap+2]: fault flag;
   // counts[cap+3 ..]: work counters of the persistent intersect kernel
-  if ((rc = dalloc(c, &c->trace_t, 4 * (size_t)c->cap))) return rc;
-  HIP_TRY(hipMemsetAsync(c->trace_t, 0, sizeof(unsigned long long) * 4 * c->cap, c->stream));
-  if ((rc = dalloc(c, &c->counts, 4 * (size_t)c->cap + 5)) || (rc = dalloc(c, &c->lb, (size_t)c->cap * c->ntiles)) || (rc = dalloc(c, &c->hits, (size_t)c->npix)) ||
-      (rc = dalloc(c, &c->cand, (size_t)c->npix)) || (rc = dalloc(c, &c->prep, (size_t)c->npix)) ||
-      (rc = dalloc(c, &c->tile_ccounts, (size_t)c->ntiles)) || (rc = dalloc(c, &c->tile_coff, (size_t)c->ntiles)) ||
-      (rc = dalloc(c, &c->cray, 2 * (size_t)c->npix)) ||
-      (rc = dalloc(c, &c->perm, (size_t)c->npix)) ||
-      (rc = dalloc(c, &c->tile_kcounts, (size_t)TRACE_KEYS * c->ntiles)) ||
-      (rc = dalloc(c, &c->tile_koff, (size_t)TRACE_KEYS * c->ntiles)) ||
-      (rc = dalloc(c, &c->tile_counts, (size_t)MAX_KEYS * c->ntiles)) ||
-      (rc = dalloc(c, &c->tile_off, (size_t)MAX_KEYS * c->ntiles)))
+  if ((rc = dalloc(it, &it->trace_t, 4 * cap))) return rc;
+  HIP_TRY(hipMemsetAsync(it->trace_t, 0, sizeof(unsigned long long) * 4 * cap, st));
+  if ((rc = dalloc(it, &it->counts, 4 * cap + 5)) || (rc = dalloc(it, &it->lb, cap * ntiles)) ||
+      (rc = dalloc(it, &it->hits, npix)) || (rc = dalloc(it, &it->cand, npix)) || (rc = dalloc(it, &it->prep, npix)) ||
+      (rc = dalloc(it, &it->tile_ccounts, ntiles)) || (rc = dalloc(it, &it->tile_coff, ntiles)) ||
+      (rc = dalloc(it, &it->cray, 2 * npix)) || (rc = dalloc(it, &it->tile_counts, (size_t)MAX_KEYS * ntiles)) ||
+      (rc = dalloc(it, &it->tile_off, (size_t)MAX_KEYS * ntiles)))
     return rc;
-  if (hipHostMalloc((void**)&c->h_counts, sizeof(int) * (c->cap + 3), hipHostMallocDefault) != hipSuccess)
+  if (hipHostMalloc((void**)&it->h_counts, sizeof(int) * (cap + 3), hipHostMallocDefault) != hipSuccess)
     return fail(KDPT_ERR_HIP, "hipHostMalloc");
-  HIP_TRY(hipMemsetAsync(c->counts, 0, sizeof(int) * (4 * c->cap + 5), c->stream));
-  HIP_TRY(hipMemsetAsync(c->lb, 0, sizeof(unsigned long long) * c->cap * c->ntiles, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  c->S.fault = c->counts + c->cap + 2;
-  c->work = c->counts + c->cap + 3;
-  c->ccount = c->work + c->cap;
-  c->tickets = c->ccount + c->cap;
-  c->ccount0 = c->tickets + c->cap;  // 2 entries, zero
-  c->gen_parity = 0;
+  HIP_TRY(hipMemsetAsync(it->counts, 0, sizeof(int) * (4 * cap + 5), st));
+  HIP_TRY(hipMemsetAsync(it->lb, 0, sizeof(unsigned long long) * cap * ntiles, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  it->fault = it->counts + cap + 2;
+  it->work = it->counts + cap + 3;
+  it->ccount = it->work + cap;
+  it->tickets = it->ccount + cap;
+  it->ccount0 = it->tickets + cap;  // 2 entries, zero
+  it->gen_parity = 0;
+  if (partial) {
+    if ((rc = dalloc(it, &it->image, 3 * npix))) return rc;
+    it->zero_partial = true;  // k_gen_rays clears the partial image
+  }
+  it->total_segments = c->total_segments;
+  HIP_TRY(hipEventCreate(&it->ev0));
+  HIP_TRY(hipEventCreate(&it->ev1));
+  it->bounce_ev.resize(2 * cap);
+  for (auto& e : it->bounce_ev) HIP_TRY(hipEventCreate(&e));
   return KDPT_OK;
 }
 
-int alloc_iteration_events(kdpt_ctx* c) {
-  HIP_TRY(hipEventCreate(&c->ev0));
-  HIP_TRY(hipEventCreate(&c->ev1));
-  c->bounce_ev.resize(2 * (size_t)c->cap);
-  for (auto& e : c->bounce_ev) HIP_TRY(hipEventCreate(&e));
-  return KDPT_OK;
-}
-
-// A pipeline slot: shares p's scene upload and counters, owns its iteration buffers, its stream
-// and a partial image that k_gen_rays' iteration accumulates into.
-// Pipeline slots, members before their group leader (the leader owns the stream they share).
-void destroy_slots(kdpt_ctx* c) {
-  for (size_t k = c->slots.size(); k-- > 0;) kdpt_destroy(c->slots[k]);
-}
-
-// Drop the pipeline slots (their streams drained by the caller) and the add chain's events.
-void drop_slots(kdpt_ctx* c) {
-  destroy_slots(c);
-  for (auto e : c->acc_ev) (void)hipEventDestroy(e);
-  c->slots.clear();
-  c->acc_ev.clear();
+// Drop the pipeline's groups (their streams drained here), last first.
+void drop_groups(kdpt_ctx* c) {
+  for (size_t g = c->groups.size(); g-- > 0;) {
+    IterGroup& grp = c->groups[g];
+    if (grp.stream) (void)hipStreamSynchronize(grp.stream);
+    for (size_t k = grp.its.size(); k-- > 0;) free_iter(grp.its[k].get());
+    if (grp.acc_ev) (void)hipEventDestroy(grp.acc_ev);
+    if (grp.stream) (void)hipStreamDestroy(grp.stream);
+  }
+  c->groups.clear();
   c->acc_last = nullptr;
 }
 
-// share: the stream of the slot's group leader (a group's batches all run on the leader's stream), or null
-// for a leader, which creates its own
-int make_slot(kdpt_ctx* p, kdpt_ctx** out, hipStream_t share = nullptr) {
-  kdpt_ctx* c = new kdpt_ctx();
-  c->parent = p;
-  c->device = p->device;
-  c->opt = p->opt;
-  c->opt.external_image = nullptr;
-  c->cam = p->cam;
-  c->traceDepth = p->traceDepth;
-  c->W = p->W;
-  c->H = p->H;
-  c->npix = p->npix;
-  c->ntiles = p->ntiles;
-  c->nkeys = p->nkeys;
-  c->cap = p->cap;
-  c->S = p->S;
-  c->tree_mode = p->tree_mode;
-  c->trace_grid = p->trace_grid;
-  c->tree_lds = p->tree_lds;
-  c->trace_order = p->trace_order;
-  c->no_fuse = p->no_fuse;
-  c->shade_batch = p->shade_batch;
-  c->gen_geoms = p->gen_geoms;
-  for (int k = 0; k < 3; k++) c->chunk_width[k] = p->chunk_width[k];
-  c->counters = p->counters;
-  c->total_segments = p->total_segments;
-  c->trace_total = p->trace_total;
-  c->wall_khz = p->wall_khz;
-  c->sync_debug = p->sync_debug;
-  c->brute = p->brute;
-  c->viz = p->viz;
-  c->shapes = p->shapes;
-  c->num_shapes = p->num_shapes;
-  c->chunk_lo = p->chunk_lo;
-  c->chunk_hi = p->chunk_hi;
-  c->cu_mask_streams = p->cu_mask_streams;
-  int rc;
-  if (share) {
-    c->stream = share;
-    c->owns_stream = false;
-  } else if (create_stream(c, &c->stream) != KDPT_OK) {
-    kdpt_destroy(c);
-    return fail(KDPT_ERR_HIP, "hipStreamCreate failed");
+// One more pipeline group: its stream, then its B iteration states.
+int make_group(kdpt_ctx* c, int B) {
+  c->groups.emplace_back();
+  IterGroup& grp = c->groups.back();
+  if (create_stream(c, &grp.stream) != KDPT_OK) return fail(KDPT_ERR_HIP, "hipStreamCreate failed");
+  for (int b = 0; b < B; b++) {
+    grp.its.emplace_back(new IterState());
+    int rc = alloc_iter(c, grp.its.back().get(), grp.stream, true);
+    if (rc) return rc;
   }
-  if ((rc = alloc_iteration_buffers(c)) || (rc = dalloc(c, &c->image, 3 * (size_t)c->npix)) ||
-      (rc = alloc_iteration_events(c))) {
-    kdpt_destroy(c);
-    return rc;
-  }
-  *out = c;
+  HIP_TRY(hipEventCreateWithFlags(&grp.acc_ev, hipEventDisableTiming));
   return KDPT_OK;
 }
 
@@ -2463,20 +2442,48 @@ int setup_trace(kdpt_ctx* c) {
 
 // A ray that needs more node steps than any valid tree allows sets the fault word and stops;
 // the iteration then reports an error instead of returning a silently wrong image.
-int fault_error(kdpt_ctx* c, int code) {
-  (void)hipMemsetAsync(c->counts + c->cap + 2, 0, sizeof(int), c->stream);
-  (void)hipStreamSynchronize(c->stream);
+int fault_error(IterState* it, hipStream_t st, int code) {  // st: the (drained) stream the state runs on
+  (void)hipMemsetAsync(it->fault, 0, sizeof(int), st);
+  (void)hipStreamSynchronize(st);
   if (code & 32)
     return fail(KDPT_ERR_HIP, "shading: a path's survival differed from its hit record's prediction, code " +
                                   std::to_string(code));
   return fail(KDPT_ERR_HIP, "KD traversal exceeded its step bound (inconsistent tree), code " + std::to_string(code));
 }
 
-int check_fault(kdpt_ctx* c) {
+int check_fault(IterState* it, hipStream_t st) {
   int f = 0;
-  HIP_TRY(hipMemcpy(&f, c->counts + c->cap + 2, sizeof(int), hipMemcpyDeviceToHost));
-  return f ? fault_error(c, f) : KDPT_OK;
+  HIP_TRY(hipMemcpy(&f, it->fault, sizeof(int), hipMemcpyDeviceToHost));
+  return f ? fault_error(it, st, f) : KDPT_OK;
 }
+
+// The solo state's next iteration into a scratch image and a scratch segment total (zeroed on the context's
+// stream), so that the accumulation image and stats.total_segments stay as they are; the scope's end puts the
+// state's targets back and frees the scratch buffers.
+struct ScratchTargets {
+  IterState& it;
+  float* const image;
+  unsigned long long* const total_segments;
+  void* scratch = nullptr;  // the image, then the total
+  explicit ScratchTargets(IterState& s) : it(s), image(s.image), total_segments(s.total_segments) {}
+  int redirect(kdpt_ctx* c) {
+    const size_t img = sizeof(float) * 3 * (size_t)c->npix;
+    HIP_TRY(hipMalloc(&scratch, img + sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(scratch, 0, img + sizeof(unsigned long long), c->stream));
+    it.image = static_cast<float*>(scratch);
+    it.total_segments = reinterpret_cast<unsigned long long*>(static_cast<char*>(scratch) + img);
+    return KDPT_OK;
+  }
+  ~ScratchTargets() {
+    it.image = image;
+    it.total_segments = total_segments;
+    if (scratch) (void)hipFree(scratch);  // (hipFree waits for whatever an early return left running)
+  }
+};
+
+struct DeviceFree {
+  void operator()(void* p) const { (void)hipFree(p); }
+};
 
 }  // namespace
 
@@ -2804,7 +2811,6 @@ int kdpt_create(const kdpt_scene* sc, const kdpt_options* opt, int device, kdpt_
   } else {
     c->S.has_obj = 0;
   }
-  if ((rc = alloc_iteration_buffers(c))) return bail(rc);
   if (o.external_image) {
     c->image = o.external_image;
     c->image_external = true;
@@ -2814,6 +2820,11 @@ int kdpt_create(const kdpt_scene* sc, const kdpt_options* opt, int device, kdpt_
   if ((rc = dalloc(c, &c->counters, 1)) || (rc = dalloc(c, &c->total_segments, 1)) ||
       (rc = dalloc(c, &c->trace_total, 3)))
     return bail(rc);
+  if ((rc = alloc_iter(c, &c->solo, c->stream, false))) return bail(rc);
+  c->solo.image = c->image;
+  // (the one-at-a-time launches and the ray queries report into the solo state's fault word; a pipelined
+  // launch gets its own states' words, launch_batch)
+  c->S.fault = c->solo.fault;
   {
     int khz = 0;
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0)
@@ -2830,12 +2841,10 @@ int kdpt_create(const kdpt_scene* sc, const kdpt_options* opt, int device, kdpt_
   // 5 798-5 802, C5 4 487 -> 4 544; 8 / 12 / 20 / 32 below 16, early_leaf 8 / 24 neutral; profiles/r05_ab_log.md)
   c->S.early_walk = 16;
   c->S.early_leaf = 1;
-  c->trace_order = false;  // superseded by k_geoms' candidate lists
   if ((rc = setup_trace(c))) return bail(rc);
   c->S.trip_limit = 8 * std::max(c->S.num_nodes, 1) + 64;
-  if ((rc = alloc_iteration_events(c))) return bail(rc);
   // the scene's uploads (hipMemcpy) complete before any kernel of the context's non-blocking streams
-  HIP_TRY(hipDeviceSynchronize());
+  if (hipDeviceSynchronize() != hipSuccess) return bail(fail(KDPT_ERR_HIP, "hipDeviceSynchronize failed"));
   if ((rc = kdpt_reset(c))) return bail(rc);
   c->reduce_spin_us = g_reduce_spin_us;
   c->create_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_create).count();
@@ -2845,7 +2854,6 @@ int kdpt_create(const kdpt_scene* sc, const kdpt_options* opt, int device, kdpt_
 
 int kdpt_set_options(kdpt_ctx* c, const kdpt_options* o) {
   if (!c || !o) return fail(KDPT_ERR_ARG, "null arg");
-  if (c->parent) return fail(KDPT_ERR_ARG, "not a top-level context");
   const kdpt_options& p = c->opt;
   // these select what is uploaded or how much is allocated: a new context is needed
   if (o->enable_kd != p.enable_kd || o->viz_kd != p.viz_kd || o->use_bbox != p.use_bbox ||
@@ -2854,23 +2862,20 @@ int kdpt_set_options(kdpt_ctx* c, const kdpt_options* o) {
     return fail(KDPT_ERR_UNSUPPORTED, "enable_kd, viz_kd, use_bbox, bounce_cap, block_size and external_image "
                                       "are fixed at kdpt_create");
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->slots.empty()) {  // iterations in flight keep the options they were enqueued with
+  if (!c->groups.empty()) {  // iterations in flight keep the options they were enqueued with
     int rc = kdpt_synchronize(c);
     if (rc) return rc;
   }
-  auto apply = [o](kdpt_options& d) {
-    d.focal_length = o->focal_length;
-    d.dof_angle = o->dof_angle;
-    d.softness = o->softness;
-    d.cacherays = o->cacherays;
-    d.antialias = o->antialias;
-    d.enable_sss = o->enable_sss;
-    d.testing_mode = o->testing_mode;
-    d.compaction = o->compaction;
-    d.short_stack = o->short_stack;
-  };
-  apply(c->opt);
-  for (auto sl : c->slots) apply(sl->opt);
+  kdpt_options& d = c->opt;
+  d.focal_length = o->focal_length;
+  d.dof_angle = o->dof_angle;
+  d.softness = o->softness;
+  d.cacherays = o->cacherays;
+  d.antialias = o->antialias;
+  d.enable_sss = o->enable_sss;
+  d.testing_mode = o->testing_mode;
+  d.compaction = o->compaction;
+  d.short_stack = o->short_stack;
   return KDPT_OK;
 }
 
@@ -2890,19 +2895,19 @@ int kdpt_set_tuning(kdpt_ctx* c, const char* name, double value) {
     return KDPT_OK;
   }
   if (!c || !name) return fail(KDPT_ERR_ARG, "null arg");
-  if (c->parent) return fail(KDPT_ERR_ARG, "not a top-level context");
   if (std::string(name) == "cast_chunk") {  // kdpt_cast_rays' chunk; its buffers are remade by the next call
     if (!(value >= 64.0 && value <= (double)(1 << 26))) return fail(KDPT_ERR_ARG, "cast_chunk must be in 64 .. 2^26");
     c->cast_chunk = (int)value;
     return KDPT_OK;
   }
   HIP_TRY(hipSetDevice(c->device));
-  // pipeline slots copy the knobs when they are made: drop them so the next kdpt_trace_iterations
-  // makes new ones
-  if (!c->slots.empty()) {
+  // queued iterations finish first: setup_trace and build_masks free and reallocate device memory their
+  // kernels read.  The pipeline's states hold no knobs; they are still dropped, as include/kdpt.h documents
+  // (the next kdpt_trace_iterations remakes them).
+  if (!c->groups.empty()) {
     int rc = kdpt_synchronize(c);
     if (rc) return rc;
-    drop_slots(c);
+    drop_groups(c);
   }
   const std::string k(name);
   const int v = (int)value;
@@ -2998,7 +3003,7 @@ int kdpt_set_tuning(kdpt_ctx* c, const char* name, double value) {
 int kdpt_reset(kdpt_ctx* c) {
   if (!c) return fail(KDPT_ERR_ARG, "null ctx");
   HIP_TRY(hipSetDevice(c->device));
-  for (auto sl : c->slots) HIP_TRY(hipStreamSynchronize(sl->stream));
+  for (auto& grp : c->groups) HIP_TRY(hipStreamSynchronize(grp.stream));
   if (c->reduce_stream) HIP_TRY(hipStreamSynchronize(c->reduce_stream));
   drain_intersect_events(c);
   c->intersect_ms_total = 0;
@@ -3024,32 +3029,35 @@ int kdpt_synchronize(kdpt_ctx* c) {
   if (!c) return fail(KDPT_ERR_ARG, "null ctx");
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  for (auto sl : c->slots) {
-    HIP_TRY(hipStreamSynchronize(sl->stream));
-    int rc = check_fault(sl);
-    if (rc) return rc;
+  for (auto& grp : c->groups) {
+    HIP_TRY(hipStreamSynchronize(grp.stream));
+    for (auto& it : grp.its) {
+      int rc = check_fault(it.get(), grp.stream);
+      if (rc) return rc;
+    }
   }
   if (c->reduce_stream) HIP_TRY(hipStreamSynchronize(c->reduce_stream));
   unregister_host(c);
   int rc = drain_intersect_events(c);
   if (rc) return rc;
   if (c->profile_batches) HIP_TRY(hipMemcpy(&c->last_profile, c->counters, sizeof(Counters), hipMemcpyDeviceToHost));
-  return check_fault(c);
+  return check_fault(&c->solo, c->stream);
 }
 
 int kdpt_trace_iteration(kdpt_ctx* c, int frame, int iter) {
   (void)frame;
   if (!c) return fail(KDPT_ERR_ARG, "null ctx");
   HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipEventRecord(c->ev0, c->stream));
-  int rc = launch_iteration(c, iter, -1, c->count_mode);
+  IterState& it = c->solo;
+  HIP_TRY(hipEventRecord(it.ev0, c->stream));
+  int rc = launch_iteration(c, iter, -1, false);
   if (rc) return rc;
-  HIP_TRY(hipEventRecord(c->ev1, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->h_counts, c->counts, sizeof(int) * (c->cap + 3), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipEventRecord(it.ev1, c->stream));
+  HIP_TRY(hipMemcpyAsync(it.h_counts, it.counts, sizeof(int) * (c->cap + 3), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->h_counts[c->cap + 2]) return fault_error(c, c->h_counts[c->cap + 2]);
+  if (it.h_counts[c->cap + 2]) return fault_error(&it, c->stream, it.h_counts[c->cap + 2]);
   float ms = 0;
-  HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+  HIP_TRY(hipEventElapsedTime(&ms, it.ev0, it.ev1));
   c->stats.ms_last_iteration = ms;
   c->stats.iterations++;
   const int bounces = segments_from_counts(c);
@@ -3057,7 +3065,7 @@ int kdpt_trace_iteration(kdpt_ctx* c, int frame, int iter) {
     float tot = 0;
     for (int d = 0; d < bounces; d++) {
       float b = 0;
-      if (hipEventElapsedTime(&b, c->bounce_ev[2 * d], c->bounce_ev[2 * d + 1]) == hipSuccess) tot += b;
+      if (hipEventElapsedTime(&b, it.bounce_ev[2 * d], it.bounce_ev[2 * d + 1]) == hipSuccess) tot += b;
     }
     c->stats.ms_intersect = tot;
     c->intersect_ms_total += tot;
@@ -3081,42 +3089,34 @@ int enqueue_iterations(kdpt_ctx* c, int first_iter, int count, int stride, int p
   hipEvent_t entry;
   HIP_TRY(hipEventCreateWithFlags(&entry, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(entry, c->stream));
-  // slots: `depth` groups of B iteration contexts; a group runs one batch at a time on its first
-  // context's stream
-  if ((int)c->slots.size() < depth * B || c->slot_batch != B) {
-    if (!c->slots.empty()) {
+  // `depth` groups of B iteration states; a group runs one batch at a time on its stream
+  if ((int)c->groups.size() < depth || c->group_batch != B) {
+    if (!c->groups.empty()) {
       int rc = kdpt_synchronize(c);
       if (rc) return rc;
-      drop_slots(c);
+      drop_groups(c);
     }
-    c->slot_batch = B;
+    c->group_batch = B;
     c->next_group = 0;
-    // Only the group leaders create streams, one after another: HIP maps streams onto its hardware queues
-    // (GPU_MAX_HW_QUEUES) in creation order, reusing the least-used queue once all exist, so a stream per
-    // slot context (8 x 4) had put pairs of leaders -- two batches' chains -- on one in-order queue.
-    while ((int)c->slots.size() < depth * B) {
-      kdpt_ctx* sl = nullptr;
-      const bool leader = c->slots.size() % B == 0;
-      int rc = make_slot(c, &sl, leader ? nullptr : c->slots[c->slots.size() / B * B]->stream);
-      if (rc) return rc;
-      c->slots.push_back(sl);
-    }
-    for (int g = 0; g < depth; g++) {
-      hipEvent_t d;
-      HIP_TRY(hipEventCreateWithFlags(&d, hipEventDisableTiming));
-      c->acc_ev.push_back(d);
+    // One stream per group, created one after another in group order: HIP maps streams onto its hardware
+    // queues (GPU_MAX_HW_QUEUES) in creation order, reusing the least-used queue once all exist, so a stream per
+    // iteration state (8 x 4) had put pairs of groups -- two batches' chains -- on one in-order queue.
+    while ((int)c->groups.size() < depth) {
+      int rc = make_group(c, B);
+      if (rc) {
+        drop_groups(c);
+        return rc;
+      }
     }
   }
-  const int ngroups = (int)c->acc_ev.size();
+  const int ngroups = (int)c->groups.size();
   // With several batches in flight each intersect launch gets a share of the chip (2/depth of the
   // persistent grid, all of it for depth <= 2, a quarter from depth 8 on): a launch's length is set by its
   // heaviest rays, so concurrent launches on disjoint CU subsets overlap those tails instead of queueing
   // behind them.  (Sweep with every batch on its own hardware queue: a quarter is best at depths 8-12.)
-  for (auto sl : c->slots)
-    sl->trace_grid =
-        c->grid_env ? c->trace_grid : std::max(1, c->trace_grid * 2 / std::min(8, std::max(2, depth)));
-  c->stats.intersect_grid_share =
-      c->slots.empty() ? 1.0f : (float)c->slots[0]->trace_grid / (float)std::max(1, c->full_trace_grid);
+  const int trace_grid =
+      c->grid_env ? c->trace_grid : std::max(1, c->trace_grid * 2 / std::min(8, std::max(2, depth)));
+  c->stats.intersect_grid_share = (float)trace_grid / (float)std::max(1, c->full_trace_grid);
   // diagnostic ("profile_batches" knob): the counting intersect kernel (kdpt_wave_profile after sync)
   if (c->profile_batches) HIP_TRY(hipMemsetAsync(c->counters, 0, sizeof(Counters), c->stream));
   bool first = true;
@@ -3126,14 +3126,15 @@ int enqueue_iterations(kdpt_ctx* c, int first_iter, int count, int stride, int p
     // shorter than the pipeline must not restart at group 0 (it would wait on that group's previous batch)
     const int g = c->next_group % ngroups;
     c->next_group = (g + 1) % ngroups;
-    kdpt_ctx* const* grp = &c->slots[(size_t)g * B];
-    hipStream_t st = grp[0]->stream;
+    IterGroup& grp = c->groups[g];
+    hipStream_t st = grp.stream;
     // (the group's previous batch's partial images were added on this stream, before this batch's camera rays
     // clear them)
     int iters[MAXB];
+    IterState* its[MAXB];
     for (int b = 0; b < nb; b++) {
       iters[b] = first_iter + (kb + b) * stride;
-      grp[b]->zero_partial = true;  // k_gen_rays clears the partial image
+      its[b] = grp.its[b].get();
     }
     std::vector<hipEvent_t>* bev = nullptr;
     if (c->opt.testing_mode) {
@@ -3147,7 +3148,7 @@ int enqueue_iterations(kdpt_ctx* c, int first_iter, int count, int stride, int p
       c->pending_ev.push_back(evs);
       bev = &c->pending_ev.back();
     }
-    int rc = launch_batch(grp, iters, nb, st, -1, c->profile_batches, bev);
+    int rc = launch_batch(c, its, iters, nb, st, trace_grid, -1, c->profile_batches, bev);
     if (rc) return rc;
     // the add: after the previous add (the chain), and for the call's first batch after the context's stream,
     // the frames' image adds (when the target is the image) and the target's zeroing
@@ -3164,11 +3165,11 @@ int enqueue_iterations(kdpt_ctx* c, int first_iter, int count, int stride, int p
     const int n3 = 3 * c->npix;
     PartialImages parts{};
     parts.nb = nb;
-    for (int b = 0; b < nb; b++) parts.p[b] = grp[b]->image;  // in iteration order
+    for (int b = 0; b < nb; b++) parts.p[b] = its[b]->image;  // in iteration order
     hipLaunchKernelGGL(k_accumulate_batch, dim3((n3 + 255) / 256), dim3(256), 0, st, target, parts, n3);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->acc_ev[g], st));
-    c->acc_last = c->acc_ev[g];
+    HIP_TRY(hipEventRecord(grp.acc_ev, st));
+    c->acc_last = grp.acc_ev;
   }
   HIP_TRY(hipEventDestroy(entry));
   c->stats.iterations += count;
@@ -3178,7 +3179,6 @@ int enqueue_iterations(kdpt_ctx* c, int first_iter, int count, int stride, int p
 int kdpt_trace_iterations(kdpt_ctx* c, int frame, int first_iter, int count, int stride, int pipeline, int batch) {
   (void)frame;
   if (!c || count < 0 || first_iter < 1 || stride < 1) return fail(KDPT_ERR_ARG, "bad arguments");
-  if (c->parent) return fail(KDPT_ERR_ARG, "not a top-level context");
   HIP_TRY(hipSetDevice(c->device));
   return enqueue_iterations(c, first_iter, count, stride, pipeline, batch, c->image);
 }
@@ -3242,7 +3242,7 @@ int kdpt_write_pbo(kdpt_ctx* c, int iter, uint8_t* rgba) {
 // The saveImage pixel pass on the device; rgb (host, 3*W*H) and/or lin (host, 3*W*H floats).
 static int save_image_pass(kdpt_ctx* c, float samples, uint8_t* rgb, float* lin) {
   HIP_TRY(hipSetDevice(c->device));
-  for (auto sl : c->slots) HIP_TRY(hipStreamSynchronize(sl->stream));
+  for (auto& grp : c->groups) HIP_TRY(hipStreamSynchronize(grp.stream));
   if (c->reduce_stream) HIP_TRY(hipStreamSynchronize(c->reduce_stream));
   const size_t n3 = 3 * (size_t)c->npix;
   uint8_t* d_rgb = nullptr;
@@ -3330,7 +3330,7 @@ int kdpt_destroy(kdpt_ctx* c) {
   if (!c) return KDPT_OK;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  drop_slots(c);  // (each slot drains its stream)
+  drop_groups(c);  // (each group's stream drained first)
   for (auto& evs : c->pending_ev)
     for (auto e : evs) (void)hipEventDestroy(e);
   for (auto e : c->free_ev) (void)hipEventDestroy(e);
@@ -3347,12 +3347,8 @@ int kdpt_destroy(kdpt_ctx* c) {
   free_cast_buffers(c);
   for (auto e : c->cast_ev)
     if (e) (void)hipEventDestroy(e);
-  if (c->h_counts) (void)hipHostFree(c->h_counts);
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
-  for (auto e : c->bounce_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (c->stream && c->owns_stream) (void)hipStreamDestroy(c->stream);
+  free_iter(&c->solo);
+  if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return KDPT_OK;
 }
@@ -3360,32 +3356,23 @@ int kdpt_destroy(kdpt_ctx* c) {
 int kdpt_debug_paths(kdpt_ctx* c, int iter, int stop_depth, kdpt_path_segment* out, int* npaths) {
   if (!c || !out || stop_depth < 0 || stop_depth >= c->cap) return fail(KDPT_ERR_ARG, "bad arg");
   HIP_TRY(hipSetDevice(c->device));
-  // run on a scratch image so the accumulation buffer is untouched
-  float* saved = c->image;
-  float* scratch = nullptr;
-  HIP_TRY(hipMalloc((void**)&scratch, sizeof(float) * 3 * (size_t)c->npix));
-  HIP_TRY(hipMemsetAsync(scratch, 0, sizeof(float) * 3 * (size_t)c->npix, c->stream));
-  c->image = scratch;
-  unsigned long long* saved_tot = c->total_segments;
-  c->total_segments = reinterpret_cast<unsigned long long*>(c->counters);  // scratch word
-  int rc = launch_iteration(c, iter, stop_depth, false);
-  c->total_segments = saved_tot;
-  c->image = saved;
-  if (rc) { (void)hipFree(scratch); return rc; }
+  IterState& it = c->solo;
+  ScratchTargets targets(it);
+  int rc = targets.redirect(c);
+  if (rc || (rc = launch_iteration(c, iter, stop_depth, false))) return rc;
   kdpt_path_segment* d = nullptr;
   HIP_TRY(hipMalloc((void**)&d, sizeof(kdpt_path_segment) * (size_t)c->npix));
+  std::unique_ptr<void, DeviceFree> d_owner(d);
   const int depth_slot = stop_depth + 1;
-  hipLaunchKernelGGL(k_unpack, dim3((c->npix + 255) / 256), dim3(256), 0, c->stream, c->buf[c->cur], c->counts,
+  hipLaunchKernelGGL(k_unpack, dim3((c->npix + 255) / 256), dim3(256), 0, c->stream, it.buf[it.cur], it.counts,
                      depth_slot, d);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(c->h_counts, c->counts, sizeof(int) * (c->cap + 2), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(it.h_counts, it.counts, sizeof(int) * (c->cap + 2), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if ((rc = check_fault(c))) { (void)hipFree(d); (void)hipFree(scratch); return rc; }
-  const int n = c->h_counts[depth_slot];
+  if ((rc = check_fault(&it, c->stream))) return rc;
+  const int n = it.h_counts[depth_slot];
   *npaths = n;
   HIP_TRY(hipMemcpy(out, d, sizeof(kdpt_path_segment) * (size_t)n, hipMemcpyDeviceToHost));
-  (void)hipFree(d);
-  (void)hipFree(scratch);
   return KDPT_OK;
 }
 
@@ -3393,29 +3380,20 @@ int kdpt_debug_paths(kdpt_ctx* c, int iter, int stop_depth, kdpt_path_segment* o
 int kdpt_count_iteration(kdpt_ctx* c, int iter, unsigned long long* aabb_tri_hit) {
   if (!c || !aabb_tri_hit) return fail(KDPT_ERR_ARG, "null arg");
   HIP_TRY(hipSetDevice(c->device));
-  float* saved = c->image;
-  float* scratch = nullptr;
-  HIP_TRY(hipMalloc((void**)&scratch, sizeof(float) * 3 * (size_t)c->npix));
-  HIP_TRY(hipMemsetAsync(scratch, 0, sizeof(float) * 3 * (size_t)c->npix, c->stream));
+  IterState& it = c->solo;
+  ScratchTargets targets(it);
+  int rc = targets.redirect(c);
+  if (rc) return rc;
   HIP_TRY(hipMemsetAsync(c->counters, 0, sizeof(Counters), c->stream));
-  c->image = scratch;
-  unsigned long long* saved_tot = c->total_segments;
-  unsigned long long* scratch_tot = nullptr;
-  HIP_TRY(hipMalloc((void**)&scratch_tot, sizeof(unsigned long long)));
-  c->total_segments = scratch_tot;
-  int rc = launch_iteration(c, iter, -1, true);
-  c->total_segments = saved_tot;
-  c->image = saved;
+  rc = launch_iteration(c, iter, -1, true);
   Counters h{};
   if (!rc) {
     HIP_TRY(hipMemcpyAsync(&h, c->counters, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->h_counts, c->counts, sizeof(int) * (c->cap + 3), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(it.h_counts, it.counts, sizeof(int) * (c->cap + 3), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     segments_from_counts(c);  // stats.segments / seg_per_bounce now describe the counting iteration
-    rc = check_fault(c);
+    rc = check_fault(&it, c->stream);
   }
-  (void)hipFree(scratch);
-  (void)hipFree(scratch_tot);
   aabb_tri_hit[0] = h.aabb;
   aabb_tri_hit[1] = h.tri;
   aabb_tri_hit[2] = h.hit;
@@ -3560,8 +3538,8 @@ int kdpt_selftest_fresnel(const float* cs, int n, float ior, float* f) {
 namespace {
 
 template <bool HYBRID, bool COUNT>
-void launch_trace_mode(kdpt_ctx* c, const TraceArgs& a, hipStream_t st) {
-  const dim3 g(c->trace_grid);
+void launch_trace_mode(kdpt_ctx* c, const TraceArgs& a, int grid, hipStream_t st) {
+  const dim3 g(grid);
   if (c->tree_mode == TREE_LDS)
     hipLaunchKernelGGL((k_trace<HYBRID, COUNT, TREE_LDS>), g, dim3(trace_block<TREE_LDS>()), c->tree_lds, st, a);
   else if (c->tree_mode == TREE_LDS16)
@@ -3576,10 +3554,11 @@ void launch_trace_mode(kdpt_ctx* c, const TraceArgs& a, hipStream_t st) {
     hipLaunchKernelGGL((k_trace<HYBRID, COUNT, TREE_WIDE>), g, dim3(trace_block<TREE_WIDE>()), 0, st, a);
 }
 
-void launch_trace(kdpt_ctx* c, const TraceArgs& a, bool count, hipStream_t st) {
+// grid: the launch's persistent workgroups (c->trace_grid, or a pipelined call's share of it)
+void launch_trace(kdpt_ctx* c, const TraceArgs& a, bool count, int grid, hipStream_t st) {
   const bool hyb = c->opt.short_stack != 0;
-  if (hyb) { if (count) launch_trace_mode<true, true>(c, a, st); else launch_trace_mode<true, false>(c, a, st); }
-  else { if (count) launch_trace_mode<false, true>(c, a, st); else launch_trace_mode<false, false>(c, a, st); }
+  if (hyb) { if (count) launch_trace_mode<true, true>(c, a, grid, st); else launch_trace_mode<true, false>(c, a, grid, st); }
+  else { if (count) launch_trace_mode<false, true>(c, a, grid, st); else launch_trace_mode<false, false>(c, a, grid, st); }
 }
 
 template <bool HYBRID>
@@ -3594,91 +3573,100 @@ void launch_shade_h(kdpt_ctx* c, const ShadeArgs& a, bool compact, bool sort, hi
   }
 }
 
-// One iteration of each context in cs (nb <= MAXB; all share the scene and options), in lockstep on
-// stream st: per bounce the analytic geoms of each, one intersect launch over all of them, then each
-// one's shading and compaction.  The iterations stay independent: only the intersect launch is shared.
-int launch_batch(kdpt_ctx* const* cs, const int* iters, int nb, hipStream_t st, int stop_depth, bool count,
-                 std::vector<hipEvent_t>* bev) {
-  kdpt_ctx* c0 = cs[0];
+// One iteration in each state of its (nb <= MAXB), with the context's scene, options and knobs, in lockstep on
+// stream st: per bounce the analytic geoms of each, one intersect launch of trace_grid workgroups over all of
+// them, then each one's shading and compaction.  The iterations stay independent: only the intersect launch is
+// shared.
+int launch_batch(kdpt_ctx* c, IterState* const* its, const int* iters, int nb, hipStream_t st, int trace_grid,
+                 int stop_depth, bool count, std::vector<hipEvent_t>* bev) {
+  IterState* it0 = its[0];
+  // The fault word is the one per-iteration member of DevScene: the batch-wide launches (camera rays + geoms,
+  // k_geoms, k_trace) report into the first state's word, each iteration's own launches into its own.
+  auto scene_of = [c](const IterState* it) {
+    DevScene S = c->S;
+    S.fault = it->fault;
+    return S;
+  };
+  const DevScene S0 = scene_of(it0);
   // camera rays and bounce 0's analytic geoms + root-box test in one launch (not for the brute-force and box-view
   // intersect kernels, which have no first part)
-  const bool gen_geoms = c0->gen_geoms && !c0->brute && !c0->viz;
+  const bool gen_geoms = c->gen_geoms && !c->brute && !c->viz;
   {  // the batch's camera rays in one launch (blockIdx.y = iteration)
     GenBatch gb;
-    gb.cam = c0->cam;
-    gb.traceDepth = c0->traceDepth;
-    gb.focalLength = c0->opt.focal_length;
-    gb.dofAngle = c0->opt.dof_angle;
-    gb.antialias = c0->opt.antialias;
-    gb.ncounts = c0->cap + 2;
-    gb.nwork = c0->cap;
-    gb.nlb = c0->cap * c0->ntiles;
+    gb.cam = c->cam;
+    gb.traceDepth = c->traceDepth;
+    gb.focalLength = c->opt.focal_length;
+    gb.dofAngle = c->opt.dof_angle;
+    gb.antialias = c->opt.antialias;
+    gb.ncounts = c->cap + 2;
+    gb.nwork = c->cap;
+    gb.nlb = c->cap * c->ntiles;
     for (int b = 0; b < nb; b++) {
-      kdpt_ctx* c = cs[b];
-      c->cur = 0;
-      gb.it[b] = GenIter{c->opt.cacherays ? 1 : iters[b], c->buf[0], c->counts, c->work, c->trace_t, c->lb,
-                         c->zero_partial ? c->image : nullptr};
+      IterState* it = its[b];
+      it->cur = 0;
+      gb.it[b] = GenIter{c->opt.cacherays ? 1 : iters[b], it->buf[0], it->counts, it->work, it->trace_t, it->lb,
+                         it->zero_partial ? it->image : nullptr};
     }
     if (gen_geoms) {
       GenGeomsBatch gg;
       gg.g = gb;
-      gg.S = c0->S;
-      gg.count_aabb = count ? c0->counters : nullptr;
+      gg.S = S0;
+      gg.count_aabb = count ? c->counters : nullptr;
       for (int b = 0; b < nb; b++) {
-        kdpt_ctx* c = cs[b];
-        c->cc0_cur = c->ccount0 + c->gen_parity;
-        gg.it[b] = GenGeomsIter{c->cc0_cur, c->ccount0 + (c->gen_parity ^ 1), c->cray, c->hits, c->cand};
-        c->gen_parity ^= 1;
+        IterState* it = its[b];
+        it->cc0_cur = it->ccount0 + it->gen_parity;
+        gg.it[b] = GenGeomsIter{it->cc0_cur, it->ccount0 + (it->gen_parity ^ 1), it->cray, it->hits, it->cand};
+        it->gen_parity ^= 1;
       }
-      hipLaunchKernelGGL(k_gen_geoms_b, dim3((c0->npix + GEN_BLOCK - 1) / GEN_BLOCK, nb), dim3(GEN_BLOCK), 0, st,
+      hipLaunchKernelGGL(k_gen_geoms_b, dim3((c->npix + GEN_BLOCK - 1) / GEN_BLOCK, nb), dim3(GEN_BLOCK), 0, st,
                          gg);
     } else {
-      hipLaunchKernelGGL(k_gen_rays_b, dim3((c0->npix + 255) / 256, nb), dim3(256), 0, st, gb);
+      hipLaunchKernelGGL(k_gen_rays_b, dim3((c->npix + 255) / 256, nb), dim3(256), 0, st, gb);
     }
     HIP_TRY(hipGetLastError());
   }
-  const bool compact = c0->opt.compaction != 0;
+  const bool compact = c->opt.compaction != 0;
   bool prep_ready = false;  // this bounce's intersect-stage first part came with the previous scatter
-  for (int depth = 0; depth < c0->cap; depth++) {
-    const bool prep_next = compact && depth + 1 < c0->cap && !c0->brute && !c0->viz;
-    if (c0->opt.testing_mode && bev) HIP_TRY(hipEventRecord((*bev)[2 * depth], st));
+  for (int depth = 0; depth < c->cap; depth++) {
+    const bool prep_next = compact && depth + 1 < c->cap && !c->brute && !c->viz;
+    if (c->opt.testing_mode && bev) HIP_TRY(hipEventRecord((*bev)[2 * depth], st));
     TraceArgs t;
-    t.S = c0->S;
+    t.S = S0;
     t.nb = nb;
-    t.prof_steps = (c0->parent ? c0->parent : c0)->profile_steps ? 1 : 0;
+    t.prof_steps = c->profile_steps ? 1 : 0;
     for (int b = 0; b < MAXB; b++) {
-      kdpt_ctx* c = cs[b < nb ? b : 0];
-      t.it[b].cand = c->cand;
-      t.it[b].ccount = (depth == 0 && gen_geoms) ? c->cc0_cur : c->ccount;  // indexed by depth (0 here)
-      t.it[b].cray = c->cray;
-      t.it[b].hits = c->hits;
+      IterState* it = its[b < nb ? b : 0];
+      t.it[b].cand = it->cand;
+      t.it[b].ccount = (depth == 0 && gen_geoms) ? it->cc0_cur : it->ccount;  // indexed by depth (0 here)
+      t.it[b].cray = it->cray;
+      t.it[b].hits = it->hits;
     }
-    t.work = c0->work;
+    t.work = it0->work;
     t.depth = depth;
-    t.counters = c0->counters;
-    t.trace_t = c0->trace_t;
-    if (c0->viz) {
+    t.counters = c->counters;
+    t.trace_t = it0->trace_t;
+    if (c->viz) {
       for (int b = 0; b < nb; b++) {
-        kdpt_ctx* c = cs[b];
-        hipLaunchKernelGGL(k_viz, dim3(c->ntiles), dim3(TILE), 0, st, c->S, c->buf[c->cur], c->counts, depth, c->hits,
-                           c0->trace_t);
+        IterState* it = its[b];
+        hipLaunchKernelGGL(k_viz, dim3(c->ntiles), dim3(TILE), 0, st, scene_of(it), it->buf[it->cur], it->counts, depth,
+                           it->hits, it0->trace_t);
         HIP_TRY(hipGetLastError());
       }
-    } else if (c0->brute) {
+    } else if (c->brute) {
       for (int b = 0; b < nb; b++) {
-        kdpt_ctx* c = cs[b];
+        IterState* it = its[b];
         BruteArgs ba;
-        ba.S = c->S;
-        ba.paths = c->buf[c->cur];
-        ba.counts = c->counts;
+        ba.S = scene_of(it);
+        ba.paths = it->buf[it->cur];
+        ba.counts = it->counts;
         ba.depth = depth;
-        ba.hits = c->hits;
+        ba.hits = it->hits;
         ba.shapes = c->shapes;
         ba.num_shapes = c->num_shapes;
         ba.chunk_lo = c->chunk_lo;
         ba.chunk_hi = c->chunk_hi;
-        ba.counters = c0->counters;
-        ba.trace_t = c0->trace_t;
+        ba.counters = c->counters;
+        ba.trace_t = it0->trace_t;
         const dim3 g(c->ntiles), bl(TILE);
         if (c->opt.use_bbox) {
           if (count) hipLaunchKernelGGL((k_brute<true, true>), g, bl, 0, st, ba);
@@ -3688,7 +3676,7 @@ int launch_batch(kdpt_ctx* const* cs, const int* iters, int nb, hipStream_t st, 
           else hipLaunchKernelGGL((k_brute<false, false>), g, bl, 0, st, ba);
         }
         HIP_TRY(hipGetLastError());
-        if (c0->sync_debug) {
+        if (c->sync_debug) {
           BruteShape h0;
           HIP_TRY(hipStreamSynchronize(st));  // (the null-stream copy below does not order after st)
           HIP_TRY(hipMemcpy(&h0, c->shapes, sizeof h0, hipMemcpyDeviceToHost));
@@ -3702,73 +3690,73 @@ int launch_batch(kdpt_ctx* const* cs, const int* iters, int nb, hipStream_t st, 
       // ran with the hand-off (prep_ready), else here
       if (!prep_ready && !(depth == 0 && gen_geoms)) {  // the batch's iterations in one launch (blockIdx.y = iteration)
         GeomsBatch gb;
-        gb.S = c0->S;
+        gb.S = S0;
         gb.depth = depth;
-        gb.count_aabb = count ? c0->counters : nullptr;
-        gb.gspan = c0->trace_t + 2 * c0->cap;
+        gb.count_aabb = count ? c->counters : nullptr;
+        gb.gspan = it0->trace_t + 2 * c->cap;
         for (int b = 0; b < nb; b++) {
-          kdpt_ctx* c = cs[b];
-          gb.it[b] = GeomsIter{c->buf[c->cur], c->counts, c->cray, c->hits, c->cand, c->ccount};
+          IterState* it = its[b];
+          gb.it[b] = GeomsIter{it->buf[it->cur], it->counts, it->cray, it->hits, it->cand, it->ccount};
         }
-        hipLaunchKernelGGL(k_geoms_b, dim3((c0->npix + GEN_BLOCK - 1) / GEN_BLOCK, nb), dim3(GEN_BLOCK), 0, st, gb);
+        hipLaunchKernelGGL(k_geoms_b, dim3((c->npix + GEN_BLOCK - 1) / GEN_BLOCK, nb), dim3(GEN_BLOCK), 0, st, gb);
         HIP_TRY(hipGetLastError());
       }
-      launch_trace(c0, t, count, st);
+      launch_trace(c, t, count, trace_grid, st);
       HIP_TRY(hipGetLastError());
     }
-    if (c0->sync_debug) {
+    if (c->sync_debug) {
       fprintf(stderr, "[kdpt] trace depth %d launched (grid %d, mode %d, lds %zu, batch %d)\n", depth,
-              c0->trace_grid, c0->tree_mode, c0->tree_lds, nb);
+              trace_grid, c->tree_mode, c->tree_lds, nb);
       HIP_TRY(hipStreamSynchronize(st));
       fprintf(stderr, "[kdpt] trace depth %d done\n", depth);
     }
-    if (c0->opt.testing_mode && bev) HIP_TRY(hipEventRecord((*bev)[2 * depth + 1], st));
+    if (c->opt.testing_mode && bev) HIP_TRY(hipEventRecord((*bev)[2 * depth + 1], st));
     ShadeBatch sbatch;
     int nfused = 0, fused_grid = 0;
     bool fused_hyb = false, fused_stage = false;
     for (int b = 0; b < nb; b++) {
-      kdpt_ctx* c = cs[b];
+      IterState* it = its[b];
       const bool sort = (iters[b] == 2);
       ShadeArgs a;
-      a.S = c->S;
-      a.paths = c->buf[c->cur];
-      a.hits = c->hits;
-      a.image = c->image;
-      a.image_zeroed = c->zero_partial ? 1 : 0;
-      a.counts = c->counts;
+      a.S = scene_of(it);
+      a.paths = it->buf[it->cur];
+      a.hits = it->hits;
+      a.image = it->image;
+      a.image_zeroed = it->zero_partial ? 1 : 0;
+      a.counts = it->counts;
       a.depth = depth;
       a.iter = iters[b];
       a.softness = c->opt.softness;
       a.enable_sss = c->opt.enable_sss;
-      a.tile_counts = c->tile_counts;
-      a.tile_kcounts = (compact && c->trace_order) ? c->tile_kcounts : nullptr;
+      a.tile_counts = it->tile_counts;
+      a.tile_kcounts = nullptr;
       a.ntiles = c->ntiles;
       a.nkeys = c->nkeys;
-      a.total_segments = c->total_segments;
-      a.trace_t = c0->trace_t;
-      a.gspan = c0->trace_t + 2 * c0->cap;
+      a.total_segments = it->total_segments;
+      a.trace_t = it0->trace_t;
+      a.gspan = it0->trace_t + 2 * c->cap;
       a.trace_total = b == 0 ? c->trace_total : nullptr;
-      a.trace_rays = (c0->brute || c0->viz) ? nullptr : c->trace_total + 2;
-      a.ccount = (depth == 0 && gen_geoms) ? c->cc0_cur : c->ccount;
+      a.trace_rays = (c->brute || c->viz) ? nullptr : c->trace_total + 2;
+      a.ccount = (depth == 0 && gen_geoms) ? it->cc0_cur : it->ccount;
       a.prep_on = prep_next ? 1 : 0;
-      a.prep = c->prep;
-      a.tile_ccounts = c->tile_ccounts;
-      a.count_aabb = count ? c0->counters : nullptr;
-      if (compact && !sort && !a.tile_kcounts && !c->no_fuse) {
+      a.prep = it->prep;
+      a.tile_ccounts = it->tile_ccounts;
+      a.count_aabb = count ? c->counters : nullptr;
+      if (compact && !sort && !c->no_fuse) {
         // single pass: shading, compaction into the other buffer and the hand-off (k_shade_fused)
-        const int nxt = c->cur ^ 1;
-        const FuseArgs f{c->buf[nxt], c->tickets, c->lb, c->counts, c->ccount, c->cray, c->hits, c->cand};
+        const int nxt = it->cur ^ 1;
+        const FuseArgs f{it->buf[nxt], it->tickets, it->lb, it->counts, it->ccount, it->cray, it->hits, it->cand};
         const bool stage = c->S.num_geoms + c->S.num_boxes <= ORDERED_GEOMS && c->S.num_materials <= STAGE_MATS;
         const bool hyb = c->opt.short_stack || c->brute;
         const int shade_grid = (c->npix + SHADE_TB - 1) / SHADE_TB;
-        if (c0->shade_batch) {  // launched below, with the batch's other fused iterations
+        if (c->shade_batch) {  // launched below, with the batch's other fused iterations
           sbatch.a[nfused] = a;
           sbatch.f[nfused] = f;
           nfused++;
           fused_hyb = hyb;
           fused_stage = stage;
           fused_grid = shade_grid;
-          c->cur = nxt;
+          it->cur = nxt;
           continue;
         }
         if (hyb && stage) hipLaunchKernelGGL((k_shade_fused<true, true>), dim3(shade_grid), dim3(SHADE_TB), 0, st, a, f);
@@ -3776,7 +3764,7 @@ int launch_batch(kdpt_ctx* const* cs, const int* iters, int nb, hipStream_t st, 
         else if (stage) hipLaunchKernelGGL((k_shade_fused<false, true>), dim3(shade_grid), dim3(SHADE_TB), 0, st, a, f);
         else hipLaunchKernelGGL((k_shade_fused<false, false>), dim3(shade_grid), dim3(SHADE_TB), 0, st, a, f);
         HIP_TRY(hipGetLastError());
-        c->cur = nxt;
+        it->cur = nxt;
         continue;
       }
       // hit point offset: 1e-4 for the hybrid traversal and the brute-force kernel, 1e-5 for traverseKDbare
@@ -3786,23 +3774,23 @@ int launch_batch(kdpt_ctx* const* cs, const int* iters, int nb, hipStream_t st, 
       if (compact || sort) {
         // survivors' offsets + the next bounce's path count; with the hand-off also the candidate-list
         // offsets per tile + the next bounce's candidate count (a second workgroup)
-        const ScanJob j0{c->tile_counts, c->tile_off, sort ? c->nkeys : 1, c->counts + depth + 1};
-        const ScanJob j1{c->tile_ccounts, c->tile_coff, 1, c->ccount + depth + 1};
-        hipLaunchKernelGGL(k_scan, dim3(prep_next ? 2 : 1), dim3(SCAN_TB), 0, st, j0, j1, c->counts, depth, c->ntiles);
+        const ScanJob j0{it->tile_counts, it->tile_off, sort ? c->nkeys : 1, it->counts + depth + 1};
+        const ScanJob j1{it->tile_ccounts, it->tile_coff, 1, it->ccount + depth + 1};
+        hipLaunchKernelGGL(k_scan, dim3(prep_next ? 2 : 1), dim3(SCAN_TB), 0, st, j0, j1, it->counts, depth, c->ntiles);
         HIP_TRY(hipGetLastError());
-        const int nxt = c->cur ^ 1;
-        ScatterPrep sp{prep_next ? 1 : 0, c->prep, c->cray, c->hits, c->cand, c->tile_coff};
+        const int nxt = it->cur ^ 1;
+        ScatterPrep sp{prep_next ? 1 : 0, it->prep, it->cray, it->hits, it->cand, it->tile_coff};
         if (sort)
-          hipLaunchKernelGGL(k_scatter<true>, dim3(c->ntiles), dim3(TILE), 0, st, c->buf[c->cur], c->buf[nxt],
-                             c->tile_off, c->counts, depth, c->ntiles, compact ? 1 : 0, sp);
+          hipLaunchKernelGGL(k_scatter<true>, dim3(c->ntiles), dim3(TILE), 0, st, it->buf[it->cur], it->buf[nxt],
+                             it->tile_off, it->counts, depth, c->ntiles, compact ? 1 : 0, sp);
         else
-          hipLaunchKernelGGL(k_scatter<false>, dim3(c->ntiles), dim3(TILE), 0, st, c->buf[c->cur], c->buf[nxt],
-                             c->tile_off, c->counts, depth, c->ntiles, compact ? 1 : 0, sp);
+          hipLaunchKernelGGL(k_scatter<false>, dim3(c->ntiles), dim3(TILE), 0, st, it->buf[it->cur], it->buf[nxt],
+                             it->tile_off, it->counts, depth, c->ntiles, compact ? 1 : 0, sp);
         HIP_TRY(hipGetLastError());
-        c->cur = nxt;
+        it->cur = nxt;
       } else {
         // no compaction, no sort: the live range stays the whole image
-        HIP_TRY(hipMemcpyAsync(c->counts + depth + 1, c->counts + depth, sizeof(int), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(it->counts + depth + 1, it->counts + depth, sizeof(int), hipMemcpyDeviceToDevice, st));
       }
     }
     if (nfused) {  // the batch's fused iterations in one launch
@@ -3813,7 +3801,7 @@ int launch_batch(kdpt_ctx* const* cs, const int* iters, int nb, hipStream_t st, 
       else hipLaunchKernelGGL((k_shade_fused_b<false, false>), g, bl, 0, st, sbatch);
       HIP_TRY(hipGetLastError());
     }
-    if (c0->sync_debug) {
+    if (c->sync_debug) {
       HIP_TRY(hipStreamSynchronize(st));
       fprintf(stderr, "[kdpt] shade depth %d done\n", depth);
     }
@@ -3822,19 +3810,21 @@ int launch_batch(kdpt_ctx* const* cs, const int* iters, int nb, hipStream_t st, 
   }
   if (!compact) {
     for (int b = 0; b < nb; b++) {
-      kdpt_ctx* c = cs[b];
-      hipLaunchKernelGGL(k_final_gather, dim3((c->npix + 255) / 256), dim3(256), 0, st, c->buf[c->cur], c->counts,
-                         c->cap, c->image);
+      IterState* it = its[b];
+      hipLaunchKernelGGL(k_final_gather, dim3((c->npix + 255) / 256), dim3(256), 0, st, it->buf[it->cur], it->counts,
+                         c->cap, it->image);
       HIP_TRY(hipGetLastError());
     }
   }
   return KDPT_OK;
 }
 
+// One iteration in the solo state, on the context's stream with the whole intersect grid.
 int launch_iteration(kdpt_ctx* c, int iter, int stop_depth, bool count) {
   int rc = join_accum(c);
   if (rc) return rc;
-  return launch_batch(&c, &iter, 1, c->stream, stop_depth, count, c->rec_ev ? c->rec_ev : &c->bounce_ev);
+  IterState* it = &c->solo;
+  return launch_batch(c, &it, &iter, 1, c->stream, c->trace_grid, stop_depth, count, &it->bounce_ev);
 }
 
 }  // namespace
@@ -4005,7 +3995,6 @@ int finish_frame(kdpt_ctx* c, const float* sum, float* out, int k, hipStream_t s
 
 int check_frames_args(kdpt_ctx* c, int first_frame, int frames, int spp) {
   if (!c || first_frame < 0 || frames < 0 || spp < 1) return fail(KDPT_ERR_ARG, "bad arguments");
-  if (c->parent) return fail(KDPT_ERR_ARG, "not a top-level context");
   return KDPT_OK;
 }
 
@@ -4035,7 +4024,6 @@ int kdpt_comm_unique_id(unsigned char* id) {
 
 int kdpt_comm_init(kdpt_ctx* c, int nranks, int rank, const unsigned char* id) {
   if (!c || nranks < 1 || rank < 0 || rank >= nranks) return fail(KDPT_ERR_ARG, "bad arguments");
-  if (c->parent) return fail(KDPT_ERR_ARG, "not a top-level context");
   HIP_TRY(hipSetDevice(c->device));
   int rc = kdpt_synchronize(c);
   if (rc) return rc;
@@ -4269,7 +4257,6 @@ int kdpt_cast_rays(kdpt_ctx* c, const float* origins, const float* directions, l
   if (n > 0 && !origins) return fail(KDPT_ERR_ARG, "kdpt_cast_rays: null origins");
   if (n > 0 && !directions) return fail(KDPT_ERR_ARG, "kdpt_cast_rays: null directions");
   if (n > 0 && !out) return fail(KDPT_ERR_ARG, "kdpt_cast_rays: null out");
-  if (c->parent) return fail(KDPT_ERR_ARG, "kdpt_cast_rays: not a top-level context");
   if (c->brute || c->viz)
     return fail(KDPT_ERR_UNSUPPORTED, "kdpt_cast_rays: the context runs the brute-force or box-view intersect kernel "
                                       "(enable_kd = 0 / viz_kd = 1); ray queries need the KD traversal");
@@ -4318,7 +4305,7 @@ int kdpt_cast_rays(kdpt_ctx* c, const float* origins, const float* directions, l
     a.out = out_dev ? out + off : c->cast_out;
     hipLaunchKernelGGL(k_cast_prep, dim3((m + GEN_BLOCK - 1) / GEN_BLOCK), dim3(GEN_BLOCK), 0, st, a);
     HIP_TRY(hipGetLastError());
-    launch_trace(c, t, false, st);
+    launch_trace(c, t, false, c->trace_grid, st);
     HIP_TRY(hipGetLastError());
     if (c->opt.short_stack) hipLaunchKernelGGL(k_cast_resolve<true>, dim3((m + 255) / 256), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_cast_resolve<false>, dim3((m + 255) / 256), dim3(256), 0, st, a);
@@ -4335,7 +4322,7 @@ int kdpt_cast_rays(kdpt_ctx* c, const float* origins, const float* directions, l
   c->cast_ms = ms;
   c->cast_rays += n;
   c->cast_traced += (long long)traced;
-  return check_fault(c);
+  return check_fault(&c->solo, c->stream);
 }
 
 int kdpt_cast_stats(kdpt_ctx* c, long long* rays, long long* traced, double* device_ms) {

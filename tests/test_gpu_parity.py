@@ -423,3 +423,86 @@ def test_process_knobs_keep_parity(kdpt):
     finally:
         set_process_tuning("cu_mask_streams", 1)
         set_process_tuning("cluster_chord", -1)
+
+
+# -- state changes on a live context between pipelined calls (cornell + dragon_5, 96 x 80, depth 8) --------------
+_LIVE_DESC = dict(scene="cornell", mesh="dragon_5", res=(96, 80), depth=8)
+_LIVE_OPTS = {"antialias": 0, "softness": 0.5}  # both change the image
+_live_oracle = {}  # (iteration, changed options?) -> (image, segments): rendered once, shared by the tests below
+
+
+def _oracle_iteration(oracle, it, changed=False):
+    if "scene" not in _live_oracle:
+        _live_oracle["scene"] = oracle.OracleScene.from_description(load_fixture_scene(
+            _LIVE_DESC["scene"], _LIVE_DESC["mesh"], res=_LIVE_DESC["res"], depth=_LIVE_DESC["depth"]))
+    if (it, changed) not in _live_oracle:
+        o = {_ORC_KEYS[k]: v for k, v in _LIVE_OPTS.items()} if changed else {}
+        im, st = _live_oracle["scene"].render(it, 1, **o)
+        _live_oracle[(it, changed)] = (im, st.segments)
+    return _live_oracle[(it, changed)]
+
+
+def _oracle_sum(oracle, plan):
+    """Sum of the oracle's one-iteration images (float32 adds in iteration order, as the accumulation image
+    gets them) and of its segment counts over plan = [(iteration, changed options?), ...]."""
+    img, segs = None, 0
+    for it, changed in plan:
+        im, n = _oracle_iteration(oracle, it, changed)
+        img = im.copy() if img is None else (img + im)
+        segs += n
+    return img, segs
+
+
+def _live_pt(kdpt):
+    desc = load_fixture_scene(_LIVE_DESC["scene"], _LIVE_DESC["mesh"], res=_LIVE_DESC["res"], depth=_LIVE_DESC["depth"])
+    return _pt(kdpt, desc)
+
+
+def test_options_and_batch_shape_change_between_pipelined_calls(kdpt, oracle):
+    """Options set between two pipelined calls (no explicit synchronise) reach every iteration state of the
+    second call, whose other batch size remakes the states and whose last batch is ragged (5 = 3 + 2); then
+    back to the defaults for a one-at-a-time iteration.  Image bits and total segments against the oracle's
+    sum with the same options per iteration."""
+    with _live_pt(kdpt) as pt:
+        pt.trace_iterations(1, 6, pipeline=2, batch=2)
+        pt.set_options(kdpt.default_options(**_LIVE_OPTS))
+        pt.trace_iterations(7, 5, pipeline=3, batch=3)
+        pt.set_options(kdpt.default_options())
+        pt.trace_iteration(12)
+        img = pt.image()
+        total = pt.stats().total_segments
+    plan = [(it, False) for it in range(1, 7)] + [(it, True) for it in range(7, 12)] + [(12, False)]
+    o_img, o_segs = _oracle_sum(oracle, plan)
+    # (a stale option would show: the two option sets give different images)
+    assert not np.array_equal(_oracle_iteration(oracle, 7, True)[0], _oracle_iteration(oracle, 7, False)[0])
+    assert total == o_segs
+    assert np.array_equal(img.view(np.uint32), o_img.view(np.uint32)), \
+        f"{int(np.sum(img != o_img))} values differ, max |d| = {float(np.abs(img - o_img).max())}"
+
+
+def test_debug_entry_points_leave_the_context_untouched(kdpt, oracle):
+    """kdpt_count_iteration and kdpt_debug_paths run an iteration of their own on a live context: the
+    accumulation image and stats.total_segments keep their bits, later pipelined iterations accumulate on top
+    as if nothing had happened, and debug_paths still returns the oracle's path state."""
+    with _live_pt(kdpt) as pt:
+        pt.trace_iterations(1, 8, pipeline=2, batch=4)
+        pt.synchronize()
+        img8 = pt.image().copy()
+        total8 = pt.stats().total_segments
+        pt.count_iteration(3)
+        g = pt.debug_paths(3, 1)
+        assert np.array_equal(pt.image().view(np.uint32), img8.view(np.uint32))
+        assert pt.stats().total_segments == total8
+        pt.trace_iterations(9, 4, pipeline=2, batch=4)
+        pt.synchronize()
+        img12 = pt.image()
+        total12 = pt.stats().total_segments
+    o_img8, o_segs8 = _oracle_sum(oracle, [(it, False) for it in range(1, 9)])
+    o_img12, o_segs12 = _oracle_sum(oracle, [(it, False) for it in range(1, 13)])
+    assert total8 == o_segs8 and total12 == o_segs12
+    assert np.array_equal(img8.view(np.uint32), o_img8.view(np.uint32))
+    assert np.array_equal(img12.view(np.uint32), o_img12.view(np.uint32))
+    o = _live_oracle["scene"].paths_after(3, 1)
+    assert len(g) == len(o)
+    for f in ("origin", "direction", "color", "pixelIndex", "remainingBounces", "materialIdHit", "isinside"):
+        assert np.array_equal(g[f], o[f]), f
