@@ -189,7 +189,12 @@ void kdpt_default_options(kdpt_options *opt);
 /* pathtraceInit: allocate + upload (geoms, materials, nodes, triangles, offsets). */
 int kdpt_create(const kdpt_scene *scene, const kdpt_options *opt, int device, kdpt_ctx **out);
 /* pathtrace(pbo, frame, iter, ...): one iteration (1 sample per pixel); iter is 1-based and
- * seeds the RNG.  Synchronous on return, like the reference. */
+ * seeds the RNG.  Synchronous on return, like the reference.
+ * KDPT_ERR_UNSUPPORTED (from every entry point that shades, before anything is queued) for a KD-traversed OBJ
+ * with triangles of a shape other than the first: the reference's traversal reports material
+ * mtlIdx + material_size - 1 for their hits (src/pathtrace.cu:1142), past the end of its materials array, so
+ * there is no defined result to reproduce.  kdpt_cast_rays (which only reports that number) and enable_kd = 0
+ * (which takes the material from the shapes' offsets) remain available. */
 int kdpt_trace_iteration(kdpt_ctx *ctx, int frame, int iter);
 /* Iterations first_iter + k*stride (k < count), in batches of `batch` (<= 16) that share each bounce's
  * intersect launch, with `pipeline` batches in flight at once (each on its own stream and buffers).
@@ -246,7 +251,8 @@ int kdpt_set_options(kdpt_ctx *ctx, const kdpt_options *opt);
  * construction), "cull_margin" (0 = the scene's; > 0 overrides the cull's margin coefficient, no masks),
  * "cull_exact" (1; 0 = for meshes of large triangles the margin-only cull instead of the masked exact one, not
  * exact), "cull_mask_n" (the direction masks' cube-map cells per face edge, 1 .. 512; default: the finest of
- * 256 / 128 / 64 ... within 640 MB), "cull_fast_k" (the masked cull's box coefficient, default 1e-3; the masks
+ * 256 / 128 / 64 ... within 640 MB; KDPT_ERR_ARG, and the current masks kept, when 6 n^2 num_clusters >= 2^32: the
+ * kernel indexes the table with 32 bits), "cull_fast_k" (the masked cull's box coefficient, default 1e-3; the masks
  * are rebuilt for it), "reduce_spin_us" (0; > 0: a device spin of that many
  * microseconds on the reduce stream before every frame's reduce, emulating an ncclReduce that waits for a slower
  * peer -- a diagnostic of the frame pipeline; ctx = NULL sets it for contexts created later, e.g. the ones

@@ -1824,6 +1824,11 @@ struct kdpt_ctx {
   int full_trace_grid = 0;  // the occupancy-derived grid (trace_grid before a "trace_grid_frac" knob)
   bool grid_env = false;  // trace_grid fixed by the "trace_grid_frac" tuning knob
   bool force_global_tree = false;  // "tree_global" tuning knob: keep the tree in HBM/L2
+  // A triangle of shape m > 0: the KD traversal reports material mtlIdx + material_size - 1 for it
+  // (src/pathtrace.cu:1142, :1205, :991), an index past the reference's own materials array, which its shading
+  // then reads (and iteration 2's sort uses as a key).  There is nothing to reproduce: iterations are refused
+  // (launch_batch); kdpt_cast_rays only reports the number and stays available.
+  bool shade_oob = false;
   bool super_cull = true;          // "super_cull" tuning knob: 0 = no TREE_LDS16S route (one-level cull)
   CullMargin cull{};                // the scene's cluster-cull margins (kdpt_clusters.h cluster_margin)
   // the exact one-level cull's direction masks (kdpt_clusters.h build_dir_masks), built when the scene's rigorous
@@ -1909,6 +1914,14 @@ namespace {
 // the others on its queue.  C4's 32-spp frames: 6.49 -> 5.68 ms with 24 queues, and a 5 ms reduce delay per frame
 // costs nothing at 4 or 24 queues (profiles/r06_ab_log.md).  Knob "cu_mask_streams" = 0 (process default):
 // plain non-blocking streams; a failed creation falls back to one.
+// kdpt_ctx::shade_oob: every entry point that shades ends here before it queues anything.
+int refuse_shading() {
+  return fail(KDPT_ERR_UNSUPPORTED,
+              "the OBJ has triangles of a shape other than the first: their hits carry material mtlIdx + "
+              "num_materials - 1, past the materials array (as in the reference), so the scene cannot be shaded; "
+              "kdpt_cast_rays and enable_kd = 0 remain available");
+}
+
 int create_stream(kdpt_ctx* c, hipStream_t* st) {
   if (c->cu_mask_streams) {
     hipDeviceProp_t prop;
@@ -2148,6 +2161,13 @@ int build_masks(kdpt_ctx* c, int n) {
   const auto t0 = std::chrono::steady_clock::now();
   const ClusterSet& cs = *c->mask_cs;
   const int ncl = (int)cs.info.size(), nb = 6 * n * n;
+  // the intersect kernel indexes the table with 32 bits (kdpt_device.h, S.cl_mask[bucket * num_clusters + c]): a
+  // resolution whose table has 2^32 cells or more is refused here, before anything is freed or allocated
+  if (n < 1 || (unsigned long long)nb * (unsigned long long)ncl >= (1ull << 32))
+    return fail(KDPT_ERR_ARG, "direction masks: 6 n^2 num_clusters must be below 2^32 (n = " + std::to_string(n) +
+                                  ", " + std::to_string(ncl) + " clusters: n <= " +
+                                  std::to_string((int)std::sqrt((double)((1ull << 32) - 1) / (6.0 * std::max(1, ncl)))) +
+                                  ")");
   const float Kf = c->cull.K;
   MaskEntries me;
   mask_entries(cs, Kf, me);
@@ -2542,6 +2562,7 @@ int kdpt_create(const kdpt_scene* sc, const kdpt_options* opt, int device, kdpt_
   // nodes[i].ID == i, root == node 0, node 1 == root's left child, <= 15 levels.
   std::vector<int> level;
   const bool brute = !o.enable_kd && sc->has_obj;
+  bool shade_oob = false;  // kdpt_ctx::shade_oob
   if (brute) {
     // the arrays pathTraceOneBounce reads (src/pathtrace.cu:485-576) must be in bounds
     if (sc->num_shapes < 1 || !sc->obj_materialOffsets || !sc->obj_polyoffsets || !sc->obj_polysidxflat ||
@@ -2591,9 +2612,11 @@ int kdpt_create(const kdpt_scene* sc, const kdpt_options* opt, int device, kdpt_
     for (int i = 0; i < sc->num_tris; i++) {
       int m = sc->tris[i].mtlIdx;
       if (m < 0 || m >= sc->num_shapes) return fail(KDPT_ERR_ARG, "triangle mtlIdx out of range");
+      if (m > 0 && !o.viz_kd) shade_oob = true;
     }
   }
   kdpt_ctx* c = new kdpt_ctx();
+  c->shade_oob = shade_oob;
   c->device = device;
   c->opt = o;
   c->cam = sc->camera;
@@ -3083,6 +3106,7 @@ int kdpt_trace_iteration(kdpt_ctx* c, int frame, int iter) {
 // event (a frame buffer after its previous reduce).  Returns once everything is queued.
 int enqueue_iterations(kdpt_ctx* c, int first_iter, int count, int stride, int pipeline, int batch, float* target,
                        hipEvent_t zero_after = nullptr) {
+  if (c->shade_oob) return refuse_shading();
   const int depth = std::min(16, std::max(1, pipeline));
   const int B = std::min(MAXB, std::max(1, batch));
   // the first add follows everything already queued on the context's own stream (reset, ...)
@@ -3579,6 +3603,7 @@ void launch_shade_h(kdpt_ctx* c, const ShadeArgs& a, bool compact, bool sort, hi
 // shared.
 int launch_batch(kdpt_ctx* c, IterState* const* its, const int* iters, int nb, hipStream_t st, int trace_grid,
                  int stop_depth, bool count, std::vector<hipEvent_t>* bev) {
+  if (c->shade_oob) return refuse_shading();
   IterState* it0 = its[0];
   // The fault word is the one per-iteration member of DevScene: the batch-wide launches (camera rays + geoms,
   // k_geoms, k_trace) report into the first state's word, each iteration's own launches into its own.

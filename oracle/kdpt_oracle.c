@@ -1077,8 +1077,19 @@ void orc_default_opts(orc_opts *o) {
     o->vizkd = 0;
 }
 
+/* The KD traversal reports material mtlIdx + material_size - 1 for a triangle hit (src/pathtrace.cu:991, :1142,
+ * :1205); for a triangle of any shape but the first that is past the end of the materials array, which the
+ * reference's shading then reads.  Nothing defined to restate: such a scene is refused (-2), not shaded. */
+static int shades_past_materials(const orc_scene *s, const orc_opts *o) {
+    if (!s->has_obj || !o->enable_kd || o->vizkd) return 0;
+    for (int i = 0; i < s->num_tris; i++)
+        if (s->tris[i].mtlIdx > 0) return 1;
+    return 0;
+}
+
 int orc_render(const orc_scene *s, const orc_opts *o, int iter_first, int iter_count, float *image,
                orc_stats *stats, int nthreads) {
+    if (shades_past_materials(s, o)) return -2;
 #ifdef _OPENMP
     if (nthreads > 0) omp_set_num_threads(nthreads);
 #else
@@ -1099,6 +1110,7 @@ int orc_render(const orc_scene *s, const orc_opts *o, int iter_first, int iter_c
 }
 
 int orc_paths_after(const orc_scene *s, const orc_opts *o, int iter, int stop_depth, orc_path *out, int *npaths) {
+    if (shades_past_materials(s, o)) return -2;
     int pixelcount = s->camera.resolution[0] * s->camera.resolution[1];
     orc_path *tmp = (orc_path *)calloc((size_t)pixelcount, sizeof(orc_path));
     orc_isect *isects = (orc_isect *)calloc((size_t)pixelcount, sizeof(orc_isect));

@@ -205,7 +205,9 @@ int orc_load_obj(const char *obj_path, float **verts9, float **norms9, int **sha
 
 /* Render iterations [iter_first, iter_first+iter_count) (1-based iter, the RNG
  * seed) accumulating into image (3*W*H floats, caller-zeroed), exactly like
- * repeated pathtrace() calls (src/pathtrace.cu:2405-2635).  nthreads<=0: all. */
+ * repeated pathtrace() calls (src/pathtrace.cu:2405-2635).  nthreads<=0: all.
+ * Returns -2 (as orc_paths_after does) for a KD-traversed OBJ with triangles of a shape other than the first:
+ * the reference indexes past its materials array for their hits (mtlIdx + material_size - 1). */
 int orc_render(const orc_scene *s, const orc_opts *o, int iter_first, int iter_count,
                float *image, orc_stats *stats, int nthreads);
 

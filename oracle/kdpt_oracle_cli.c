@@ -49,7 +49,7 @@ int main(int argc, char **argv) {
     size_t npx = (size_t)s.camera.resolution[0] * s.camera.resolution[1];
     float *img = (float *)calloc(npx * 3, sizeof(float));
     orc_stats st;
-    orc_render(&s, &o, first, iters, img, &st, threads);
+    if (orc_render(&s, &o, first, iters, img, &st, threads)) { fprintf(stderr, "orc_render failed\n"); return 1; }
     double t2 = now_s();
     /* imgsum as the survey defines it: per-pixel float (r+g+b) accumulated in double */
     double sum = 0;

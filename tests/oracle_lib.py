@@ -198,8 +198,10 @@ class OracleScene:
         img = np.zeros((h, w, 3), dtype=np.float32)
         st = OStats()
         o = default_opts(**opts)
-        lib().orc_render(C.byref(self.s), C.byref(o), iter_first, iter_count,
-                         img.ctypes.data_as(C.POINTER(C.c_float)), C.byref(st), nthreads)
+        rc = lib().orc_render(C.byref(self.s), C.byref(o), iter_first, iter_count,
+                              img.ctypes.data_as(C.POINTER(C.c_float)), C.byref(st), nthreads)
+        if rc:
+            raise RuntimeError(f"orc_render rc={rc}")
         return img, st
 
     def paths_after(self, iteration, stop_depth, **opts):
@@ -208,7 +210,9 @@ class OracleScene:
         out = np.zeros(w * h, dtype=PATH_DTYPE)
         n = C.c_int()
         o = default_opts(**opts)
-        lib().orc_paths_after(C.byref(self.s), C.byref(o), iteration, stop_depth, out.ctypes.data, C.byref(n))
+        rc = lib().orc_paths_after(C.byref(self.s), C.byref(o), iteration, stop_depth, out.ctypes.data, C.byref(n))
+        if rc:
+            raise RuntimeError(f"orc_paths_after rc={rc}")
         return out[: n.value].copy()
 
     def close(self):

@@ -204,3 +204,42 @@ def test_real_rays_never_hit_a_dropped_pass(cull_diff, trees, rays_c3):
     r = run(cull_diff, trees("dragon_5"), "--rays", rays_c3)
     assert r["rays"] == 150_000 and r["pairs"] > 10_000_000, r
     assert r["violations"] == 0, r
+
+
+@pytest.fixture(scope="module")
+def soup_trees(tmp_path_factory):
+    """The host builder's trees of the adversarial soups (tests/soups.py), in the harness's file format."""
+    import soups
+    from kdtreepathtraceroptimization_amd import SceneData
+    d = tmp_path_factory.mktemp("cull_soups")
+    out = {}
+
+    def get(name):
+        if name not in out:
+            sd = SceneData.from_description(soups.soup_scene(name, res=(64, 64)))
+            out[name] = soups.write_tree(sd, str(d / f"{name}.bin"))
+            sd.close()
+        return out[name]
+    return get
+
+
+# `pass` (lines on which some triangle of some cluster passes glm's own u/v tests: nothing the cull decides) as the
+# harness reports it for 10^6 lines, seed 71 -- the same at the default mask resolution and at MASK_N = 32, since
+# the lines do not depend on the masks.  The tests' floor is half of it.
+SOUP_PASS = {"rootleaf8200": 181_028, "growth": 150_241, "syn20000": 319_443, "coincident": 41_602, "flat": 125_921}
+
+
+@pytest.mark.parametrize("mask_n", [0, 32], ids=["default-n", "n32"])
+@pytest.mark.parametrize("soup", list(SOUP_PASS))
+def test_soups_masked_cull_never_drops_a_pass(cull_diff, soup_trees, soup, mask_n):
+    """The soups with big leaves: clusters of zero-area triangles and of duplicates (syn20000), of triangles all in
+    one plane (flat: boxes of zero thickness), of huge overlapping triangles (growth, rootleaf8200), of 64
+    coincident copies (coincident).  None has a rigorous margin below the cap (exact = 0), so each takes the masked
+    cull: for 10^6 adversarial lines every triangle that passes glm's u/v tests is swept or kept by its danger
+    mask, and the measured error stays inside the derived bound."""
+    r = run(cull_diff, soup_trees(soup), 1_000_000, 71, env={"MASK_N": str(mask_n)} if mask_n else None)
+    print(soup, mask_n, {k: v for k, v in r.items() if k != "gens"}, {g: v["pass"] for g, v in r["gens"].items()})
+    assert r["exact"] == 0 and r["clusters"] > 0, r
+    assert r["viol_mask"] == 0, r
+    assert 0 < r["bound"] <= 1.0, r
+    assert r["pass"] >= SOUP_PASS[soup] // 2, r
