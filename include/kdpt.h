@@ -186,7 +186,10 @@ typedef struct kdpt_ctx kdpt_ctx;
 
 void kdpt_default_options(kdpt_options *opt);
 
-/* pathtraceInit: allocate + upload (geoms, materials, nodes, triangles, offsets). */
+/* pathtraceInit: allocate + upload (geoms, materials, nodes, triangles, offsets).
+ * All argument and scene errors (KDPT_ERR_ARG / KDPT_ERR_UNSUPPORTED: options, resolution, KD tree shape,
+ * triangle and OBJ arrays, geom types and materials) are reported before any device work, so they read the
+ * same on a machine without a device; KDPT_ERR_HIP can only follow an accepted scene. */
 int kdpt_create(const kdpt_scene *scene, const kdpt_options *opt, int device, kdpt_ctx **out);
 /* pathtrace(pbo, frame, iter, ...): one iteration (1 sample per pixel); iter is 1-based and
  * seeds the RNG.  Synchronous on return, like the reference.

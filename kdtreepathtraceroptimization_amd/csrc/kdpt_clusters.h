@@ -1,6 +1,6 @@
 // kdpt_clusters.h -- host-side construction of the big-leaf clusters, super-clusters and cluster slabs
 // (DevScene::leaf_cl, cl_lo / cl_hi / cl_n, sup, c_v0 / c_e1 / c_e2).  Shared by the runtime
-// (kdpt_runtime.hip build_clusters, which uploads the result) and the host differential test of the cluster
+// (kdpt_scene_prep.h choose_clusters; kdpt_create uploads the result) and the host differential test of the cluster
 // cull (tests/native/cull_diff.cpp), so that the test checks exactly the boxes the kernels read.
 //
 // Only the order in which a wave tests a big leaf's triangles depends on this grouping (results are

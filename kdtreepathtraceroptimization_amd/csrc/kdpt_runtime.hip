@@ -1,18 +1,25 @@
-// kdpt_runtime.hip -- gfx950 kernels and the C-ABI (include/kdpt.h) for the
-// reference's per-sample hot path (src/pathtrace.cu:2405-2635 `pathtrace`).
+// kdpt_runtime.hip -- the runtime behind the C ABI (include/kdpt.h): the context and its device memory,
+// kdpt_create (upload of what kdpt_scene_prep.h prepared), the knobs, the launch sequence of an iteration
+// (launch_batch), pipelined / batched iterations, the multi-GPU frame path and the ray queries.  One HIP
+// translation unit: the kernels live in the kernels_*.h headers included below, one per stage; scene
+// validation and packing live in kdpt_scene_prep.h and run before any device call.
 //
-// One iteration = k_gen_rays, then per bounce (cap 8, src/pathtrace.cu:2608):
-//   k_trace    : the intersect kernel -- 6 analytic geoms + KD traversal, one lane
-//                per live path, persistent waves pulling 64-path chunks, the KD
-//                tree read from LDS when it fits (32-byte packed nodes)
-//   k_shade    : scatterRay + shadeMaterial + partialGather, writes the path in
-//                place and the tile's survivor count
-//   k_scan     : exclusive scan of tile counts (key-major when iter == 2 sorts)
-//   k_scatter  : stable compaction (thrust::remove_if) -- and on iter 2 the
-//                stable sort by materialIdHit (thrust::sort, a merge sort) --
-//                into the other path buffer.
-// No host synchronisation inside an iteration: the live-path count lives on
-// the device and kernels past the end of the live range exit at once.
+// One iteration of the reference's per-sample hot path (src/pathtrace.cu:2405-2635 `pathtrace`), as queued by
+// launch_batch for a batch of up to MAXB iterations in lockstep (blockIdx.y / the batch records = iteration):
+//   k_gen_geoms_b   : camera rays + bounce 0's analytic geoms and root-box test, which queue the rays that
+//                     meet the KD root box (k_gen_rays_b alone on the brute-force / viz routes)
+//   then per bounce (cap 8, src/pathtrace.cu:2608):
+//   k_trace         : the intersect kernel -- KD traversal of the queued rays, persistent waves pulling
+//                     64-ray chunks, the tree read from LDS when a record format fits (setup_trace); k_brute /
+//                     k_viz instead with enable_kd = 0 / viz_kd
+//   k_shade_fused_b : scatterRay + shadeMaterial + partialGather, the stable compaction of the survivors into
+//                     the other path buffer (thrust::remove_if; decoupled look-back over the tiles) and the
+//                     next bounce's geoms stage and ray queue, in one launch
+//   and k_final_gather after the last bounce.
+// Iteration 2's stable sort by materialIdHit (thrust::sort), compaction = 0 and the "shade_fused" = 0 knob take
+// the three-kernel route instead: k_shade, k_scan, k_scatter (and k_geoms_b where no hand-off prepared the rays).
+// No host synchronisation inside an iteration: the live-path count lives on the device and kernels past the
+// end of the live range exit at once.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,17 +40,11 @@
 #include "../../include/kdpt.h"
 #include "kdpt_device.h"
 #include "kdpt_clusters.h"
+#include "kdpt_scene_prep.h"
 
 using namespace kdpt;
 
-namespace kdpt_host {
-void node_box_matrices(const float* mins, const float* maxs, float* transform16, float* inverse16);
-}
-
 namespace {
-
-constexpr int TILE = 256;  // paths per workgroup (4 waves of 64)
-constexpr int MAX_KEYS = 64;
 
 thread_local std::string g_last_error;
 double g_reduce_spin_us = 0;  // kdpt_set_tuning(NULL, "reduce_spin_us", v): the default of new contexts
@@ -62,1701 +63,16 @@ int fail(int code, const std::string& msg) {
       return fail(KDPT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));        \
   } while (0)
 
-// Path state, structure of arrays of float4 (coalesced 1 KiB per wave load):
-//   p0 = {origin.xyz, sdepth}
-//   p1 = {direction.xyz, pixelIndex | isinside << 31}
-//   p2 = {color.rgb, remainingBounces}
-//   pm = materialIdHit
-struct PathBuf {
-  float4* p0;
-  float4* p1;
-  float4* p2;
-  int* pm;
-};
-
-struct Counters {
-  unsigned long long aabb, tri, hit;
-  unsigned long long aabb_prep;  // root-box tests of rays that end before the intersect kernel (k_geoms/k_shade)
-  unsigned long long cand;       // rays handed to the intersect kernel
-  unsigned long long wave[PROF_SLOTS + 2];  // WaveLeafLDS::prof summed over chunks, then chunks, cycles
-  unsigned long long life[64];  // count mode: wave lifetimes in the intersect kernel, 10 us bins (s_memrealtime)
-  unsigned long long steps[64];  // count mode: node steps per ray, bins of 4
-  unsigned long long chord_steps[8], chord_n[8];  // ... summed by the ray's chord through the root box (8ths of
-                                                  // the box diagonal): does the chord predict a ray's cost?
-};
-
-// ---------------------------------------------------------------------------
-// generateRayFromCamera (src/pathtrace.cu:315-397)
-// ---------------------------------------------------------------------------
-__device__ __attribute__((always_inline)) inline bool gen_rays_body(
-    const kdpt_camera& cam, int iter, int traceDepth, PathBuf out, float focalLength, float dofAngle, int antialias,
-    int* counts, int ncounts, int* work, int nwork, unsigned long long* trace_t, unsigned long long* lb, int nlb,
-    float* zero_image, f3& ray_o, f3& ray_d) {
-  const int W = cam.resolution[0], H = cam.resolution[1];
-  const int index = blockIdx.x * blockDim.x + threadIdx.x;
-  if (index == 0) {
-    counts[0] = W * H;
-    for (int k = 1; k < ncounts; k++) counts[k] = 0;
-    for (int k = 0; k < nwork; k++) {
-      work[k] = 0;
-      work[nwork + k] = 0;  // candidate counts (k_geoms), stored after the work counters
-      work[2 * nwork + k] = 0;  // k_shade_fused's tile tickets
-      trace_t[2 * k] = ~0ull;  // k_trace span of bounce k, then (at 2*nwork) k_geoms' span
-      trace_t[2 * k + 1] = 0ull;
-      trace_t[2 * nwork + 2 * k] = ~0ull;
-      trace_t[2 * nwork + 2 * k + 1] = 0ull;
-    }
-  }
-  for (int e = index; e < nlb; e += gridDim.x * blockDim.x) lb[e] = 0ull;  // k_shade_fused's look-back records
-  if (index >= W * H) return false;
-  if (zero_image) {  // batched iterations: this iteration's partial image starts at zero (no separate fill)
-    zero_image[3 * index] = 0.0f;
-    zero_image[3 * index + 1] = 0.0f;
-    zero_image[3 * index + 2] = 0.0f;
-  }
-  const int x = index % W, y = index / W;
-  const f3 view = mk3(cam.view[0], cam.view[1], cam.view[2]);
-  const f3 right = mk3(cam.right[0], cam.right[1], cam.right[2]);
-  const f3 upv = mk3(cam.up[0], cam.up[1], cam.up[2]);
-  Ray ray;
-  ray.origin = mk3(cam.position[0], cam.position[1], cam.position[2]);
-  ray.isinside = false;
-  // cam.right * cam.pixelLength.x * (...): (vec * float) * float
-  f3 a = scl(scl(right, cam.pixelLength[0]), ((float)x - (float)W * 0.5f));
-  f3 b = scl(scl(upv, cam.pixelLength[1]), ((float)y - (float)H * 0.5f));
-  ray.direction = normalize(sub(sub(view, a), b));
-  Rng rng = rng_seed(utilhash((uint32_t)iter));  // same stream for every pixel (:334)
-  if (antialias) {
-    const float jitterscale = (float)0.002;
-    float j0 = u01(rng), j1 = u01(rng), j2 = u01(rng);
-    f3 v3a = normalize(mk3(j0, j1, j2));
-    ray.direction = add(ray.direction, scl(v3a, jitterscale));
-    ray.direction = normalize(ray.direction);
-  }
-  float u = kdpt_cosf(PI_F * u01(rng));
-  float u2 = u * u;
-  float sq = sqrtf(1 - u2);
-  float theta = 2 * PI_F * u01(rng);
-  f3 vv = normalize(mk3(sq * kdpt_cosf(theta), sq * kdpt_sinf(theta), u));
-  (void)u01(rng);  // R1
-  (void)u01(rng);  // R2
-  float randangle = u01(rng) * PI_F * dofAngle;
-  float qw = kdpt_cosf(randangle / 2.0f);
-  float sh = kdpt_sinf(randangle / 2.0f);
-  f3 qv = mk3(vv.x * sh, vv.y * sh, vv.z * sh);
-  const f3 randrot = quat_rotate(qw, qv, ray.direction);  // glm::rotate(Q1, direction)
-  ray.origin = sub(add(ray.origin, scl(ray.direction, focalLength)), scl(randrot, focalLength));
-  ray.direction = normalize(randrot);
-  out.p0[index] = make_float4(ray.origin.x, ray.origin.y, ray.origin.z, 0.0f);
-  out.p1[index] = make_float4(ray.direction.x, ray.direction.y, ray.direction.z, ibits(index));
-  out.p2[index] = make_float4(1.0f, 1.0f, 1.0f, ibits(traceDepth));
-  ray_o = ray.origin;
-  ray_d = ray.direction;
-  return true;
-}
-
-// Launched for a whole batch of iterations at once (k_gen_rays_b, blockIdx.y = iteration).
-struct GenIter {
-  int iter;
-  PathBuf out;
-  int* counts;
-  int* work;
-  unsigned long long* trace_t;
-  unsigned long long* lb;
-  float* zero_image;
-};
-
-// ---------------------------------------------------------------------------
-// pathTraceOneBounceKDbare (src/pathtrace.cu:1489-1662): the intersect kernel.
-//
-// Persistent: one 1024-thread workgroup per CU slot; every wave repeatedly takes
-// the next 64 live paths from a device counter, so a wave that drew heavy rays
-// never holds a CU idle.  With MODE == TREE_LDS the workgroup first copies the
-// packed KD tree into LDS and every node step is an LDS read.
-// Output per path: hit code (-1 none, g >= 0 analytic geom g, -(k + 2) triangle k)
-// and objMaterialIdx; k_shade recomputes the winner's point and normal with the
-// same functions, so nothing else needs to travel.
-// ---------------------------------------------------------------------------
-// TREE_LDS: 32-byte NodesPacked records in LDS (+ the cluster boxes); TREE_LDS16: 16-byte NodesDerived
-// records + cluster boxes in LDS; TREE_LDS16G: NodesDerived in LDS, cluster boxes in HBM/L2 (trees whose
-// clusters do not fit, e.g. the C5 icosphere: 2 655 nodes = 41 KB, 22 848 clusters = 714 KB); TREE_LDS16S:
-// NodesDerived + the super-cluster boxes in LDS, cluster boxes in HBM/L2, two-level cull (the C5 icosphere:
-// 1 430 supers of 16 clusters = 45 KB)
-enum TreeMode { TREE_WIDE = 0, TREE_PACKED = 1, TREE_LDS = 2, TREE_LDS16 = 3, TREE_LDS16G = 4, TREE_LDS16S = 5 };
-#ifndef KDPT_TRACE_BLOCK
-#define KDPT_TRACE_BLOCK 1024  // tools/build_variant.sh experiments only
-#endif
-constexpr int TRACE_BLOCK = KDPT_TRACE_BLOCK;  // LDS mode: one workgroup per CU shares the tree copy
-#ifndef KDPT_SRUN_SPREAD
-#define KDPT_SRUN_SPREAD 0  // 1: static runs of ceil(n / waves) instead of 64 (experiment)
-#endif
-// workgroup size of the intersect kernel: with the tree in LDS every wave of a CU must share the copy,
-// otherwise small workgroups let the tail of one launch hold only a quarter of a CU
-// NodesDerived halves the tree copy.  Two 512-thread workgroups per CU (30 KB of per-wave leaf scratch + 46 KB
-// of tree and cluster boxes each for dragon_5), so that one workgroup's launch tail would overlap the next
-// one's start, measured 5.5 % slower than one 1024-thread workgroup (profiles/r03_ab_log.md)
-#ifndef KDPT_TRACE_BLOCK16
-#define KDPT_TRACE_BLOCK16 1024  // tools/build_variant.sh experiments only
-#endif
-constexpr int TRACE_BLOCK16 = KDPT_TRACE_BLOCK16;
-constexpr bool tree_in_lds(int mode) { return mode >= 2; }
-template <int MODE>
-constexpr int trace_block() { return MODE == 2 ? TRACE_BLOCK : (MODE >= 3 ? TRACE_BLOCK16 : 256); }
-
-// Up to MAXB iterations (each its own path buffers) at the same bounce share one intersect launch:
-// more rays per launch keep the lanes of the persistent waves busy.
-#ifndef KDPT_MAXB
-#define KDPT_MAXB 16  // tools/build_variant.sh experiments only
-#endif
-constexpr int MAXB = KDPT_MAXB;
-struct TraceIter {
-  const int* cand;      // k_geoms' list of the paths whose ray meets the KD root box (queue slot -> path)
-  const int* ccount;    // ... and its length per bounce
-  const float4* cray;   // ... and their rays in queue order: [2 slot] = {origin, t_min}, [2 slot + 1] = {dir, geom}
-  int2* hits;
-};
-
-struct TraceArgs {
-  DevScene S;
-  TraceIter it[MAXB];
-  int nb;
-  int prof_steps;  // count mode, "profile_batches" = 2: per-ray node-step histogram
-  int* work;  // chunk counters, zeroed by k_gen_rays (of iteration 0 of the batch)
-  int depth;
-  Counters* counters;
-  unsigned long long* trace_t;  // [4 * cap]: per bounce first block start / last block end (s_memrealtime)
-                                // of k_trace, then of k_geoms (at 2 * cap)
-};
-
-struct GenBatch {
-  GenIter it[MAXB];
-  kdpt_camera cam;
-  int traceDepth, antialias, ncounts, nwork, nlb;
-  float focalLength, dofAngle;
-};
-__global__ __launch_bounds__(256) void k_gen_rays_b(GenBatch B) {
-  const GenIter& g = B.it[blockIdx.y];
-  f3 o, d;
-  (void)gen_rays_body(B.cam, g.iter, B.traceDepth, g.out, B.focalLength, B.dofAngle, B.antialias, g.counts,
-                      B.ncounts, g.work, B.nwork, g.trace_t, g.lb, B.nlb, g.zero_image, o, d);
-}
-
-__device__ inline void flush_counters(Counters* C, const TraverseCounters& cnt, WaveProf* W,
-                                      unsigned long long t_k0) {
-  unsigned int a = cnt.aabb, tr = cnt.tri, hi = cnt.hit;
-  for (int off = 32; off > 0; off >>= 1) {
-    a += __shfl_down(a, off);
-    tr += __shfl_down(tr, off);
-    hi += __shfl_down(hi, off);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    atomicAdd(&C->aabb, (unsigned long long)a);
-    atomicAdd(&C->tri, (unsigned long long)tr);
-    atomicAdd(&C->hit, (unsigned long long)hi);
-    for (int k = 0; k < PROF_SLOTS; k++) {
-      atomicAdd(&C->wave[k], W->prof[k]);
-      W->prof[k] = 0;
-    }
-    atomicAdd(&C->wave[PROF_SLOTS], 1ull);
-    atomicAdd(&C->wave[PROF_SLOTS + 1], __builtin_readcyclecounter() - t_k0);
-  }
-}
-
-// The intersect stage's first part for one ray: the analytic geoms of pathTraceOneBounceKDbare (tested
-// before the KD tree; src/pathtrace.cu:1600-1640) -> t_min / hit, and the traversal's first step, the
-// KD root's box (same intersectAABB, same invdir): false = the traversal ends there.
-constexpr int ORDERED_GEOMS = 8;  // scenes with at most this many analytic geoms test them nearest-first
-__device__ __attribute__((always_inline)) inline bool prep_ray(const DevScene& S, bool kd, f3 o, f3 d, float& t_min, int& hit) {
-  Ray ray;
-  ray.origin = o;
-  ray.direction = d;
-  ray.isinside = false;
-  ray.sdepth = 0.0f;
-  t_min = FLT_MAXV;
-  hit = -1;
-  f3 tmp_i = mk3(0, 0, 0), tmp_n = mk3(0, 0, 0);
-  const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-  const bool finite = fabsf(inv.x) < FLT_INFV && fabsf(inv.y) < FLT_INFV && fabsf(inv.z) < FLT_INFV;
-  const int ng = S.num_geoms;
-  if (finite && ng <= ORDERED_GEOMS) {
-    // Nearest-first: the reference keeps the first geom (index order) reaching the smallest t > 0; here
-    // the geoms whose bounds the ray enters are tested in order of their entry bound, stopping once that
-    // bound exceeds the best t, and ties go to the lower index -- the same winner and the same t, with
-    // typically one or two exact tests per ray instead of one per geom the wave's rays come near.
-    float lo[ORDERED_GEOMS];
-    uint32_t pending = 0;
-#pragma unroll
-    for (int g = 0; g < ORDERED_GEOMS; g++) {
-      lo[g] = FLT_INFV;
-      if (g < ng && geom_entry_bound(S.geoms[g], o, inv, lo[g])) pending |= 1u << g;
-    }
-    while (pending) {
-      int gb = 0;
-      float lb = FLT_INFV;
-#pragma unroll
-      for (int g = 0; g < ORDERED_GEOMS; g++)
-        if (((pending >> g) & 1u) && lo[g] < lb) {
-          lb = lo[g];
-          gb = g;
-        }
-      if (lb > t_min) break;  // every remaining geom's exact t exceeds the best
-      pending &= ~(1u << gb);
-      const DevGeom& G = S.geoms[gb];
-      const float t = G.type == 1 ? boxIntersectionTest(G, ray, tmp_i, tmp_n)
-                                  : sphereIntersectionTest(G, ray, tmp_i, tmp_n);
-      if (t > 0.0f && (t < t_min || (t == t_min && gb < hit))) {
-        t_min = t;
-        hit = gb;
-      }
-    }
-  } else {
-    float t = 0;
-    for (int g = 0; g < ng; g++) {
-      const DevGeom& G = S.geoms[g];
-      if (finite && !geom_may_hit(G, o, inv)) {
-        t = -1.0f;  // the exact test would miss
-      } else if (G.type == 1) {
-        t = boxIntersectionTest(G, ray, tmp_i, tmp_n);
-      } else if (G.type == 0) {
-        t = sphereIntersectionTest(G, ray, tmp_i, tmp_n);
-      }
-      if (t > 0.0f && t_min > t) {
-        t_min = t;
-        hit = g;
-      }
-    }
-  }
-  if (!kd) return false;
-  float dist;
-  return intersectAABB(o, inv, make_float4(S.rlo.x, S.rlo.y, S.rlo.z, S.rhi.x),
-                       make_float4(S.rhi.y, S.rhi.z, 0.0f, 0.0f), dist);
-}
-
-// The analytic geoms of pathTraceOneBounceKDbare (tested before the KD tree; src/pathtrace.cu:1600-1640),
-// one lane per live path, consecutive paths per wave: {t_min bits, geom index} for k_trace.
-//
-// The KD traversal's first step tests the root's box, and a ray that misses it ends there with no other
-// effect (traverseKDbareShortHybrid: `!hitGeom && parentID == -1` -> break), so such a ray's hit record
-// is final here: it is written now, and only the rays that meet the root box are listed (cand, ccount)
-// for the intersect kernel -- whose lanes then all hold rays that actually walk the tree.
-// k_gen_geoms_b / k_geoms_b: 256-thread workgroups (one wave per SIMD), one candidate-list atomic per
-// workgroup.  A 1024-thread workgroup needs 4 waves x 88 VGPRs on every SIMD of a CU, which a CU running an
-// intersect workgroup (4 x 96 of 512) never has, so the batch's first launch waited for CUs free of k_trace:
-// 0.93 ms per launch in the pipelined bench against 0.18 ms alone (profiles/r03_ab_log.md); one 88-VGPR
-// wave fits beside the intersect workgroup
-#ifndef KDPT_GEN_BLOCK
-#define KDPT_GEN_BLOCK 256  // tools/build_variant.sh experiments only
-#endif
-constexpr int GEN_BLOCK = KDPT_GEN_BLOCK;
-// One workgroup's part: the analytic geoms + root-box test of its paths (live: the lane holds a path still
-// bouncing), the final hit record of the rays that end there, and the others appended to the candidate list
-// through *ccnt (one atomic per workgroup; a single counter hit once per wave by ~10k waves serialises for
-// ~100 us at 800x800).  Every thread of the workgroup must call it.
-template <int TB = GEN_BLOCK>
-__device__ __attribute__((always_inline)) inline void geoms_core(const DevScene& S, bool live, int i, f3 o, f3 d,
-                                                                 float4* __restrict__ cray, int2* __restrict__ hits,
-                                                                 int* __restrict__ cand, int* __restrict__ ccnt,
-                                                                 Counters* count_aabb) {
-  const bool kd = S.has_obj && S.num_nodes > 0;
-  bool tested = false, walk = false;  // traversed at all / goes on to the intersect kernel
-  float t_min = 0.0f;
-  int hit = -1;
-  if (live) {
-    tested = kd;
-    walk = prep_ray(S, kd, o, d, t_min, hit);
-    if (!walk) hits[i] = make_int2(hit, -1);  // final: the analytic geoms' hit (code -1: none)
-  }
-  __shared__ int s_wcount[TB / 64], s_base;
-  const unsigned long long wm = __ballot(walk);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) s_wcount[wv] = __popcll(wm);
-  if (count_aabb) {  // count mode: the root test of the rays that end here, and the candidates
-    const unsigned long long miss = __ballot(tested && !walk);
-    if (lane == 0 && miss) {
-      atomicAdd(&count_aabb->aabb, (unsigned long long)__popcll(miss));
-      atomicAdd(&count_aabb->aabb_prep, (unsigned long long)__popcll(miss));
-    }
-    if (lane == 0 && wm) atomicAdd(&count_aabb->cand, (unsigned long long)__popcll(wm));
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int tot = 0;
-    for (int w = 0; w < TB / 64; w++) {
-      const int c = s_wcount[w];
-      s_wcount[w] = tot;
-      tot += c;
-    }
-    s_base = tot ? atomicAdd(ccnt, tot) : 0;
-  }
-  __syncthreads();
-  if (walk) {
-    const int slot = s_base + s_wcount[wv] + (int)lane_prefix(wm);
-    cand[slot] = i;
-    cray[2 * slot] = make_float4(o.x, o.y, o.z, t_min);
-    cray[2 * slot + 1] = make_float4(d.x, d.y, d.z, ibits(hit));
-  }
-}
-
-__device__ __attribute__((always_inline)) inline void geoms_body(const DevScene& S, PathBuf paths, const int* counts,
-                                                                 int depth, float4* __restrict__ cray,
-                                                                 int2* __restrict__ hits, int* __restrict__ cand,
-                                                                 int* __restrict__ ccount, Counters* count_aabb,
-                                                                 unsigned long long* gspan) {
-  const int n = counts[depth];
-  if ((int)(blockIdx.x * blockDim.x) >= n) return;  // uniform per block
-  if (threadIdx.x == 0) atomicMin(&gspan[2 * depth], (unsigned long long)__builtin_amdgcn_s_memrealtime());
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  // finished paths (compaction off) are skipped, as pathTraceOneBounce* skips them
-  const bool live = i < n && fbits(paths.p2[i].w) > 0;
-  f3 o = mk3(0, 0, 0), d = mk3(0, 0, 1);
-  if (live) {
-    const float4 q0 = paths.p0[i], q1 = paths.p1[i];
-    o = mk3(q0.x, q0.y, q0.z);
-    d = mk3(q1.x, q1.y, q1.z);
-  }
-  geoms_core<GEN_BLOCK>(S, live, i, o, d, cray, hits, cand, ccount + depth, count_aabb);
-  if (threadIdx.x == 0) atomicMax(&gspan[2 * depth + 1], (unsigned long long)__builtin_amdgcn_s_memrealtime());
-}
-
-// Launched for a whole batch of iterations at once (blockIdx.y = iteration).
-struct GeomsIter {
-  PathBuf paths;
-  const int* counts;
-  float4* cray;
-  int2* hits;
-  int* cand;
-  int* ccount;
-};
-struct GeomsBatch {
-  DevScene S;
-  GeomsIter it[MAXB];
-  int depth;
-  Counters* count_aabb;
-  unsigned long long* gspan;
-};
-__global__ __launch_bounds__(GEN_BLOCK) void k_geoms_b(GeomsBatch B) {
-  const GeomsIter& g = B.it[blockIdx.y];
-  geoms_body(B.S, g.paths, g.counts, B.depth, g.cray, g.hits, g.cand, g.ccount, B.count_aabb, B.gspan);
-}
-
-// A batch's camera rays and their bounce-0 intersect-stage first part in one launch (blockIdx.y = iteration):
-// each lane generates its pixel's ray (written out for the shading) and tests it against the analytic geoms
-// and the KD root box straight from registers.  The bounce-0 candidate counter cannot be the one the
-// generation zeroes (other workgroups of this launch already add to it), so bounce 0 counts into
-// ccount0[parity] of the context, and the launch zeroes ccount0[!parity] for the context's next use (always
-// on the same stream, so nothing still reads it).
-struct GenGeomsIter {
-  int* ccount0;       // this use's bounce-0 candidate counter
-  int* ccount0_next;  // the next use's (zeroed here)
-  float4* cray;
-  int2* hits;
-  int* cand;
-};
-struct GenGeomsBatch {
-  GenBatch g;
-  DevScene S;
-  GenGeomsIter it[MAXB];
-  Counters* count_aabb;
-};
-__global__ __launch_bounds__(GEN_BLOCK) void k_gen_geoms_b(GenGeomsBatch B) {
-  const GenIter& g = B.g.it[blockIdx.y];
-  const GenGeomsIter& q = B.it[blockIdx.y];
-  f3 o = mk3(0, 0, 0), d = mk3(0, 0, 1);
-  const bool valid = gen_rays_body(B.g.cam, g.iter, B.g.traceDepth, g.out, B.g.focalLength, B.g.dofAngle,
-                                   B.g.antialias, g.counts, B.g.ncounts, g.work, B.g.nwork, g.trace_t, g.lb, B.g.nlb,
-                                   g.zero_image, o, d);
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0) *q.ccount0_next = 0;
-  geoms_core<GEN_BLOCK>(B.S, valid && B.g.traceDepth > 0, i, o, d, q.cray, q.hits, q.cand, q.ccount0,
-                        B.count_aabb);
-}
-
-#ifdef KDPT_TAIL_PROF  // tools/build_variant.sh experiments only: intersect workgroup life / tail (ticks)
-__device__ unsigned long long g_tail_prof[4];
-#endif
-
-// KD traversal of every live path.  Each lane holds one ray; whenever rays finish, the idle lanes take
-// the next paths of the bounce from a device counter, so a wave stays full until the bounce runs out
-// of paths (the per-ray algorithm is unchanged -- only which lane runs it, and when).
-// Compiled for 5 waves per SIMD although a workgroup brings only 4 (its LDS tree copy keeps it alone on the
-// CU): the cap (96 VGPRs instead of 108, a few spilled to scratch outside the hot loops) leaves 128 VGPRs per
-// SIMD, room for a fused-shading wave of another batch on the same CU while the traversal runs -- and its LDS
-// (WaveProf only in the counting kernel) leaves room for that workgroup's 4.2 KB.  A/B +2.8 %.
-#ifndef KDPT_TRACE_WAVES
-#define KDPT_TRACE_WAVES 5  // tools/build_variant.sh experiments
-#endif
-// (only with the tree in LDS: the 256-thread workgroups of the other modes share CUs anyway, and the C5
-// icosphere, whose tree lives in HBM, lost 3.5 % to the cap)
-#define KDPT_TRACE_ATTR __attribute__((amdgpu_waves_per_eu(tree_in_lds(MODE) ? KDPT_TRACE_WAVES : 1)))
-template <bool HYBRID, bool COUNT, int MODE>
-__global__ __launch_bounds__(trace_block<MODE>()) KDPT_TRACE_ATTR void k_trace(TraceArgs A) {
-  constexpr int TB = trace_block<MODE>();
-  extern __shared__ int4 s_tree[];
-  __shared__ WaveLeafLDS s_leaf[TB / 64];
-  __shared__ WaveProf s_prof[COUNT ? TB / 64 : 1];
-  const DevScene& S = A.S;
-  int pre[MAXB + 1];  // the batch's paths, concatenated: iteration b owns queue slots [pre[b], pre[b+1])
-  pre[0] = 0;
-#pragma unroll
-  for (int b = 0; b < MAXB; b++) pre[b + 1] = pre[b] + (b < A.nb ? A.it[b].ccount[A.depth] : 0);
-  const int n = pre[MAXB];
-  // tree copy: NodesPacked (2 x 16 bytes per node) or NodesDerived (16 bytes), then the cluster boxes
-  constexpr int NODE_WORDS = MODE == TREE_LDS ? 2 : 1;
-  if (tree_in_lds(MODE)) {
-    if (n == 0) return;  // uniform: nothing to trace
-    const int words = NODE_WORDS * S.num_nodes;
-    const int4* src = MODE == TREE_LDS ? S.pnodes : (MODE == TREE_LDS16S ? S.snodes : S.dnodes);
-    for (int k = threadIdx.x; k < words; k += TB) s_tree[k] = src[k];
-    if (MODE == TREE_LDS16S) {
-      for (int k = threadIdx.x; k < S.num_supers; k += TB) s_tree[words + k] = S.sup[k];
-    } else if (MODE != TREE_LDS16G) {
-      float4* s_cl = reinterpret_cast<float4*>(s_tree + words);
-      for (int k = threadIdx.x; k < S.num_clusters; k += TB) {
-        s_cl[2 * k] = S.cl_lo[k];
-        s_cl[2 * k + 1] = S.cl_hi[k];
-      }
-    }
-    __syncthreads();
-  }
-  const int lane = threadIdx.x & 63;
-  WaveLeafLDS* W = &s_leaf[threadIdx.x >> 6];
-  WaveProf* P = &s_prof[COUNT ? (threadIdx.x >> 6) : 0];
-  if (COUNT && lane < PROF_SLOTS) P->prof[lane] = 0;
-  if (COUNT && lane == 0) P->tail_t0 = 0;
-  W->slot[lane] = 0;  // pair_owner's invariant
-  // launch duration on the device clock (first block start .. last block end); the HIP events around
-  // the launch also count time spent queued behind other streams' kernels when iterations overlap
-  __shared__ int s_waves_done;
-#ifdef KDPT_TAIL_PROF
-  __shared__ unsigned long long s_t0, s_tex;
-#endif
-  if (threadIdx.x == 0) {
-    s_waves_done = 0;
-    atomicMin(&A.trace_t[2 * A.depth], (unsigned long long)__builtin_amdgcn_s_memrealtime());
-#ifdef KDPT_TAIL_PROF
-    s_t0 = __builtin_amdgcn_s_memrealtime();
-    s_tex = ~0ull;
-#endif
-  }
-  __syncthreads();
-  int* work = A.work + A.depth;
-  const unsigned long long rt0 = COUNT ? __builtin_amdgcn_s_memrealtime() : 0ull;
-  const unsigned long long t_k0 = COUNT ? __builtin_readcyclecounter() : 0ull;
-  TraverseCounters cnt{};
-  WaveRay R;  // every field defined: idle lanes take part in the wave-level code with a finished ray
-  wave_ray_start(S, R, mk3(0.0f, 0.0f, 0.0f), mk3(0.0f, 0.0f, 1.0f), FLT_MAXV, -1, W);
-  R.done = true;
-  int pidx = -1;  // the lane's path (-1: idle)
-  int pb = 0;     // ... and the batch iteration it belongs to
-  // Path slots: each wave first takes a static run of 64 consecutive slots, the runs dealt out wave-major
-  // across the workgroups (run r goes to wave r / grid of workgroup r % grid): a bounce with few rays then
-  // still fills every CU (the kernel is issue-bound: rays piled onto a few CUs would leave the others idle)
-  // while each wave stays dense (a node trip costs the same whatever the number of walking lanes).  A device
-  // counter hands out the rest, exactly as many as the wave has idle lanes, so the tail stays balanced.
-  const int nwaves = gridDim.x * (TB / 64);
-  const int wid = (threadIdx.x >> 6) * gridDim.x + blockIdx.x;
-  const int srun = KDPT_SRUN_SPREAD ? min(64, max(1, (n + nwaves - 1) / nwaves)) : 64;
-  bool first = true, exhausted = false;
-  long long rounds = 0;
-#ifdef KDPT_TAIL_PROF
-  unsigned long long tex_seen = 0;
-#endif
-  while (true) {
-    if (__ballot(1) != ~0ull) {  // the refill protocol needs the whole wave here
-      atomicOr(S.fault, 4);
-      break;
-    }
-    // ---- refill idle lanes ----
-    if (COUNT) prof_lap(P, -1);
-    const unsigned long long im = exhausted ? 0ull : __ballot(pidx < 0);
-    if (im) {
-      const int p = (int)lane_prefix(im);
-      int k;
-      if (first) {  // static run: slots [wid*srun, wid*srun + srun)
-        first = false;
-        k = p < srun ? wid * srun + p : n;
-        exhausted = (long long)nwaves * srun >= n;
-      } else {
-        int b = 0;
-        if (lane == 0) b = nwaves * srun + atomicAdd(work, __popcll(im));
-        const int base = __builtin_amdgcn_readfirstlane(b);  // lane 0 is active: the whole wave is here
-        k = base + p;
-        exhausted = base + __popcll(im) >= n;  // the counter only grows: later rounds find nothing
-      }
-      if (COUNT && exhausted && lane == 0 && !P->tail_t0) P->tail_t0 = __builtin_readcyclecounter();
-#ifdef KDPT_TAIL_PROF
-      if (exhausted && !tex_seen) tex_seen = __builtin_amdgcn_s_memrealtime();
-#endif
-      if (pidx < 0 && k < n) {
-        int b = 0;
-#pragma unroll
-        for (int q = 1; q < MAXB; q++) b += k >= pre[q];
-        const int* cand = A.it[0].cand;
-        const float4* cray = A.it[0].cray;
-        int local = k;
-#pragma unroll
-        for (int q = 1; q < MAXB; q++)
-          if (b == q) {
-            cand = A.it[q].cand;
-            cray = A.it[q].cray;
-            local = k - pre[q];
-          }
-        // the slot's path index and its ray (written in queue order with the slot): three independent loads
-        // of consecutive slots, not a slot load followed by scattered path loads
-        const int i = cand[local];
-        const float4 q0 = cray[2 * local], q1 = cray[2 * local + 1];
-        pidx = i;
-        pb = b;
-        wave_ray_start(S, R, mk3(q0.x, q0.y, q0.z), mk3(q1.x, q1.y, q1.z), q0.w, fbits(q1.w), W);
-      }
-    }
-    if (COUNT) prof_lap(P, PROF_SETUP_CYC);
-    const bool busy = pidx >= 0 && !R.done;
-    if (__any(busy)) {
-      const bool fastAABB = __all(!busy || (fabsf(R.invdir.x) < FLT_INFV && fabsf(R.invdir.y) < FLT_INFV &&
-                                            fabsf(R.invdir.z) < FLT_INFV));
-      if (MODE == TREE_LDS)
-        trace_phase<HYBRID, COUNT>(S, NodesPacked{s_tree},
-                                   ClustersInterleaved{reinterpret_cast<const float4*>(s_tree + 2 * S.num_nodes)}, R,
-                                   fastAABB, S.num_materials, cnt, W, P);
-      else if (MODE == TREE_LDS16)
-        trace_phase<HYBRID, COUNT>(S, NodesDerived{s_tree},
-                                   ClustersInterleaved{reinterpret_cast<const float4*>(s_tree + S.num_nodes)}, R,
-                                   fastAABB, S.num_materials, cnt, W, P);
-      else if (MODE == TREE_LDS16G)
-        trace_phase<HYBRID, COUNT>(S, NodesDerived{s_tree}, ClustersSplit{S.cl_lo, S.cl_hi}, R, fastAABB,
-                                   S.num_materials, cnt, W, P);
-      else if (MODE == TREE_LDS16S)
-        trace_phase<HYBRID, COUNT>(
-            S, NodesDerived{s_tree},
-            ClustersSuper{s_tree + S.num_nodes, S.cl_lo, S.cl_hi, S.cl_n, S.cl_u, S.cl_v, S.cl_w}, R, fastAABB,
-            S.num_materials, cnt, W, P);
-      else if (MODE == TREE_PACKED)
-        trace_phase<HYBRID, COUNT>(S, NodesPacked{S.pnodes}, ClustersSplit{S.cl_lo, S.cl_hi}, R, fastAABB,
-                                   S.num_materials, cnt, W, P);
-      else
-        trace_phase<HYBRID, COUNT>(S, NodesWide{S.nodes}, ClustersSplit{S.cl_lo, S.cl_hi}, R, fastAABB,
-                                   S.num_materials, cnt, W, P);
-    }
-    // ---- finished rays: their hit record (what ShadeableIntersection would carry) ----
-    if (pidx >= 0 && R.done) {
-      if (COUNT && A.prof_steps) {  // (its atomics distort the cycle profile: a separate run)
-        const int st = R.guard;
-        atomicAdd(&A.counters->steps[min(st >> 2, 63)], 1ull);
-        const float4 lo = S.rlo, hi = S.rhi;
-        const float ax = (lo.x - R.o.x) * R.invdir.x, bx = (hi.x - R.o.x) * R.invdir.x;
-        const float ay = (lo.y - R.o.y) * R.invdir.y, by = (hi.y - R.o.y) * R.invdir.y;
-        const float az = (lo.z - R.o.z) * R.invdir.z, bz2 = (hi.z - R.o.z) * R.invdir.z;
-        const float t0 = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz2), 0.0f));
-        const float t1 = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz2));
-        const float dx = hi.x - lo.x, dy = hi.y - lo.y, dz = hi.z - lo.z;
-        const float diag = sqrtf(dx * dx + dy * dy + dz * dz);
-        const float f = diag > 0.0f ? 8.0f * fmaxf(t1 - t0, 0.0f) / diag : 0.0f;
-        const int cb = f >= 7.0f || !(f == f) ? 7 : (int)f;
-        atomicAdd(&A.counters->chord_steps[cb], (unsigned long long)st);
-        atomicAdd(&A.counters->chord_n[cb], 1ull);
-      }
-      const Hit& h = R.h;
-      const int code = h.hit_geom_index == -1 ? -1 : (h.obj_intersect ? -(R.objTri + 2) : h.hit_geom_index);
-      int2* hits = A.it[0].hits;
-#pragma unroll
-      for (int q = 1; q < MAXB; q++)
-        if (pb == q) hits = A.it[q].hits;
-      hits[pidx] = make_int2(code, h.objMaterialIdx);
-      pidx = -1;
-    }
-    if (exhausted && !__any(pidx >= 0)) break;
-    if (++rounds > (1ll << 20)) {  // unreachable: every round finishes or advances some ray
-      if (lane == 0) atomicOr(S.fault, 8);
-      break;
-    }
-  }
-  if (COUNT) {
-    prof_lap(P, PROF_POST_CYC);
-    if (lane == 0 && P->tail_t0) P->prof[PROF_TAIL_CYC] += __builtin_readcyclecounter() - P->tail_t0;
-    flush_counters(A.counters, cnt, P, t_k0);
-    if (lane == 0) {
-      const unsigned long long us10 = (__builtin_amdgcn_s_memrealtime() - rt0) / 1000;  // 100 MHz ticks
-      atomicAdd(&A.counters->life[us10 < 63 ? us10 : 63], 1ull);
-    }
-  }
-#ifdef KDPT_TAIL_PROF
-  if (lane == 0 && tex_seen) atomicMin(&s_tex, tex_seen);
-#endif
-  if (lane == 0 && atomicAdd(&s_waves_done, 1) == TB / 64 - 1) {
-    atomicMax(&A.trace_t[2 * A.depth + 1], (unsigned long long)__builtin_amdgcn_s_memrealtime());
-#ifdef KDPT_TAIL_PROF
-    // this workgroup's life, and its part after its first wave found the ray queue empty
-    const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
-    const unsigned long long tex = s_tex == ~0ull ? t1 : s_tex;
-    atomicAdd(&g_tail_prof[0], t1 - s_t0);
-    atomicAdd(&g_tail_prof[1], t1 - (tex < s_t0 ? s_t0 : tex));
-    atomicAdd(&g_tail_prof[2], 1ull);
-#endif
-  }
-}
-
-// ---------------------------------------------------------------------------
-// pathTraceOneBounce (src/pathtrace.cu:402-628, enable_kd = false): the brute-force intersect kernel,
-// the reference's "bruteforce" / "bbox" benchmark columns.  One lane per live path, consecutive paths
-// per wave; the analytic geoms, then every OBJ triangle in file order, shape after shape.
-//
-// The triangle index is wave-uniform (every lane of a wave tests the same triangle), so the triangle
-// is fetched with scalar loads once per wave.  Each lane first evaluates, without the division,
-// the exact values the reference's Moller-Trumbore divides (a, u = dot(s,p), v = dot(d,q),
-// w = dot(e2,q): same operations, same order, so the same bits) and rejects the triangle when the
-// decision is certain whatever f = 1/a rounds to; only the remaining lanes (the line crosses the
-// triangle, or a decision sits within a few ulps of its threshold) run the reference's exact test and
-// hit point.  Output: the same hit record as k_trace (code, objMaterialIdx).
-// ---------------------------------------------------------------------------
-struct BruteShape {
-  float4 lo;  // bbox min (the reference's float(obj_polysbboxes[i + k] - 0.01)), w = index count bits
-  float4 hi;  // bbox max (+ 0.01), w = obj_materialOffsets[i] bits
-};
-
-struct BruteArgs {
-  DevScene S;  // tv0/te1/te2/tn0..2: the OBJ triangles in file order
-  PathBuf paths;
-  const int* counts;
-  int depth;
-  int2* hits;
-  const BruteShape* shapes;
-  int num_shapes;
-  const float4* chunk_lo;  // boxes of the file-order triangles [64j, 64j + 64) (the tested triangles
-  const float4* chunk_hi;  // v0, v0 + e1, v0 + e2, rounded outward)
-  Counters* counters;
-  unsigned long long* trace_t;
-};
-
-// intersectBbox (src/interactions.h:136-165), std::min/max as in intersectAABBarrays
-__device__ inline float intersectBbox(f3 o, f3 d, float4 lo, float4 hi) {
-  const f3 invdir = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-  const float v1 = (lo.x - o.x) * invdir.x, v2 = (hi.x - o.x) * invdir.x;
-  const float v3 = (lo.y - o.y) * invdir.y, v4 = (hi.y - o.y) * invdir.y;
-  const float v5 = (lo.z - o.z) * invdir.z, v6 = (hi.z - o.z) * invdir.z;
-  const float dmin = std_max(std_max(std_min(v1, v2), std_min(v3, v4)), std_min(v5, v6));
-  const float dmax = std_min(std_min(std_max(v1, v2), std_max(v3, v4)), std_max(v5, v6));
-  if (dmax < 0) return dmax;
-  if (dmin > dmax) return dmax;
-  return dmin;
-}
-
-// Is glm::intersectRayTriangle certain to return false?  a, u, v, w are the reference's exact values;
-// f = RN(1/a) > 0 (a >= eps).  bx = RN(f*u) < 0 for u < -a*2^-100 (|f*u| >= 2^-101, far from rounding
-// to -0); bx > 1 for u > RN(a*(1+2^-20)) (then u/a > 1 + 2^-21 and two roundings cannot bring it to 1);
-// likewise by, the sum (u + v > a*(1+2^-18) with u, v >= 0) and bz = RN(f*w) < 0.
-__device__ inline bool tri_certain_miss(float a, float u, float v, float w) {
-  const float tiny = a * 0x1p-100f;
-  const float one_u = a * 1.00000095367431640625f;  // a * (1 + 2^-20)
-  const float one_s = a * 1.000003814697265625f;    // a * (1 + 2^-18)
-  return !(a >= FLT_EPS) || u < -tiny || u > one_u || v < -tiny || w < -tiny ||
-         (u >= 0.0f && v >= 0.0f && u + v > one_s);
-}
-
-template <bool COUNT>
-__device__ inline void brute_triangle(const DevScene& S, int k, const TriData& T, f3 o, f3 d, float& t_min, int& best,
-                                      bool take, TraverseCounters& cnt) {
-  const f3 v0 = mk3(T.v0.x, T.v0.y, T.v0.z), e1 = mk3(T.e1.x, T.e1.y, T.e1.z), e2 = mk3(T.e2.x, T.e2.y, T.e2.z);
-  const f3 p = cross(d, e2);
-  const float a = dot(e1, p);
-  const f3 s = sub(o, v0);
-  const float u = dot(s, p);
-  const f3 q = cross(s, e1);
-  const float v = dot(d, q);
-  const float w = dot(e2, q);
-  if (take && !tri_certain_miss(a, u, v, w)) {
-    float bx, by, bz;
-    if (tri_test_v(T, o, d, bx, by, bz) == 2) {  // intersected: bary.z >= 0
-      if (COUNT) cnt.hit++;
-      f3 hp, nn;
-      const float t = tri_hit_t<true>(S, k, o, d, bx, by, bz, hp, nn);  // hit += norm * 0.0001f
-      if (t > 0.0f && t_min > t) {
-        t_min = t;
-        best = k;
-      }
-    }
-  }
-}
-
-template <bool USEBBOX, bool COUNT>
-__global__ __launch_bounds__(TILE) void k_brute(BruteArgs A) {
-  const int n = A.counts[A.depth];
-  if ((int)blockIdx.x * TILE >= n) return;  // uniform per block
-  if (threadIdx.x == 0) atomicMin(&A.trace_t[2 * A.depth], (unsigned long long)__builtin_amdgcn_s_memrealtime());
-  const DevScene& S = A.S;
-  const int i = blockIdx.x * TILE + threadIdx.x;
-  bool live = false;
-  f3 o = mk3(0.0f, 0.0f, 0.0f), d = mk3(0.0f, 0.0f, 1.0f);
-  if (i < n) {
-    const float4 q0 = A.paths.p0[i], q1 = A.paths.p1[i];
-    live = fbits(A.paths.p2[i].w) > 0;
-    o = mk3(q0.x, q0.y, q0.z);
-    d = mk3(q1.x, q1.y, q1.z);
-  }
-  // the analytic geoms (src/pathtrace.cu:461-483)
-  float t_min = FLT_MAXV;
-  int geom = -1;
-  if (live) {
-    Ray ray;
-    ray.origin = o;
-    ray.direction = d;
-    ray.isinside = false;
-    ray.sdepth = 0.0f;
-    f3 tmp_i, tmp_n;
-    float t = 0;
-    const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-    const bool finite = fabsf(inv.x) < FLT_INFV && fabsf(inv.y) < FLT_INFV && fabsf(inv.z) < FLT_INFV;
-    for (int g = 0; g < S.num_geoms; g++) {
-      const DevGeom& G = S.geoms[g];
-      if (finite && !geom_may_hit(G, o, inv)) t = -1.0f;
-      else if (G.type == 1) t = boxIntersectionTest(G, ray, tmp_i, tmp_n);
-      else if (G.type == 0) t = sphereIntersectionTest(G, ray, tmp_i, tmp_n);
-      if (t > 0.0f && t_min > t) {
-        t_min = t;
-        geom = g;
-      }
-    }
-  }
-  // the polygon loop (src/pathtrace.cu:485-576)
-  const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-  const bool cull = __all(!live || (fabsf(inv.x) < FLT_INFV && fabsf(inv.y) < FLT_INFV && fabsf(inv.z) < FLT_INFV));
-  TraverseCounters cnt{};
-  int best = -1;
-  int objMat = -1;
-  int iterator = 0;  // in vertex indices, like the reference; advances only past shapes whose bbox passed
-  if (S.has_obj) {
-    for (int sh = 0; sh < A.num_shapes; sh++) {
-      const BruteShape B = A.shapes[sh];
-      objMat = fbits(B.hi.w);
-      const int nidx = fbits(B.lo.w);
-      bool take = live;
-      if (USEBBOX) take = live && intersectBbox(o, d, B.lo, B.hi) > -1.0f;
-      const unsigned long long tm = __ballot(take);
-      if (tm) {
-        const int it0 = __shfl(iterator, __builtin_ctzll(tm));
-        if (__all(!take || iterator == it0)) {
-          // every lane that tests this shape starts at the same triangle: scalar triangle fetches
-          const int k0 = __builtin_amdgcn_readfirstlane(it0 / 3);
-          const int nt = nidx / 3;
-          // 64-triangle chunks: no triangle of a chunk whose box the lane's line misses (box widened as in
-          // cluster_may_pass) passes the u/v tests, so those lanes skip it, and the wave skips a chunk no lane
-          // can hit; the others test its triangles in file order as before
-          for (int k = k0; k < k0 + nt;) {
-            const int j = k >> 6, kend = min(k0 + nt, (j + 1) << 6);
-            const bool may = take && (!cull || cluster_may_pass(A.chunk_lo[j], A.chunk_hi[j], o, inv, S.cl_margin));
-            if (__any(may)) {
-              for (; k < kend; k++) {
-                const TriData T = tri_load(S, k);
-                brute_triangle<COUNT>(S, k, T, o, d, t_min, best, may, cnt);
-              }
-            }
-            k = kend;
-          }
-        } else {
-          const int nt = nidx / 3;
-          for (int j = 0; j < nt; j++) {
-            const int k = iterator / 3 + j;
-            if (take) {
-              const TriData T = tri_load(S, k);
-              brute_triangle<COUNT>(S, k, T, o, d, t_min, best, true, cnt);
-            }
-          }
-        }
-        if (COUNT && take) cnt.tri += nidx / 3;
-      }
-      if (take) iterator += nidx;
-    }
-  }
-  if (i < n && live) {
-    const int code = best >= 0 ? -(best + 2) : geom;
-    A.hits[i] = make_int2(code, objMat);
-  }
-  if (COUNT) {
-    unsigned int tr = cnt.tri, hi = cnt.hit;
-    for (int off = 32; off > 0; off >>= 1) {
-      tr += __shfl_down(tr, off);
-      hi += __shfl_down(hi, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-      atomicAdd(&A.counters->tri, (unsigned long long)tr);
-      atomicAdd(&A.counters->hit, (unsigned long long)hi);
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) atomicMax(&A.trace_t[2 * A.depth + 1], (unsigned long long)__builtin_amdgcn_s_memrealtime());
-}
-
-// ---------------------------------------------------------------------------
-// pathTraceOneBounceKDbareBoxes (src/pathtrace.cu:1738-1885, viz_kd): the analytic geoms, then every KD
-// node's box as a box (boxIntersectionTestBox = boxIntersectionTest of the node's unit-cube transform).
-// One lane per path; the node index is wave-uniform, so each box's matrices are scalar loads.  A winning
-// node box k is reported as geom num_geoms + k (its record carries material num_materials - 1), which
-// k_shade recomputes like any analytic geom.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(TILE) void k_viz(DevScene S, PathBuf paths, const int* counts, int depth, int2* hits,
-                                               unsigned long long* trace_t) {
-  const int n = counts[depth];
-  if ((int)blockIdx.x * TILE >= n) return;
-  if (threadIdx.x == 0) atomicMin(&trace_t[2 * depth], (unsigned long long)__builtin_amdgcn_s_memrealtime());
-  const int i = blockIdx.x * TILE + threadIdx.x;
-  if (i < n && fbits(paths.p2[i].w) > 0) {
-    const float4 q0 = paths.p0[i], q1 = paths.p1[i];
-    Ray ray;
-    ray.origin = mk3(q0.x, q0.y, q0.z);
-    ray.direction = mk3(q1.x, q1.y, q1.z);
-    ray.isinside = false;
-    ray.sdepth = q0.w;
-    const f3 inv = mk3(1.0f / ray.direction.x, 1.0f / ray.direction.y, 1.0f / ray.direction.z);
-    const bool finite = fabsf(inv.x) < FLT_INFV && fabsf(inv.y) < FLT_INFV && fabsf(inv.z) < FLT_INFV;
-    float t_min = FLT_MAXV, t = 0;
-    int hit = -1;
-    f3 tmp_i, tmp_n;
-    const int total = S.num_geoms + (S.has_obj ? S.num_boxes : 0);
-    for (int g = 0; g < total; g++) {
-      const DevGeom& G = S.geoms[g];
-      if (finite && !geom_may_hit(G, ray.origin, inv)) t = -1.0f;
-      else if (G.type == 1) t = boxIntersectionTest(G, ray, tmp_i, tmp_n);
-      else if (G.type == 0) t = sphereIntersectionTest(G, ray, tmp_i, tmp_n);
-      if (t > 0.0f && t_min > t) {
-        t_min = t;
-        hit = g;
-      }
-    }
-    hits[i] = make_int2(hit, -1);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) atomicMax(&trace_t[2 * depth + 1], (unsigned long long)__builtin_amdgcn_s_memrealtime());
-}
-
-// ---------------------------------------------------------------------------
-// shadeMaterial + scatterRay (src/pathtrace.cu:1885-2100, src/interactions.h) +
-// partialGather, one lane per live path; writes the path in place and the tile's
-// survivor count (or, when sorting, its per-material histogram).
-// ---------------------------------------------------------------------------
-struct ShadeArgs {
-  DevScene S;
-  PathBuf paths;
-  const int2* hits;
-  float* image;
-  const int* counts;
-  int depth;
-  int iter;
-  float softness;
-  int enable_sss;
-  int* tile_counts;  // [ntiles] or key-major [MAX_KEYS][ntiles] when sorting
-  int* tile_kcounts;  // key-major [TRACE_KEYS][ntiles] survivors per trace-order class, or null
-  int ntiles;
-  int nkeys;
-  unsigned long long* total_segments;  // running sum of paths launched into the intersect kernel
-  const unsigned long long* trace_t;   // this bounce's intersect launch record (see TraceArgs)
-  const unsigned long long* gspan;     // ... and the k_geoms launches' record
-  unsigned long long* trace_total;     // [2]: summed launch ticks, launches (the batch's first iteration only)
-  unsigned long long* trace_rays;      // rays handed to the intersect kernel, summed (every iteration)
-  const int* ccount;                   // ... per bounce (this iteration's candidate counts)
-  // next bounce's intersect-stage first part (prep_ray) for every surviving path, fused here instead of a
-  // k_geoms pass: {t_min bits, (geom + 1) | walks << 16} at the path's current slot (k_scatter moves it)
-  int image_zeroed;  // `image` is this iteration's partial image, zeroed by its camera-ray launch: a pixel's
-                     // partialGather then reads +0 (each pixel's path ends once), so its load is skipped
-  int prep_on;
-  int2* prep;
-  int* tile_ccounts;   // [ntiles] walking survivors per tile
-  Counters* count_aabb;  // count mode: root tests of the rays that end there
-};
-
-// One path's shading (shadeMaterial + scatterRay, src/pathtrace.cu), the partialGather of a path that ends
-// here, and, when the hand-off runs, the next bounce's intersect-stage first part (prep_ray).
-struct ShadeOut {
-  float4 q0, q1, q2;
-  int pm;
-  bool changed, alive, walk, tested;
-  float tm;
-  int gh;
-};
-
-// Everything one path's shading reads from memory, loaded in one go: the path, its hit record, the pixel's
-// accumulated value (COMPACT: partialGather) and the hit triangle's vertex, edge and normal records (all in
-// flight together; k_shade_fused issues them before its publication barrier, and must read the hit record
-// before it lets later tiles write the next bounce's records into the same array).
-struct ShadeIn {
-  float4 q0, q1, q2;
-  int pm;
-  int2 hr;
-  float3 px_old;
-  TriData T;
-  float4 n1v, n2v, n3v;
-};
-
-template <bool COMPACT>
-__device__ __attribute__((always_inline)) inline void shade_load(const ShadeArgs& A, const DevScene& S, int i,
-                                                                 ShadeIn& in) {
-  in.q0 = A.paths.p0[i];
-  in.q1 = A.paths.p1[i];
-  in.q2 = A.paths.p2[i];
-  in.pm = A.paths.pm[i];
-  in.hr = A.hits[i];
-  in.px_old = make_float3(0.0f, 0.0f, 0.0f);
-  if (COMPACT && !A.image_zeroed) {
-    const float* px = A.image + 3 * (size_t)(fbits(in.q1.w) & 0x7fffffff);
-    in.px_old = make_float3(px[0], px[1], px[2]);
-  }
-  if (in.hr.x < -1 && fbits(in.q2.w) > 0) {
-    const int k = -in.hr.x - 2;
-    in.T = TriData{S.tv0[k], S.te1[k], S.te2[k]};
-    in.n1v = S.tn0[k];
-    in.n2v = S.tn1[k];
-    in.n3v = S.tn2[k];
-  }
-}
-
-template <bool HYBRID, bool COMPACT>
-__device__ __attribute__((always_inline)) inline void shade_one(const ShadeArgs& A, const DevScene& S, int i,
-                                                                const ShadeIn& in, ShadeOut& o) {
-  const float4 q0 = in.q0, q1 = in.q1, q2 = in.q2;
-  int matHit = in.pm;
-  const int2 hr = in.hr;
-  const int pw = fbits(q1.w);
-  const int pix = pw & 0x7fffffff;
-  Ray ray;
-  ray.origin = mk3(q0.x, q0.y, q0.z);
-  ray.direction = mk3(q1.x, q1.y, q1.z);
-  ray.isinside = (pw >> 31) & 1;
-  ray.sdepth = q0.w;
-  f3 color = mk3(q2.x, q2.y, q2.z);
-  int bounces = fbits(q2.w);
-  o.changed = bounces > 0;
-  const float3 px_old = in.px_old;
-  if (bounces > 0) {
-    float isect_t = -1.0f;
-    int isect_mat = 0;
-    if (hr.x != -1) {
-      f3 ip, nrm;
-      float t;
-      int mid;
-      if (hr.x < -1) {  // triangle: the traversal's final recomputation, repeated
-        float bx, by, bzk;
-        tri_test_v(in.T, ray.origin, ray.direction, bx, by, bzk);
-        t = tri_hit_t_n<HYBRID>(in.n1v, in.n2v, in.n3v, ray.origin, ray.direction, bx, by, bzk, ip, nrm);
-        mid = hr.y;
-      } else {
-        const DevGeom& G = S.geoms[hr.x];
-        t = G.type == 1 ? boxIntersectionTest(G, ray, ip, nrm) : sphereIntersectionTest(G, ray, ip, nrm);
-        mid = G.materialid;
-      }
-      Rng rng = seeded_rng(A.iter, i, A.depth);
-      matHit = mid;
-      scatterRay(ray, ip, nrm, S.materials[mid], rng, A.softness);
-      isect_t = t;
-      isect_mat = mid;
-    }
-    shade(isect_t, isect_mat, S.materials, A.enable_sss != 0, ray, color, bounces);
-  }
-  o.q0 = make_float4(ray.origin.x, ray.origin.y, ray.origin.z, ray.sdepth);
-  o.q1 = make_float4(ray.direction.x, ray.direction.y, ray.direction.z, ibits(pix | ((ray.isinside ? 1 : 0) << 31)));
-  o.q2 = make_float4(color.x, color.y, color.z, ibits(bounces));
-  o.pm = matHit;
-  if (COMPACT && bounces == 0) {
-    // partialGather: one live path per pixel, so this read-modify-write never collides
-    float* px = A.image + 3 * (size_t)pix;
-    px[0] = px_old.x + color.x;
-    px[1] = px_old.y + color.y;
-    px[2] = px_old.z + color.z;
-  }
-  o.alive = COMPACT ? (bounces != 0) : true;
-  o.walk = o.tested = false;
-  o.tm = 0.0f;
-  o.gh = -1;
-  if (COMPACT && A.prep_on && bounces != 0) {
-    o.walk = prep_ray(S, S.has_obj && S.num_nodes > 0, ray.origin, ray.direction, o.tm, o.gh);
-    o.tested = S.has_obj && S.num_nodes > 0;
-  }
-}
-
-__device__ inline void shade_stats(const ShadeArgs& A, int n) {
-  atomicAdd(A.total_segments, (unsigned long long)n);
-  // the intersect kernel of this bounce on the device clock (first block start .. last block end; a
-  // launch that had nothing to do left its record empty)
-  const unsigned long long t0 = A.trace_t[2 * A.depth], t1 = A.trace_t[2 * A.depth + 1];
-  const unsigned long long span = t1 > t0 ? t1 - t0 : 0ull;
-  if (A.trace_total && span) {
-    atomicAdd(&A.trace_total[0], span);
-    atomicAdd(&A.trace_total[1], 1ull);
-  }
-  if (A.trace_rays) atomicAdd(A.trace_rays, (unsigned long long)A.ccount[A.depth]);
-}
-
-__device__ inline void count_prep(const ShadeArgs& A, bool tested, bool walk) {
-  const unsigned long long miss = __ballot(tested && !walk), wm = __ballot(walk);
-  if ((threadIdx.x & 63) == 0 && miss) {
-    atomicAdd(&A.count_aabb->aabb, (unsigned long long)__popcll(miss));
-    atomicAdd(&A.count_aabb->aabb_prep, (unsigned long long)__popcll(miss));
-  }
-  if ((threadIdx.x & 63) == 0 && wm) atomicAdd(&A.count_aabb->cand, (unsigned long long)__popcll(wm));
-}
-
-// Shading in place, then k_scan + k_scatter (the material sort of iteration 2, no compaction, or the
-// trace-order classes).
-template <bool HYBRID, bool COMPACT, bool SORT>
-__global__ __launch_bounds__(TILE) void k_shade(ShadeArgs A) {
-  const int n = A.counts[A.depth];
-  const int tile = blockIdx.x;
-  if (tile * TILE >= n) return;  // uniform per block
-  const int i = tile * TILE + threadIdx.x;
-  if (i == 0) shade_stats(A, n);
-  __shared__ int s_hist[MAX_KEYS];
-  __shared__ int s_khist[TRACE_KEYS];
-  if (SORT) {
-    for (int k = threadIdx.x; k < MAX_KEYS; k += TILE) s_hist[k] = 0;
-  }
-  if (COMPACT && A.tile_kcounts && threadIdx.x < TRACE_KEYS) s_khist[threadIdx.x] = 0;
-  if (SORT || (COMPACT && A.tile_kcounts)) __syncthreads();
-  const DevScene& S = A.S;
-  bool alive = false, walk = false, tested = false;
-  int key = 0;
-  if (i < n) {
-    ShadeOut o;
-    ShadeIn in;
-    shade_load<COMPACT>(A, A.S, i, in);
-    shade_one<HYBRID, COMPACT>(A, A.S, i, in, o);
-    if (o.changed) {
-      A.paths.p0[i] = o.q0;
-      A.paths.p1[i] = o.q1;
-      A.paths.p2[i] = o.q2;
-      A.paths.pm[i] = o.pm;
-    }
-    alive = o.alive;
-    walk = o.walk;
-    tested = o.tested;
-    key = o.pm;
-    if (COMPACT && A.prep_on && alive) A.prep[i] = make_int2(fbits(o.tm), (o.gh + 1) | (walk ? 0x10000 : 0));
-    if (COMPACT && A.tile_kcounts && alive)
-      atomicAdd(&s_khist[trace_class(S, mk3(o.q0.x, o.q0.y, o.q0.z), mk3(o.q1.x, o.q1.y, o.q1.z))], 1);
-  }
-  if (COMPACT && A.tile_kcounts) {
-    __syncthreads();
-    if (threadIdx.x < TRACE_KEYS) A.tile_kcounts[threadIdx.x * A.ntiles + tile] = s_khist[threadIdx.x];
-  }
-  if (SORT) {
-    if (alive) atomicAdd(&s_hist[key], 1);
-    __syncthreads();
-    for (int k = threadIdx.x; k < A.nkeys; k += TILE) A.tile_counts[k * A.ntiles + tile] = s_hist[k];
-  } else {
-    const int c = __syncthreads_count(alive);
-    if (threadIdx.x == 0) A.tile_counts[tile] = c;
-  }
-  if (COMPACT && A.prep_on) {
-    const int cw = __syncthreads_count(walk);
-    if (threadIdx.x == 0) A.tile_ccounts[tile] = cw;
-    if (A.count_aabb) count_prep(A, tested, walk);
-  }
-}
-
-// Single-pass shading + stable stream compaction (the usual case: compaction on, no material sort).
-// Tiles take tickets in arrival order, publish their survivor / walker counts and find their offsets by a
-// decoupled look-back over the earlier tiles' records (lb: flag << 62 | survivors << 31 | walkers; flag 1 =
-// this tile's counts, 2 = inclusive prefix), then write the survivors straight into the other path buffer in
-// the order the scan + scatter would give, with the next bounce's hand-off records.  A tile writes only
-// after every earlier tile has published, i.e. has read its inputs, and its own slots are >= the ones it
-// writes, so the hit records can be compacted in place.
-struct FuseArgs {
-  PathBuf dst;
-  int* tickets;               // [cap] tile tickets per bounce
-  unsigned long long* lb;     // [cap][ntiles] look-back records
-  int* counts;                // [cap + 2] live paths per bounce
-  int* ccount;                // [cap] candidates per bounce
-  float4* cray;
-  int2* hits;
-  int* cand;
-};
-
-__device__ inline unsigned long long lb_load(const unsigned long long* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ inline void lb_store(unsigned long long* p, unsigned long long v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ inline unsigned long long lb_pack(unsigned long long flag, unsigned s, unsigned w) {
-  return (flag << 62) | ((unsigned long long)s << 31) | (unsigned long long)w;
-}
-
-constexpr int STAGE_MATS = 32;
-#ifdef KDPT_SHADE_PROF  // tools/build_variant.sh experiments only: shading phase times (s_memrealtime ticks)
-__device__ unsigned long long g_shade_prof[8];
-#endif
-#ifndef KDPT_SHADE_TB
-#define KDPT_SHADE_TB 256  // tools/build_variant.sh experiments only
-#endif
-#ifndef KDPT_SHADE_WAVES
-#define KDPT_SHADE_WAVES 6  // fused shading: waves per SIMD it is compiled for (caps its VGPRs at 80)
-#endif
-constexpr int SHADE_TB = KDPT_SHADE_TB;  // paths per fused-shading workgroup (one tile ticket each)
-
-// The LDS a shading workgroup uses: staged geoms/materials and the per-tile compaction scratch.
-template <bool STAGE, int TB = TILE>
-struct ShadeLDS {
-  int tile, b;
-  unsigned cnt[2][TB / 64];
-  unsigned ex[2];
-  uint32_t geoms[STAGE ? ORDERED_GEOMS * sizeof(DevGeom) / 4 : 1];
-  uint32_t mats[STAGE ? STAGE_MATS * sizeof(DevMaterial) / 4 : 1];
-};
-
-// what a fused-shading workgroup needs beside a resident intersect workgroup (the LDS16S route leaves it free)
-constexpr size_t SHADE_LDS_RESERVE = sizeof(ShadeLDS<true, SHADE_TB>);
-
-// STAGE: the analytic geoms and the materials copied into LDS (small scenes: their per-lane reads, indexed
-// by hit and by nearest-first order, are then LDS reads instead of L2 round trips)
-// (SYNC false: the caller's next __syncthreads publishes the copy -- k_shade_fused overlaps it with the
-// tile ticket's atomic round trip)
-template <bool STAGE, int TB, bool SYNC = true>
-__device__ __attribute__((always_inline)) inline DevScene stage_scene(const DevScene& S0, ShadeLDS<STAGE, TB>& L) {
-  static_assert(sizeof(DevGeom) % 4 == 0 && sizeof(DevMaterial) % 4 == 0, "staged as dwords");
-  DevScene S = S0;
-  if (STAGE) {
-    const int gw = S0.num_geoms * (int)(sizeof(DevGeom) / 4), mw = S0.num_materials * (int)(sizeof(DevMaterial) / 4);
-    for (int k = threadIdx.x; k < gw; k += TB) L.geoms[k] = reinterpret_cast<const uint32_t*>(S0.geoms)[k];
-    for (int k = threadIdx.x; k < mw; k += TB) L.mats[k] = reinterpret_cast<const uint32_t*>(S0.materials)[k];
-    if (SYNC) __syncthreads();
-    S.geoms = reinterpret_cast<const DevGeom*>(L.geoms);
-    S.materials = reinterpret_cast<const DevMaterial*>(L.mats);
-  }
-  return S;
-}
-
-// shade()'s outcome for path i ahead of the shading: bounces left after this bounce != 0.  A listed hit
-// has t > 0 (the traversal and k_geoms/prep_ray keep only t > 0, and shade_one recomputes the same t), so
-// the path survives iff it has bounces left, hit something, the hit material does not emit, and one bounce
-// remains after this one.
-__device__ __attribute__((always_inline)) inline bool survives(const DevScene& S, int bounces, int2 hr) {
-  if (bounces <= 0) return bounces != 0;
-  if (hr.x == -1) return false;
-  const int mid = hr.x < -1 ? hr.y : S.geoms[hr.x].materialid;
-  return !(S.materials[mid].emittance > 0.0f) && bounces - 1 != 0;
-}
-
-// One 256-path tile of one iteration: shading, the survivors' stable compaction into the other path buffer
-// (decoupled look-back over the earlier tiles' records), the next bounce's intersect-stage hand-off.  Tiles
-// of an iteration must be started in increasing order (tickets), so every earlier tile is already running.
-template <bool HYBRID, bool STAGE, int TB>
-__device__ __attribute__((always_inline)) inline void shade_tile(const ShadeArgs& A, const FuseArgs& F, const DevScene& S, int tile, int n,
-                                  ShadeLDS<STAGE, TB>& L, unsigned long long t_wg = 0ull) {
-  const int i = tile * TB + threadIdx.x;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#ifdef KDPT_SHADE_PROF
-  const unsigned long long pt0 = __builtin_amdgcn_s_memrealtime();
-#endif
-  if (i == 0) shade_stats(A, n);
-  unsigned long long* lb = F.lb + (size_t)A.depth * A.ntiles;
-  // (1) Which paths survive this bounce follows from the hit record and the hit material alone, so the
-  // tile's survivor count is published (look-back aggregate) before the shading: later tiles' look-backs
-  // then wait on this tile's two loads, not on its whole shading (measured: the look-back wait had grown
-  // as long as the shading itself, the slowest of 64 predecessors' shading each time).
-  // the hit record is read once, here: once this tile's aggregate is out, later tiles may finish their
-  // look-back and write the next bounce's records (F.hits == A.hits) into this tile's index range
-  ShadeIn in;
-  in.hr = make_int2(-1, -1);
-  if (i < n) shade_load<true>(A, S, i, in);
-  const bool pred = i < n && survives(S, fbits(in.q2.w), in.hr);
-  const unsigned long long ms = __ballot(pred);
-#ifdef KDPT_SHADE_PROF
-  const unsigned long long pa = __builtin_amdgcn_s_memrealtime();
-#endif
-  if (lane == 0) L.cnt[0][wid] = (unsigned)__popcll(ms);
-  __syncthreads();
-#ifdef KDPT_SHADE_PROF
-  const unsigned long long pb = __builtin_amdgcn_s_memrealtime();
-#endif
-  if (wid == 0) {
-    unsigned aS = 0;
-    for (int w = 0; w < TB / 64; w++) aS += L.cnt[0][w];
-    if (lane == 0) lb_store(lb + tile, lb_pack(tile == 0 ? 2 : 1, aS, 0));
-  }
-  // (2) the shading
-  ShadeOut o;
-  o.alive = o.walk = o.tested = false;
-  if (i < n) shade_one<HYBRID, true>(A, S, i, in, o);
-  if (o.alive != pred) atomicOr(S.fault, 32);  // unreachable: survives() restates shade()'s outcome
-  const unsigned long long mw = __ballot(o.walk);
-  if (A.count_aabb && A.prep_on) count_prep(A, o.tested, o.walk);
-  if (lane == 0) L.cnt[1][wid] = (unsigned)__popcll(mw);
-  __syncthreads();
-#ifdef KDPT_SHADE_PROF
-  const unsigned long long pt1 = __builtin_amdgcn_s_memrealtime();
-#endif
-  // (3) the survivors' exclusive prefix (look-back), the walkers' place in the next bounce's candidate
-  // list (one counter add per tile: the list's order only decides which lane traces which ray)
-  if (wid == 0) {
-    unsigned aS = 0, aW = 0;
-    for (int w = 0; w < TB / 64; w++) {
-      aS += L.cnt[0][w];
-      aW += L.cnt[1][w];
-    }
-    unsigned eS = 0;
-    if (tile != 0) {
-      for (int base = tile - 1;; base -= 64) {
-        const int j = base - lane;
-        unsigned long long v = j >= 0 ? lb_load(lb + j) : lb_pack(2, 0, 0);
-        while (__ballot((v >> 62) == 0)) {
-          __builtin_amdgcn_s_sleep(1);
-          if ((v >> 62) == 0) v = lb_load(lb + j);
-        }
-        const unsigned long long pre = __ballot((v >> 62) == 2);
-        const int upto = pre ? __ffsll((long long)pre) - 1 : 63;  // nearest inclusive prefix, and the counts before it
-        unsigned sm = lane <= upto ? (unsigned)(v >> 31) & 0x7fffffffu : 0u;
-        for (int off = 32; off > 0; off >>= 1) sm += __shfl_xor(sm, off);
-        eS += sm;
-        if (pre) break;
-      }
-      if (lane == 0) lb_store(lb + tile, lb_pack(2, eS + aS, 0));
-    }
-    if (lane == 0) {
-      L.ex[0] = eS;
-      L.ex[1] = (A.prep_on && aW) ? (unsigned)atomicAdd(&F.ccount[A.depth + 1], (int)aW) : 0u;
-      if (tile == (n - 1) / TB) F.counts[A.depth + 1] = (int)(eS + aS);  // the last tile: the next bounce's paths
-    }
-  }
-  __syncthreads();
-#ifdef KDPT_SHADE_PROF
-  const unsigned long long pt2 = __builtin_amdgcn_s_memrealtime();
-#endif
-  if (o.alive) {
-    unsigned bS = L.ex[0], bW = L.ex[1];
-    for (int w = 0; w < wid; w++) {
-      bS += L.cnt[0][w];
-      bW += L.cnt[1][w];
-    }
-    const int d = (int)(bS + lane_prefix(ms));
-    F.dst.p0[d] = o.q0;
-    F.dst.p1[d] = o.q1;
-    F.dst.p2[d] = o.q2;
-    F.dst.pm[d] = o.pm;
-    if (A.prep_on) {
-      if (o.walk) {
-        const int slot = (int)(bW + lane_prefix(mw));
-        F.cand[slot] = d;
-        F.cray[2 * slot] = make_float4(o.q0.x, o.q0.y, o.q0.z, o.tm);
-        F.cray[2 * slot + 1] = make_float4(o.q1.x, o.q1.y, o.q1.z, ibits(o.gh));
-      } else {
-        F.hits[d] = make_int2(o.gh, -1);  // final: the analytic geoms' hit (code -1: none)
-      }
-    }
-  }
-#ifdef KDPT_SHADE_PROF
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned long long pt3 = __builtin_amdgcn_s_memrealtime();
-    atomicAdd(&g_shade_prof[0], pt1 - pt0);
-    atomicAdd(&g_shade_prof[1], pt2 - pt1);
-    atomicAdd(&g_shade_prof[2], pt3 - pt2);
-    atomicAdd(&g_shade_prof[3], 1ull);
-    atomicAdd(&g_shade_prof[4], (unsigned long long)min(TB, n - tile * TB));
-    atomicAdd(&g_shade_prof[5], pt0 - t_wg);  // ticket + staging
-    atomicAdd(&g_shade_prof[6], pa - pt0);    // the path / hit-record loads (thread 0's wave)
-    atomicAdd(&g_shade_prof[7], pb - pa);     // the publication barrier (the tile's slowest wave)
-  }
-#endif
-}
-
-// One launch per bounce and iteration: tile = ticket (tickets start the tiles in order).
-template <bool HYBRID, bool STAGE>
-__device__ __attribute__((always_inline)) inline void shade_fused_body(const ShadeArgs& A, const FuseArgs& F) {
-  const int n = A.counts[A.depth];
-  // the grid covers every pixel, so past the first bounces most workgroups have no tile: exactly the first
-  // ceil(n / SHADE_TB) take tickets (one contended atomic per tile, not per workgroup), the rest leave at once
-  if ((int)blockIdx.x * SHADE_TB >= n) return;
-#ifdef KDPT_SHADE_PROF
-  const unsigned long long t_wg = __builtin_amdgcn_s_memrealtime();
-#else
-  const unsigned long long t_wg = 0ull;
-#endif
-  __shared__ ShadeLDS<STAGE, SHADE_TB> L;
-  // the ticket's device-scope atomic and the staging copy are in flight together; one barrier for both
-  if (threadIdx.x == 0) L.tile = atomicAdd(&F.tickets[A.depth], 1);
-  const DevScene S = stage_scene<STAGE, SHADE_TB, false>(A.S, L);
-  __syncthreads();
-  const int tile = L.tile;
-  shade_tile<HYBRID, STAGE, SHADE_TB>(A, F, S, tile, n, L, t_wg);
-}
-
-template <bool HYBRID, bool STAGE>
-__global__ __launch_bounds__(SHADE_TB) __attribute__((amdgpu_waves_per_eu(KDPT_SHADE_WAVES))) void k_shade_fused(ShadeArgs A, FuseArgs F) {
-  shade_fused_body<HYBRID, STAGE>(A, F);
-}
-
-// The same for every fused iteration of a batch in one launch (blockIdx.y = iteration): the batch's
-// shading no longer runs iteration after iteration on its stream.
-struct ShadeBatch {
-  ShadeArgs a[MAXB];
-  FuseArgs f[MAXB];
-};
-template <bool HYBRID, bool STAGE>
-__global__ __launch_bounds__(SHADE_TB) __attribute__((amdgpu_waves_per_eu(KDPT_SHADE_WAVES))) void k_shade_fused_b(ShadeBatch B) {
-  shade_fused_body<HYBRID, STAGE>(B.a[blockIdx.y], B.f[blockIdx.y]);
-}
-
-// Exclusive scan of the tile counts (one workgroup; <= MAX_KEYS * ntiles entries).
-// One workgroup per scan job: job 0 = the survivors (or, when sorting, the per-material histogram),
-// job 1 = the walking survivors of the intersect-stage hand-off (launched only when it runs).
-struct ScanJob {
-  const int* tile_counts;
-  int* tile_off;
-  int nkeys;
-  int* total_out;
-};
-// 256 threads: every kernel a batch launches fits beside a resident intersect workgroup (4 waves x 96 VGPRs per
-// SIMD, 150 KB of LDS per CU), which a 1024-thread workgroup never does
-constexpr int SCAN_TB = 256;
-__global__ __launch_bounds__(SCAN_TB) void k_scan(ScanJob j0, ScanJob j1, const int* counts, int depth,
-                                                  int ntiles_alloc) {
-  const ScanJob& J = blockIdx.x == 0 ? j0 : j1;
-  const int* __restrict__ tile_counts = J.tile_counts;
-  int* __restrict__ tile_off = J.tile_off;
-  const int nkeys = J.nkeys;
-  int* total_out = J.total_out;
-  const int n = counts[depth];
-  const int ntiles = (n + TILE - 1) / TILE;
-  const int total_entries = nkeys * ntiles;
-  __shared__ int s_wave[SCAN_TB / 64];
-  __shared__ int s_carry;
-  if (threadIdx.x == 0) s_carry = 0;
-  __syncthreads();
-  for (int base = 0; base < total_entries; base += SCAN_TB) {
-    const int e = base + threadIdx.x;
-    int v = 0;
-    int k = 0, t = 0;
-    if (e < total_entries) {
-      k = e / ntiles;
-      t = e - k * ntiles;
-      v = tile_counts[k * ntiles_alloc + t];
-    }
-    // inclusive wave scan
-    int x = v;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    for (int off = 1; off < 64; off <<= 1) {
-      int y = __shfl_up(x, off);
-      if (lane >= off) x += y;
-    }
-    if (lane == 63) s_wave[wid] = x;
-    __syncthreads();
-    if (wid == 0) {
-      int w = lane < SCAN_TB / 64 ? s_wave[lane] : 0;
-      for (int off = 1; off < SCAN_TB / 64; off <<= 1) {
-        int y = __shfl_up(w, off);
-        if (lane >= off) w += y;
-      }
-      if (lane < SCAN_TB / 64) s_wave[lane] = w;
-    }
-    __syncthreads();
-    const int carry = s_carry;
-    const int excl = carry + (wid > 0 ? s_wave[wid - 1] : 0) + x - v;
-    if (e < total_entries) tile_off[k * ntiles_alloc + t] = excl;
-    __syncthreads();
-    if (threadIdx.x == SCAN_TB - 1) s_carry = excl + v;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && total_out) *total_out = s_carry;
-}
-
-// Stable compaction (and, on iter 2, the stable sort by materialIdHit).
-// The next bounce's intersect-stage hand-off, moved with the survivors by k_scatter: walking rays get their
-// geoms record at the new slot and a candidate-list entry (stable: tile order, offsets from k_scan), the
-// others their final hit record.
-struct ScatterPrep {
-  int on;
-  const int2* prep;
-  float4* cray;
-  int2* hits;
-  int* cand;
-  const int* tile_coff;
-};
-
-template <bool SORT>
-__global__ __launch_bounds__(TILE) void k_scatter(PathBuf src, PathBuf dst, const int* __restrict__ tile_off,
-                                                  const int* counts, int depth, int ntiles_alloc, int compact,
-                                                  ScatterPrep P) {
-  const int n = counts[depth];
-  const int tile = blockIdx.x;
-  if (tile * TILE >= n) return;
-  const int i = tile * TILE + threadIdx.x;
-  const bool valid = i < n;
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  float4 q0, q1, q2;
-  int pm = 0;
-  bool alive = false;
-  if (valid) {
-    q0 = src.p0[i];
-    q1 = src.p1[i];
-    q2 = src.p2[i];
-    pm = src.pm[i];
-    alive = compact ? (fbits(q2.w) != 0) : true;
-  }
-  int dst_i;
-  if (!SORT) {
-    __shared__ int s_wave[TILE / 64];
-    const unsigned long long m = __ballot(alive);
-    if (lane == 0) s_wave[wid] = __popcll(m);
-    __syncthreads();
-    int before = 0;
-    for (int w = 0; w < wid; w++) before += s_wave[w];
-    dst_i = tile_off[tile] + before + (int)lane_prefix(m);
-  } else {
-    __shared__ int s_key[TILE];
-    s_key[threadIdx.x] = alive ? pm : -0x7fffffff;
-    __syncthreads();
-    int r = 0;
-    for (int j = 0; j < (int)threadIdx.x; j++) r += (s_key[j] == pm);
-    dst_i = tile_off[pm * ntiles_alloc + tile] + r;
-  }
-  if (alive) {
-    dst.p0[dst_i] = q0;
-    dst.p1[dst_i] = q1;
-    dst.p2[dst_i] = q2;
-    dst.pm[dst_i] = pm;
-  }
-  if (P.on) {
-    __shared__ int s_walk[TILE / 64];
-    const int2 pr = alive ? P.prep[i] : make_int2(0, 0);
-    const bool w = alive && (pr.y & 0x10000);
-    const int geom = (pr.y & 0xffff) - 1;
-    const unsigned long long m = __ballot(w);
-    if (lane == 0) s_walk[wid] = __popcll(m);
-    __syncthreads();
-    if (alive) {
-      if (w) {
-        int before = 0;
-        for (int k = 0; k < wid; k++) before += s_walk[k];
-        const int slot = P.tile_coff[tile] + before + (int)lane_prefix(m);
-        P.cand[slot] = dst_i;
-        P.cray[2 * slot] = make_float4(q0.x, q0.y, q0.z, u2f((uint32_t)pr.x));
-        P.cray[2 * slot + 1] = make_float4(q1.x, q1.y, q1.z, ibits(geom));
-      } else {
-        P.hits[dst_i] = make_int2(geom, -1);  // final: the analytic geoms' hit (code -1: none)
-      }
-    }
-  }
-}
-
-// finalGather (src/pathtrace.cu:2373-2383), including index = paths[index].pixelIndex
-__global__ void k_final_gather(PathBuf paths, const int* counts, int depth, float* image) {
-  const int n = counts[depth];
-  const int index = blockIdx.x * blockDim.x + threadIdx.x;
-  if (index >= n) return;
-  const int j = fbits(paths.p1[index].w) & 0x7fffffff;
-  const float4 c = paths.p2[j];
-  const int pix = fbits(paths.p1[j].w) & 0x7fffffff;
-  image[3 * (size_t)pix + 0] += c.x;
-  image[3 * (size_t)pix + 1] += c.y;
-  image[3 * (size_t)pix + 2] += c.z;
-}
-
-// sendImageToPBO (src/pathtrace.cu:69-89)
-__global__ void k_pbo(const float* image, int npix, int iter, uchar4* pbo) {
-  const int index = blockIdx.x * blockDim.x + threadIdx.x;
-  if (index >= npix) return;
-  int c[3];
-  for (int k = 0; k < 3; k++) {
-    int v = (int)((double)(image[3 * (size_t)index + k] / iter) * 255.0);
-    c[k] = v < 0 ? 0 : (v > 255 ? 255 : v);
-  }
-  pbo[index] = make_uchar4((unsigned char)c[0], (unsigned char)c[1], (unsigned char)c[2], 0);
-}
-
-// saveImage (src/main.cpp:1087-1108): x-flip and divide by the sample count, then image::savePNG's
-// bytes (src/image.cpp:22-35): glm::clamp(pix, 0, 1) * 255.f truncated to unsigned char.  `lin`
-// (optional) receives the flipped, divided float image that image::saveHDR writes.
-__global__ void k_save_image(const float* __restrict__ image, int W, int H, float samples, uint8_t* __restrict__ rgb,
-                             float* __restrict__ lin) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= W * H) return;
-  const int y = i / W, X = i - y * W;
-  const size_t src = 3 * ((size_t)(W - 1 - X) + (size_t)y * W);
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const float v = image[src + k] / samples;
-    if (lin) lin[3 * (size_t)i + k] = v;
-    const float cl = glm_min(glm_max(v, 0.0f), 1.0f) * 255.f;
-    rgb[3 * (size_t)i + k] = (uint8_t)cl;
-  }
-}
-
-// debug: unpack the live path array into the reference PathSegment layout
-__global__ void k_unpack(PathBuf src, const int* counts, int depth, kdpt_path_segment* out) {
-  const int n = counts[depth];
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float4 q0 = src.p0[i], q1 = src.p1[i], q2 = src.p2[i];
-  kdpt_path_segment s;
-  s.origin[0] = q0.x; s.origin[1] = q0.y; s.origin[2] = q0.z;
-  s.direction[0] = q1.x; s.direction[1] = q1.y; s.direction[2] = q1.z;
-  const int pw = fbits(q1.w);
-  s.isinside = (uint8_t)((pw >> 31) & 1);
-  s.pad_[0] = s.pad_[1] = s.pad_[2] = 0;
-  s.sdepth = q0.w;
-  s.color[0] = q2.x; s.color[1] = q2.y; s.color[2] = q2.z;
-  s.pixelIndex = pw & 0x7fffffff;
-  s.remainingBounces = fbits(q2.w);
-  s.materialIdHit = src.pm[i];
-  out[i] = s;
-}
-
-// ---------------------------------------------------------------------------
-// Ray queries (kdpt_cast_rays): caller-supplied rays through the intersect stage of the path tracer, one
-// chunk at a time -- k_cast_prep (validation + the stage's first part, geoms_core), k_trace (unchanged, a batch
-// of one "iteration" at depth 0 over the query's own queue) and k_cast_resolve (the hit code turned into a
-// kdpt_ray_hit with the calls shade_one makes).  No PathSegment, iteration number or image is involved.
-// ---------------------------------------------------------------------------
-struct CastArgs {
-  DevScene S;
-  const float* o;  // the chunk's origins and directions (3 n floats each), device memory
-  const float* d;
-  int n;
-  int normalize;   // KDPT_CAST_NORMALIZE
-  float4* cray;    // the query's own candidate queue and hit records (one chunk)
-  int2* hits;
-  int* cand;
-  int* cnt;        // [0] k_trace's work counter, [1] the chunk's candidate count
-  unsigned long long* tt;  // [0..1] k_trace's launch record (TraceArgs::trace_t), [2] candidates summed over the call
-  kdpt_ray_hit* out;
-};
-constexpr int CAST_REJECTED = (int)0x80000000;  // hits[i].y of a rejected ray (objMaterialIdx never takes it)
-
-// The chunk's ray i as it is traced: false = rejected (a non-finite component, a zero direction or one whose
-// normalisation is not finite, or a direction that is not unit length: |dot(d, d) - 1| > 1e-6 in float).
-__device__ __attribute__((always_inline)) inline bool cast_load(const CastArgs& A, int i, f3& o, f3& d) {
-  o = mk3(A.o[3 * (size_t)i], A.o[3 * (size_t)i + 1], A.o[3 * (size_t)i + 2]);
-  d = mk3(A.d[3 * (size_t)i], A.d[3 * (size_t)i + 1], A.d[3 * (size_t)i + 2]);
-  bool ok = fabsf(o.x) < FLT_INFV && fabsf(o.y) < FLT_INFV && fabsf(o.z) < FLT_INFV && fabsf(d.x) < FLT_INFV &&
-            fabsf(d.y) < FLT_INFV && fabsf(d.z) < FLT_INFV;
-  if (A.normalize) d = normalize(d);  // glm::normalize, as the camera and the scatter form their directions
-  ok = ok && fabsf(d.x) < FLT_INFV && fabsf(d.y) < FLT_INFV && fabsf(d.z) < FLT_INFV;
-  return ok && fabsf(dot(d, d) - 1.0f) <= 1e-6f;
-}
-
-// One lane per ray of the chunk; zeroes the work counter and the launch record of the k_trace that follows
-// (as gen_rays_body does for an iteration).  The candidate count is zero on entry: k_cast_resolve of the
-// previous chunk (or the call's fill on the context's stream) left it so.
-__global__ __launch_bounds__(GEN_BLOCK) void k_cast_prep(CastArgs A) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0) {
-    A.cnt[0] = 0;
-    A.tt[0] = ~0ull;
-    A.tt[1] = 0ull;
-  }
-  f3 o = mk3(0, 0, 0), d = mk3(0, 0, 1);
-  bool live = false;
-  if (i < A.n) {
-    live = cast_load(A, i, o, d);
-    if (!live) A.hits[i] = make_int2(-1, CAST_REJECTED);
-  }
-  geoms_core<GEN_BLOCK>(A.S, live, i, o, d, A.cray, A.hits, A.cand, A.cnt + 1, nullptr);
-}
-
-// (code, objMaterialIdx) + the ray -> kdpt_ray_hit: t, point and normal recomputed exactly as shade_one
-// recomputes them for scatterRay.  A triangle's code indexes tv0 / tn0, the TriBare order of scene->tris (the
-// clustered routes carry that index in e1.w).
-template <bool HYBRID>
-__global__ __launch_bounds__(256) void k_cast_resolve(CastArgs A) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i == 0) {  // k_trace is done with the chunk's candidate count: add it up, and zero it for the next chunk
-    A.tt[2] += (unsigned long long)A.cnt[1];
-    A.cnt[1] = 0;
-  }
-  if (i >= A.n) return;
-  const DevScene& S = A.S;
-  const int2 hr = A.hits[i];
-  f3 o, d;
-  (void)cast_load(A, i, o, d);
-  float t = -1.0f;
-  int kind = hr.y == CAST_REJECTED ? KDPT_HIT_INVALID : KDPT_HIT_NONE, prim = -1, mid = -1;
-  f3 ip = mk3(0, 0, 0), nrm = mk3(0, 0, 0);
-  if (hr.x < -1) {  // triangle: the traversal's final recomputation, repeated
-    const int k = -hr.x - 2;
-    float bx, by, bzk;
-    tri_test_v(TriData{S.tv0[k], S.te1[k], S.te2[k]}, o, d, bx, by, bzk);
-    t = tri_hit_t_n<HYBRID>(S.tn0[k], S.tn1[k], S.tn2[k], o, d, bx, by, bzk, ip, nrm);
-    kind = KDPT_HIT_TRIANGLE;
-    prim = k;
-    mid = hr.y;
-  } else if (hr.x >= 0) {
-    const DevGeom& G = S.geoms[hr.x];
-    Ray ray;
-    ray.origin = o;
-    ray.direction = d;
-    ray.isinside = false;
-    ray.sdepth = 0.0f;
-    t = G.type == 1 ? boxIntersectionTest(G, ray, ip, nrm) : sphereIntersectionTest(G, ray, ip, nrm);
-    kind = KDPT_HIT_GEOM;
-    prim = hr.x;
-    mid = G.materialid;
-  }
-  kdpt_ray_hit r;
-  r.t = t;
-  r.kind = kind;
-  r.prim = prim;
-  r.material = mid;
-  r.point[0] = ip.x; r.point[1] = ip.y; r.point[2] = ip.z;
-  r.normal[0] = nrm.x; r.normal[1] = nrm.y; r.normal[2] = nrm.z;
-  A.out[i] = r;
-}
-
-__global__ void k_selftest_math(const float* x, int n, float* so, float* co) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) { so[i] = kdpt_sinf(x[i]); co[i] = kdpt_cosf(x[i]); }
-}
-// glibc acosf / sin / cos restatements (kdpt_math.h): fn 0 acosf(x), 1 sin((double)x), 2 cos((double)x)
-__device__ inline uint64_t libm_bits(int fn, float x) {
-  if (fn == 0) return f2u(kdpt_acosf(x));
-  return d2u(fn == 1 ? kdpt_sin((double)x) : kdpt_cos((double)x));
-}
-__device__ inline uint64_t splitmix64(uint64_t z) {
-  z += 0x9e3779b97f4a7c15ull;
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
-__global__ void k_selftest_libm(int fn, const float* x, int n, double* out) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  uint64_t b = libm_bits(fn, x[i]);
-  out[i] = fn == 0 ? (double)u2f((uint32_t)b) : u2d(b);
-}
-__global__ void k_selftest_libm_digest(int fn, uint32_t first, uint64_t count, unsigned long long* acc) {
-  uint64_t sum = 0;
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += stride) {
-    const uint32_t xb = (uint32_t)(first + k);
-    sum += splitmix64(libm_bits(fn, u2f(xb)) ^ splitmix64(xb));
-  }
-  atomicAdd(acc, (unsigned long long)sum);
-}
-__global__ void k_selftest_rng(const int* iid, int n, int k, float* u) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  Rng r = seeded_rng(iid[3 * i], iid[3 * i + 1], iid[3 * i + 2]);
-  float v = 0;
-  for (int j = 0; j <= k; j++) v = u01(r);
-  u[i] = v;
-}
-__global__ void k_selftest_rng_draws(int mode, const uint32_t* in, int n, int k, float* out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  Rng r = mode == 0 ? seeded_rng((int)in[3 * i], (int)in[3 * i + 1], (int)in[3 * i + 2])
-        : mode == 1 ? rng_seed(utilhash(in[i])) : rng_seed(in[i]);
-  for (int j = 0; j < k; j++) out[(size_t)i * k + j] = u01(r);
-}
-__global__ void k_selftest_glm(int fn, const float* in, int n, float* out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  glm_kat(fn, in + (size_t)glm_kat_inputs(fn) * i, out + (size_t)glm_kat_outputs(fn) * i);
-}
-__global__ void k_selftest_fresnel(const float* c, int n, float R0, float* f) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  // getFresnelVal with dot(N,-I) == c[i]: F = R0 + (1-R0) * pow(1 - c, 5)
-  double F = (double)R0 + (double)(1.0f - R0) * pow5((double)(1.0f - c[i]));
-  f[i] = (float)F;
-}
-
 }  // namespace
+
+// The kernels, one header per stage, in the order the code object keeps them.
+#include "kernels_gen.h"
+#include "kernels_trace.h"
+#include "kernels_brute.h"
+#include "kernels_shade.h"
+#include "kernels_image.h"
+#include "kernels_cast.h"
+#include "kernels_selftest.h"
 
 // ---------------------------------------------------------------------------
 // Context
@@ -2226,158 +542,6 @@ int build_masks(kdpt_ctx* c, int n) {
   return KDPT_OK;
 }
 
-// Big leaves as clusters of <= 64 triangles, super-clusters and slabs (kdpt_clusters.h), uploaded.
-int build_clusters(kdpt_ctx* c, const kdpt_scene* sc, const std::vector<float4>& tv, const std::vector<float4>& e1,
-                   const std::vector<float4>& e2, std::vector<int2>& leaf_cl, std::vector<int2>& leaf_sp) {
-  ClusterSet cs;
-  build_cluster_set(sc->nodes, sc->num_nodes, sc->tris, tv, e1, e2, cs);
-  // Meshes of small triangles (a rigorous margin: the two-level cull of the C5 icosphere) group each big leaf's
-  // triangles into normal cones of chord CLUSTER_CHORD_EXACT first, then Morton runs per cone: flatter clusters
-  // whose oriented boxes the lines miss more often -- C5's sweeps per ray 1.83 -> 1.30 (host simulation), C5
-  // 4 568 / 4 377 -> 5 110 / 5 087 Mrays/s (profiles/r06_ab_log.md).  Only the order of a leaf's sweeps changes
-  // (the results fold order-free); such leaves hold more clusters than ceil(size / 64) (S.cl_counts).  Not for meshes of large triangles: dragon_5's leaves split into 4-8x as many
-  // clusters.  Kept only while the super-clusters grow by at most 40 % (they must fit the LDS route); knob
-  // "cluster_chord" (process default): 0 = Morton runs only, > 0 = that chord for every mesh.
-  {
-    const double chord = g_cluster_chord >= 0 ? g_cluster_chord
-                                             : (cluster_margin(cs.cv0, cs.ce1, cs.ce2).exact ? CLUSTER_CHORD_EXACT : 0.0);
-    if (chord > 0 && !cs.info.empty()) {
-      ClusterGrouping g;
-      g.mode = 1;
-      g.chord = chord;
-      ClusterSet cones;
-      build_cluster_set(sc->nodes, sc->num_nodes, sc->tris, tv, e1, e2, cones, g);
-      if (g_cluster_chord > 0 || cones.sup.size() * 10 <= cs.sup.size() * 14) cs = std::move(cones);
-    }
-  }
-  leaf_cl = cs.leaf_cl;
-  leaf_sp = cs.leaf_sp;
-  const std::vector<int4>& sp = cs.sup;
-  const std::vector<float4>&lo = cs.lo, &hi = cs.hi, &nrm = cs.nrm, &cv0 = cs.cv0, &ce1 = cs.ce1, &ce2 = cs.ce2;
-  const std::vector<int2>& info = cs.info;
-  int2 *dl, *di;
-  float4 *dlo, *dhi, *dv0, *de1, *de2;
-  int rc;
-  if ((rc = dupload(c, &dl, leaf_cl.data(), leaf_cl.size())) || (rc = dupload(c, &di, info.data(), info.size())) ||
-      (rc = dupload(c, &dlo, lo.data(), lo.size())) || (rc = dupload(c, &dhi, hi.data(), hi.size())) ||
-      (rc = dupload(c, &dv0, cv0.data(), cv0.size())) || (rc = dupload(c, &de1, ce1.data(), ce1.size())) ||
-      (rc = dupload(c, &de2, ce2.data(), ce2.size())))
-    return rc;
-  int4* dsp;
-  float4 *dn, *du, *dv, *dw;
-  if ((rc = dupload(c, &dsp, sp.data(), sp.size())) || (rc = dupload(c, &dn, nrm.data(), nrm.size())) ||
-      (rc = dupload(c, &du, cs.obb_u.data(), cs.obb_u.size())) ||
-      (rc = dupload(c, &dv, cs.obb_v.data(), cs.obb_v.size())) ||
-      (rc = dupload(c, &dw, cs.obb_w.data(), cs.obb_w.size())))
-    return rc;
-  c->S.cl_n = dn;
-  c->S.cl_slab = 1;
-  c->S.cl_u = du;
-  c->S.cl_v = dv;
-  c->S.cl_w = dw;
-  c->S.cl_obb = 1;
-  c->S.flat_obb = 1;
-  float4 *dsn, *dsb;
-  if ((rc = dupload(c, &dsn, cs.sup_n.data(), cs.sup_n.size())) || (rc = dupload(c, &dsb, cs.sup_b.data(), cs.sup_b.size())))
-    return rc;
-  c->S.sup_n = dsn;
-  c->S.sup_b = dsb;
-  c->S.sup_slab = 1;
-  set_cull(c, cluster_margin(cv0, ce1, ce2));
-  // no margin makes the cull exact for these triangles: the masked one-level cull (its direction masks for the
-  // fast margin the box levels use)
-  if (!c->cull.exact && !info.empty()) {
-    c->mask_cs.reset(new ClusterSet(cs));
-    if ((rc = build_masks(c, dir_mask_resolution((int)info.size())))) return rc;
-  }
-  c->S.sup = dsp;
-  // a super box past the half range (+-65504) would be infinite, its centre NaN and the cull wrong: such a
-  // scene gets no super-cluster route (TREE_LDS16S needs num_supers > 0)
-  c->S.num_supers = cs.supers_finite ? (int)sp.size() : 0;
-  c->S.leaf_cl = dl;
-  c->S.num_clusters = (int)info.size();
-  c->S.cl_counts = 0;
-  for (int i = 0; i < sc->num_nodes; i++)
-    if (leaf_cl[i].y != 0 && leaf_cl[i].y != (sc->nodes[i].triIdSize + CLUSTER - 1) / CLUSTER) c->S.cl_counts = 1;
-  c->S.cl_info = di;
-  c->S.cl_lo = dlo;
-  c->S.cl_hi = dhi;
-  c->S.c_v0 = dv0;
-  c->S.c_e1 = de1;
-  c->S.c_e2 = de2;
-  return KDPT_OK;
-}
-
-// NodesPacked records (kdpt_device.h); false when the tree does not fit the format.
-bool pack_nodes(const kdpt_node_bare* N, int nn, const std::vector<int2>& leaf_cl, std::vector<int4>& out) {
-  if (nn >= 0xffff) return false;
-  out.assign(2 * (size_t)nn, make_int4(0, 0, 0, 0));
-  auto l16 = [](int v) { return v == -1 ? 0xffffu : (uint32_t)v; };
-  for (int i = 0; i < nn; i++) {
-    const kdpt_node_bare& n = N[i];
-    const bool tris = n.triIdSize > 0;
-    if (tris && (n.leftID != -1 || n.rightID != -1 || n.triIdSize >= (1 << 13))) return false;
-    const uint32_t axis = n.axis == 0 ? 0u : (n.axis == 1 ? 1u : 2u);  // comp(): anything else reads z
-    // a big leaf keeps its first cluster instead of its first triangle (its clusters carry the triangles)
-    const uint32_t first = n.triIdSize >= BIG_LEAF ? (uint32_t)leaf_cl[i].x : (uint32_t)n.triIdStart;
-    const uint32_t w6 = tris ? first : (l16(n.leftID) | (l16(n.rightID) << 16));
-    const uint32_t kids = (n.leftID != -1 ? 1u : 0u) | (n.rightID != -1 ? 2u : 0u);
-    const uint32_t w7 = l16(n.parentID) | (axis << 16) | ((tris ? 1u : 0u) << 18) |
-                        ((tris ? (uint32_t)n.triIdSize : kids) << 19);
-    out[2 * i] = make_int4(fbits(n.mins[0]), fbits(n.mins[1]), fbits(n.mins[2]), fbits(n.maxs[0]));
-    out[2 * i + 1] = make_int4(fbits(n.maxs[1]), fbits(n.maxs[2]), (int)w6, (int)w7);
-  }
-  return true;
-}
-
-// NodesDerived records (kdpt_device.h); false unless every node's box is its parent's with exactly the one
-// coordinate the reference's split replaces (checked bit for bit), both children write the same centre, and
-// the tree fits the 16-bit links.
-bool pack_nodes16(const kdpt_node_bare* N, int nn, const std::vector<int2>& leaf_cl, std::vector<int4>& out) {
-  if (nn < 1 || nn >= 0xffff || N[0].parentID != -1) return false;
-  out.assign((size_t)nn, make_int4(0, 0, 0, 0));
-  auto l16 = [](int v) { return v == -1 ? 0xffffu : (uint32_t)v; };
-  auto same = [](float a, float b) { return fbits(a) == fbits(b); };
-  for (int i = 0; i < nn; i++) {
-    const kdpt_node_bare& n = N[i];
-    const bool tris = n.triIdSize > 0;
-    if (tris && (n.leftID != -1 || n.rightID != -1)) return false;
-    if (n.axis < 0 || n.axis > 2) return false;
-    for (int ch : {n.leftID, n.rightID})
-      if (ch != -1 && (ch <= 0 || ch >= nn || N[ch].parentID != i)) return false;
-    uint32_t kc = 7u;
-    float restore = 0.0f;
-    if (i > 0) {
-      const int p = n.parentID;
-      if (p < 0 || p >= nn) return false;
-      const kdpt_node_bare& P = N[p];
-      const bool isL = P.leftID == i, isR = P.rightID == i;
-      if (isL == isR) return false;
-      const int a = P.axis;
-      for (int k = 0; k < 3; k++) {
-        if (!(k == a && isR) && !same(n.mins[k], P.mins[k])) return false;
-        if (!(k == a && isL) && !same(n.maxs[k], P.maxs[k])) return false;
-      }
-      kc = isR ? (uint32_t)a : 3u + (uint32_t)a;
-      restore = isR ? P.mins[a] : P.maxs[a];
-    }
-    float center = 0.0f;
-    if (n.leftID != -1) center = N[n.leftID].maxs[n.axis];
-    if (n.rightID != -1) {
-      if (n.leftID != -1 && !same(center, N[n.rightID].mins[n.axis])) return false;
-      center = N[n.rightID].mins[n.axis];
-    }
-    const uint32_t first = n.triIdSize >= BIG_LEAF ? (uint32_t)leaf_cl[i].x : (uint32_t)n.triIdStart;
-    const uint32_t w1 = tris ? first : fbits(center);
-    const uint32_t w2 = tris ? (uint32_t)n.triIdSize : (l16(n.leftID) | (l16(n.rightID) << 16));
-    const uint32_t kids = (n.leftID != -1 ? 1u : 0u) | (n.rightID != -1 ? 2u : 0u);
-    const uint32_t w3 = l16(n.parentID) | ((uint32_t)n.axis << 16) | ((tris ? 1u : 0u) << 18) |
-                        ((tris ? 0u : kids) << 19) | (kc << 21);
-    out[i] = make_int4(fbits(restore), (int)w1, (int)w2, (int)w3);
-  }
-  return true;
-}
-
 template <bool HYBRID, bool COUNT, int MODE>
 int trace_occupancy(kdpt_ctx* c, size_t lds, int* blocks) {
   if (lds > 0)
@@ -2525,24 +689,7 @@ extern "C" int kdpt_debug_shade_prof(unsigned long long* out) {  // sums, then z
 #endif
 extern "C" {
 
-void kdpt_default_options(kdpt_options* o) {
-  memset(o, 0, sizeof *o);
-  o->focal_length = 6.0f;
-  o->dof_angle = 0.0f;
-  o->softness = 0.0f;
-  o->cacherays = 0;
-  o->antialias = 1;
-  o->enable_sss = 0;
-  o->testing_mode = 0;
-  o->compaction = 1;
-  o->enable_kd = 1;
-  o->viz_kd = 0;
-  o->use_bbox = 0;
-  o->short_stack = 1;
-  o->bounce_cap = 8;
-  o->block_size = 0;
-  o->external_image = nullptr;
-}
+void kdpt_default_options(kdpt_options* o) { default_options(o); }
 
 const char* kdpt_last_error(void) { return g_last_error.c_str(); }
 
@@ -2550,80 +697,23 @@ int kdpt_create(const kdpt_scene* sc, const kdpt_options* opt, int device, kdpt_
   const auto t_create = std::chrono::steady_clock::now();
   if (!sc || !out) return fail(KDPT_ERR_ARG, "null scene/out");
   *out = nullptr;
-  kdpt_options o;
-  if (opt) o = *opt; else kdpt_default_options(&o);
-  if (o.bounce_cap <= 0) o.bounce_cap = 8;
-  if (o.bounce_cap > 30) return fail(KDPT_ERR_ARG, "bounce_cap > 30");
-  if (o.block_size && o.block_size != TILE) return fail(KDPT_ERR_UNSUPPORTED, "block_size must be 0 or 256");
-  const int W = sc->camera.resolution[0], H = sc->camera.resolution[1];
-  if (W <= 0 || H <= 0 || (long long)W * H >= (1ll << 30)) return fail(KDPT_ERR_ARG, "bad resolution");
-  if (sc->num_materials > MAX_KEYS) return fail(KDPT_ERR_UNSUPPORTED, "more than 64 materials");
-  // The compact visited-state traversal needs the reference builder's shape:
-  // nodes[i].ID == i, root == node 0, node 1 == root's left child, <= 15 levels.
-  std::vector<int> level;
-  const bool brute = !o.enable_kd && sc->has_obj;
-  bool shade_oob = false;  // kdpt_ctx::shade_oob
-  if (brute) {
-    // the arrays pathTraceOneBounce reads (src/pathtrace.cu:485-576) must be in bounds
-    if (sc->num_shapes < 1 || !sc->obj_materialOffsets || !sc->obj_polyoffsets || !sc->obj_polysidxflat ||
-        !sc->obj_verts || !sc->obj_norms)
-      return fail(KDPT_ERR_ARG, "enable_kd=0 needs the OBJ arrays (obj_verts, obj_norms, obj_polysidxflat, ...)");
-    long long total = 0;
-    for (int i = 0; i < sc->num_shapes; i++) {
-      if (sc->obj_polyoffsets[i] < 0 || sc->obj_polyoffsets[i] % 3)
-        return fail(KDPT_ERR_UNSUPPORTED, "OBJ shapes must be triangulated (index counts multiple of 3)");
-      if (sc->obj_materialOffsets[i] < 0 || sc->obj_materialOffsets[i] >= sc->num_materials)
-        return fail(KDPT_ERR_ARG, "obj_materialOffsets out of range");
-      total += sc->obj_polyoffsets[i];
-    }
-    if (total != sc->polyidxcount) return fail(KDPT_ERR_ARG, "obj_polyoffsets do not sum to polyidxcount");
-    for (int j = 0; j < sc->polyidxcount; j++) {
-      const long long v = sc->obj_polysidxflat[j];
-      if (v < 0 || 3 * v + 2 >= sc->num_obj_verts || 3 * v + 2 >= sc->num_obj_norms)
-        return fail(KDPT_ERR_ARG, "OBJ vertex index out of range (vertex or normal array)");
-    }
-    if (o.use_bbox && (!sc->obj_bboxes || sc->num_bbox_floats < sc->num_shapes + 5))
-      return fail(KDPT_ERR_ARG, "use_bbox needs obj_bboxes[num_shapes + 5]");
+  // every argument and scene error is reported here, before any device work (kdpt_scene_prep.h)
+  PreparedScene p;
+  {
+    std::string err;
+    const int prc = prepare_scene(sc, opt, g_cluster_chord, &p, &err);
+    if (prc) return fail(prc, err);
   }
-  if (sc->has_obj && sc->num_nodes > 0 && !brute) {
-    const kdpt_node_bare* N = sc->nodes;
-    int root = -1;
-    for (int i = 0; i < sc->num_nodes; i++)
-      if (N[i].parentID == -1) { root = N[i].ID; break; }
-    if (root != 0) return fail(KDPT_ERR_UNSUPPORTED, "root must be node 0");
-    for (int i = 0; i < sc->num_nodes; i++) {
-      if (N[i].ID != i) return fail(KDPT_ERR_UNSUPPORTED, "nodes must be stored in ID order");
-      for (int ch : {N[i].leftID, N[i].rightID})
-        if (ch != -1 && (ch <= i || ch >= sc->num_nodes || N[ch].parentID != i))
-          return fail(KDPT_ERR_ARG, "inconsistent KD node links");
-      if (N[i].triIdSize > 0 && (N[i].triIdStart < 0 || N[i].triIdStart + N[i].triIdSize > sc->num_tris))
-        return fail(KDPT_ERR_ARG, "triangle range out of bounds");
-      if (N[i].triIdSize > 0 && (N[i].leftID != -1 || N[i].rightID != -1))
-        return fail(KDPT_ERR_UNSUPPORTED, "KD node with both triangles and children");
-    }
-    if (sc->num_nodes > 1 && N[0].leftID != 1) return fail(KDPT_ERR_UNSUPPORTED, "node 1 must be root's left child");
-    level.assign(sc->num_nodes, 0);
-    for (int i = 1; i < sc->num_nodes; i++) {
-      // only the root has no parent (the traversal tests `parentID == -1` as `cur == root`)
-      if (N[i].parentID < 0 || N[i].parentID >= i) return fail(KDPT_ERR_ARG, "inconsistent KD parent links");
-      level[i] = level[N[i].parentID] + 1;
-      if (level[i] > 15) return fail(KDPT_ERR_UNSUPPORTED, "KD tree deeper than 15 levels");
-    }
-    for (int i = 0; i < sc->num_tris; i++) {
-      int m = sc->tris[i].mtlIdx;
-      if (m < 0 || m >= sc->num_shapes) return fail(KDPT_ERR_ARG, "triangle mtlIdx out of range");
-      if (m > 0 && !o.viz_kd) shade_oob = true;
-    }
-  }
+  const kdpt_options& o = p.opt;
   kdpt_ctx* c = new kdpt_ctx();
-  c->shade_oob = shade_oob;
+  c->shade_oob = p.shade_oob;
   c->device = device;
   c->opt = o;
   c->cam = sc->camera;
   c->traceDepth = sc->traceDepth;
-  c->W = W;
-  c->H = H;
-  c->npix = W * H;
+  c->W = sc->camera.resolution[0];
+  c->H = sc->camera.resolution[1];
+  c->npix = c->W * c->H;
   c->ntiles = (c->npix + TILE - 1) / TILE;
   c->cap = o.bounce_cap;
   c->nkeys = std::max(1, sc->num_materials);
@@ -2635,204 +725,91 @@ int kdpt_create(const kdpt_scene* sc, const kdpt_options* opt, int device, kdpt_
   c->cu_mask_streams = g_cu_mask_streams;
   if (create_stream(c, &c->stream) != KDPT_OK) return bail(fail(KDPT_ERR_HIP, "hipStreamCreate failed"));
   int rc;
-  // geoms / materials (viz_kd: the KD node boxes follow the analytic geoms, as boxes with the last material,
-  // src/pathtrace.cu:1813-1831)
-  const bool viz = o.viz_kd && o.enable_kd && sc->has_obj && sc->num_nodes > 0;
-  std::vector<kdpt_geom> allg(sc->geoms, sc->geoms + sc->num_geoms);
-  if (viz) {
-    if (sc->num_materials < 1) return fail(KDPT_ERR_ARG, "viz_kd needs a material");
-    for (int k = 0; k < sc->num_nodes; k++) {
-      kdpt_geom g{};
-      g.type = 1;
-      g.materialid = sc->num_materials - 1;
-      kdpt_host::node_box_matrices(sc->nodes[k].mins, sc->nodes[k].maxs, g.transform, g.inverseTransform);
-      allg.push_back(g);
-    }
-  }
-  std::vector<DevGeom> dg(allg.size());
-  for (size_t i = 0; i < allg.size(); i++) {
-    dg[i].type = allg[i].type;
-    dg[i].materialid = allg[i].materialid;
-    memcpy(dg[i].transform, allg[i].transform, 64);
-    memcpy(dg[i].inverseTransform, allg[i].inverseTransform, 64);
-    memcpy(dg[i].invTranspose, allg[i].invTranspose, 64);
-    {  // world bounds of the transformed unit cube (contains the transformed unit sphere), + margin
-      const float* m = allg[i].transform;  // column-major
-      double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-      for (int k = 0; k < 8; k++) {
-        const double v[3] = {(k & 1) ? 0.5 : -0.5, (k & 2) ? 0.5 : -0.5, (k & 4) ? 0.5 : -0.5};
-        for (int r = 0; r < 3; r++) {
-          const double w = (double)m[r] * v[0] + (double)m[4 + r] * v[1] + (double)m[8 + r] * v[2] + (double)m[12 + r];
-          lo[r] = std::min(lo[r], w);
-          hi[r] = std::max(hi[r], w);
-        }
-      }
-      const double ext = std::max(std::max(hi[0] - lo[0], hi[1] - lo[1]), hi[2] - lo[2]);
-      const double margin = 1e-3 * ext + 1e-3;
-      for (int r = 0; r < 3; r++) {
-        dg[i].wlo[r] = (float)(lo[r] - margin);
-        dg[i].whi[r] = (float)(hi[r] + margin);
-      }
-      dg[i].wlo[3] = dg[i].whi[3] = 0.0f;
-    }
-    if (dg[i].type != 0 && dg[i].type != 1)  // SPHERE / CUBE: the only types the scene parser creates
-      return bail(fail(KDPT_ERR_UNSUPPORTED, "geom type other than sphere (0) or cube (1)"));
-    if (dg[i].materialid < 0 || dg[i].materialid >= sc->num_materials)
-      return bail(fail(KDPT_ERR_ARG, "geom materialid out of range"));
-  }
-  std::vector<DevMaterial> dm(sc->num_materials);
-  for (int i = 0; i < sc->num_materials; i++) {
-    const kdpt_material& m = sc->materials[i];
-    DevMaterial& d = dm[i];
-    memcpy(d.color, m.color, 12);
-    d.spec_exponent = m.specular_exponent;
-    memcpy(d.spec_color, m.specular_color, 12);
-    d.hasReflective = m.hasReflective;
-    d.hasRefractive = m.hasRefractive;
-    d.indexOfRefraction = m.indexOfRefraction;
-    d.emittance = m.emittance;
-    memcpy(d.transmittance, m.transmittance, 12);
-    // glm::pow((1.0f - ior) / (1.0f + ior), 2.0f): powf(x, 2) folds to x * x
-    float rr = (1.0f - m.indexOfRefraction) / (1.0f + m.indexOfRefraction);
-    d.fresnel_R0 = rr * rr;
-    d.pad_[0] = d.pad_[1] = d.pad_[2] = 0;
-  }
+  // the prepared arrays onto the device, DevScene pointed at them
+  auto up = [&](auto** d, const auto& v) { return dupload(c, d, v.data(), v.size()); };
+  DevScene& S = c->S;
   DevGeom* d_geoms;
   DevMaterial* d_mats;
-  if ((rc = dupload(c, &d_geoms, dg.data(), dg.size()))) return bail(rc);
-  if ((rc = dupload(c, &d_mats, dm.data(), dm.size()))) return bail(rc);
-  c->S.geoms = d_geoms;
-  c->S.num_geoms = sc->num_geoms;
-  c->S.num_boxes = viz ? sc->num_nodes : 0;
-  c->viz = viz;
-  c->S.materials = d_mats;
-  c->S.num_materials = sc->num_materials;
-  c->S.has_obj = sc->has_obj ? 1 : 0;
-  c->S.num_nodes = sc->has_obj ? sc->num_nodes : 0;
-  c->S.root = 0;
-  c->S.n0_left = c->S.n0_right = c->S.n1_left = c->S.n1_right = -1;
-  set_cull(c, cluster_margin({}, {}, {}));  // (no triangles: the fast margin; replaced below)
-  if (sc->has_obj && sc->num_nodes > 0 && !brute) {
-    const int nn = sc->num_nodes, nt = sc->num_tris;
-    std::vector<int4> nodes(4 * (size_t)nn);
-    std::vector<float4> tv(nt), e1(nt), e2(nt), n0(nt), n1(nt), n2(nt);
-    for (int i = 0; i < nn; i++) {  // one 64-byte record per node (one cache line per visit)
-      const kdpt_node_bare& N = sc->nodes[i];
-      nodes[4 * i + 0] = make_int4(fbits(N.mins[0]), fbits(N.mins[1]), fbits(N.mins[2]), fbits(N.maxs[0]));
-      nodes[4 * i + 1] = make_int4(fbits(N.maxs[1]), fbits(N.maxs[2]), N.leftID, N.rightID);
-      nodes[4 * i + 2] = make_int4(N.parentID, N.triIdStart, N.triIdSize, N.axis);
-      nodes[4 * i + 3] = make_int4(0, 0, 0, 0);
-    }
-    for (int i = 0; i < nt; i++) {
-      const kdpt_tri_bare& T = sc->tris[i];
-      // glm::intersectRayTriangle's e1 = v1 - v0, e2 = v2 - v0 in float: same bits here
-      tv[i] = make_float4(T.x1, T.y1, T.z1, ibits(T.mtlIdx));
-      e1[i] = make_float4(T.x2 - T.x1, T.y2 - T.y1, T.z2 - T.z1, 0.0f);
-      e2[i] = make_float4(T.x3 - T.x1, T.y3 - T.y1, T.z3 - T.z1, 0.0f);
-      n0[i] = make_float4(T.nx1, T.ny1, T.nz1, 0.0f);
-      n1[i] = make_float4(T.nx2, T.ny2, T.nz2, 0.0f);
-      n2[i] = make_float4(T.nx3, T.ny3, T.nz3, 0.0f);
-    }
-    int4* dnodes;
+  if ((rc = up(&d_geoms, p.geoms)) || (rc = up(&d_mats, p.materials))) return bail(rc);
+  S.geoms = d_geoms;
+  S.num_geoms = p.num_geoms;
+  S.num_boxes = p.num_boxes;
+  c->viz = p.viz;
+  S.materials = d_mats;
+  S.num_materials = sc->num_materials;
+  S.has_obj = (p.kd || p.brute) ? 1 : 0;
+  S.num_nodes = p.num_nodes;
+  S.root = 0;
+  S.n0_left = p.n0_left;
+  S.n0_right = p.n0_right;
+  S.n1_left = p.n1_left;
+  S.n1_right = p.n1_right;
+  S.rlo = p.rlo;
+  S.rhi = p.rhi;
+  set_cull(c, p.cull);
+  if (p.kd || p.brute) {
     float4 *dtv, *de1, *de2, *dn0, *dn1, *dn2;
+    if ((rc = up(&dtv, p.tri.tv0)) || (rc = up(&de1, p.tri.te1)) || (rc = up(&de2, p.tri.te2)) ||
+        (rc = up(&dn0, p.tri.tn0)) || (rc = up(&dn1, p.tri.tn1)) || (rc = up(&dn2, p.tri.tn2)))
+      return bail(rc);
+    S.tv0 = dtv;
+    S.te1 = de1;
+    S.te2 = de2;
+    S.tn0 = dn0;
+    S.tn1 = dn1;
+    S.tn2 = dn2;
+  }
+  if (p.kd) {
+    const ClusterSet& cs = p.clusters;
+    int4 *dnodes, *dpn = nullptr, *ddn = nullptr, *dsn = nullptr, *dsp;
     int* doff;
-    if ((rc = dupload(c, &dnodes, nodes.data(), nodes.size())) || (rc = dupload(c, &dtv, tv.data(), nt)) ||
-        (rc = dupload(c, &de1, e1.data(), nt)) || (rc = dupload(c, &de2, e2.data(), nt)) ||
-        (rc = dupload(c, &dn0, n0.data(), nt)) || (rc = dupload(c, &dn1, n1.data(), nt)) ||
-        (rc = dupload(c, &dn2, n2.data(), nt)) ||
-        (rc = dupload(c, &doff, sc->obj_materialOffsets, (size_t)sc->num_shapes)))
+    int2 *dl, *di;
+    float4 *dlo, *dhi, *dv0, *dce1, *dce2, *dn, *du, *dv, *dw, *dsupn, *dsupb;
+    if ((rc = up(&dnodes, p.nodes)) || (rc = up(&doff, p.obj_material_offsets)) ||
+        (!p.pnodes.empty() && (rc = up(&dpn, p.pnodes))) || (!p.dnodes.empty() && (rc = up(&ddn, p.dnodes))) ||
+        (!p.snodes.empty() && (rc = up(&dsn, p.snodes))) ||
+        (rc = up(&dl, cs.leaf_cl)) || (rc = up(&di, cs.info)) || (rc = up(&dlo, cs.lo)) || (rc = up(&dhi, cs.hi)) ||
+        (rc = up(&dv0, cs.cv0)) || (rc = up(&dce1, cs.ce1)) || (rc = up(&dce2, cs.ce2)) ||
+        (rc = up(&dsp, cs.sup)) || (rc = up(&dn, cs.nrm)) || (rc = up(&du, cs.obb_u)) ||
+        (rc = up(&dv, cs.obb_v)) || (rc = up(&dw, cs.obb_w)) || (rc = up(&dsupn, cs.sup_n)) ||
+        (rc = up(&dsupb, cs.sup_b)))
       return bail(rc);
-    c->S.nodes = dnodes;
-    c->S.pnodes = nullptr;
-    std::vector<int2> leaf_cl, leaf_sp;
-    if ((rc = build_clusters(c, sc, tv, e1, e2, leaf_cl, leaf_sp))) return bail(rc);
-    std::vector<int4> packed;
-    if (pack_nodes(sc->nodes, nn, leaf_cl, packed)) {
-      int4* dp;
-      if ((rc = dupload(c, &dp, packed.data(), packed.size()))) return bail(rc);
-      c->S.pnodes = dp;
+    S.nodes = dnodes;
+    S.pnodes = dpn;
+    S.dnodes = ddn;
+    S.snodes = dsn;
+    S.obj_material_offsets = doff;
+    S.leaf_cl = dl;
+    S.num_clusters = (int)cs.info.size();
+    S.cl_counts = p.cl_counts;
+    S.cl_info = di;
+    S.cl_lo = dlo;
+    S.cl_hi = dhi;
+    S.c_v0 = dv0;
+    S.c_e1 = dce1;
+    S.c_e2 = dce2;
+    S.sup = dsp;
+    S.num_supers = p.num_supers;
+    S.cl_n = dn;
+    S.cl_slab = 1;
+    S.cl_u = du;
+    S.cl_v = dv;
+    S.cl_w = dw;
+    S.cl_obb = 1;
+    S.flat_obb = 1;
+    S.sup_n = dsupn;
+    S.sup_b = dsupb;
+    S.sup_slab = 1;
+    // the masked one-level cull's direction masks, for the fast margin the box levels use
+    if (p.wants_masks) {
+      c->mask_cs.reset(new ClusterSet(std::move(p.clusters)));
+      if ((rc = build_masks(c, dir_mask_resolution(S.num_clusters)))) return bail(rc);
     }
-    c->S.dnodes = nullptr;
-    c->S.snodes = nullptr;
-    if (pack_nodes16(sc->nodes, nn, leaf_cl, packed)) {
-      int4* dp;
-      if ((rc = dupload(c, &dp, packed.data(), packed.size()))) return bail(rc);
-      c->S.dnodes = dp;
-      // the same records with a big leaf's first super-cluster (TREE_LDS16S), when the scene has supers
-      if (c->S.num_supers > 0 && pack_nodes16(sc->nodes, nn, leaf_sp, packed)) {
-        if ((rc = dupload(c, &dp, packed.data(), packed.size()))) return bail(rc);
-        c->S.snodes = dp;
-      }
-    }
-    c->S.tv0 = dtv;
-    c->S.te1 = de1;
-    c->S.te2 = de2;
-    c->S.tn0 = dn0;
-    c->S.tn1 = dn1;
-    c->S.tn2 = dn2;
-    c->S.obj_material_offsets = doff;
-    c->S.rlo = make_float4(sc->nodes[0].mins[0], sc->nodes[0].mins[1], sc->nodes[0].mins[2], 0.0f);
-    c->S.rhi = make_float4(sc->nodes[0].maxs[0], sc->nodes[0].maxs[1], sc->nodes[0].maxs[2], 0.0f);
-    c->S.n0_left = sc->nodes[0].leftID;
-    c->S.n0_right = sc->nodes[0].rightID;
-    if (nn > 1) {
-      c->S.n1_left = sc->nodes[1].leftID;
-      c->S.n1_right = sc->nodes[1].rightID;
-    }
-  } else if (brute) {
-    // pathTraceOneBounce's triangles: the file-order OBJ triangles (vertex/normal gathers done here
-    // once; the values are the ones the reference's kernel gathers per test)
-    const int nt = sc->polyidxcount / 3;
-    std::vector<float4> tv(nt), e1(nt), e2(nt), n0(nt), n1(nt), n2(nt);
-    for (int k = 0; k < nt; k++) {
-      const int* ix = sc->obj_polysidxflat + 3 * (size_t)k;
-      const float* a = sc->obj_verts + 3 * (size_t)ix[0];
-      const float* b = sc->obj_verts + 3 * (size_t)ix[1];
-      const float* cc = sc->obj_verts + 3 * (size_t)ix[2];
-      tv[k] = make_float4(a[0], a[1], a[2], 0.0f);
-      e1[k] = make_float4(b[0] - a[0], b[1] - a[1], b[2] - a[2], 0.0f);
-      e2[k] = make_float4(cc[0] - a[0], cc[1] - a[1], cc[2] - a[2], 0.0f);
-      const float* na = sc->obj_norms + 3 * (size_t)ix[0];
-      const float* nb = sc->obj_norms + 3 * (size_t)ix[1];
-      const float* nc = sc->obj_norms + 3 * (size_t)ix[2];
-      n0[k] = make_float4(na[0], na[1], na[2], 0.0f);
-      n1[k] = make_float4(nb[0], nb[1], nb[2], 0.0f);
-      n2[k] = make_float4(nc[0], nc[1], nc[2], 0.0f);
-    }
-    std::vector<float4> clo, chi;
-    build_chunk_boxes(tv, e1, e2, nt, clo, chi);
-    set_cull(c, cluster_margin(tv, e1, e2));
-    std::vector<BruteShape> shp(sc->num_shapes);
-    for (int i = 0; i < sc->num_shapes; i++) {
-      // glm::vec3(obj_polysbboxes[i] - 0.01, ...): double arithmetic, rounded to float by the constructor
-      const float* bb = sc->obj_bboxes;
-      float l[3] = {0, 0, 0}, h[3] = {0, 0, 0};
-      if (o.use_bbox)
-        for (int k = 0; k < 3; k++) {
-          l[k] = (float)((double)bb[i + k] - 0.01);
-          h[k] = (float)((double)bb[i + 3 + k] + 0.01);
-        }
-      shp[i].lo = make_float4(l[0], l[1], l[2], ibits(sc->obj_polyoffsets[i]));
-      shp[i].hi = make_float4(h[0], h[1], h[2], ibits(sc->obj_materialOffsets[i]));
-    }
-    float4 *dtv, *de1, *de2, *dn0, *dn1, *dn2;
-    if ((rc = dupload(c, &dtv, tv.data(), nt)) || (rc = dupload(c, &de1, e1.data(), nt)) ||
-        (rc = dupload(c, &de2, e2.data(), nt)) || (rc = dupload(c, &dn0, n0.data(), nt)) ||
-        (rc = dupload(c, &dn1, n1.data(), nt)) || (rc = dupload(c, &dn2, n2.data(), nt)) ||
-        (rc = dupload(c, &c->shapes, shp.data(), shp.size())) ||
-        (rc = dupload(c, &c->chunk_lo, clo.data(), clo.size())) || (rc = dupload(c, &c->chunk_hi, chi.data(), chi.size())))
+  } else if (p.brute) {
+    if ((rc = up(&c->shapes, p.shapes)) || (rc = up(&c->chunk_lo, p.chunk_lo)) || (rc = up(&c->chunk_hi, p.chunk_hi)))
       return bail(rc);
-    c->S.tv0 = dtv;
-    c->S.te1 = de1;
-    c->S.te2 = de2;
-    c->S.tn0 = dn0;
-    c->S.tn1 = dn1;
-    c->S.tn2 = dn2;
-    c->S.num_nodes = 0;
-    c->num_shapes = sc->num_shapes;
+    c->num_shapes = (int)p.shapes.size();
     c->brute = true;
-  } else {
-    c->S.has_obj = 0;
   }
   if (o.external_image) {
     c->image = o.external_image;

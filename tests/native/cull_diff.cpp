@@ -19,7 +19,7 @@
 #include <vector>
 
 #define KDPT_RCP_ULP  // kd_rcp follows kdpt_rcp_ulp (the device reciprocal's 1-ulp error)
-#include "../../kdtreepathtraceroptimization_amd/csrc/kdpt_clusters.h"
+#include "../../kdtreepathtraceroptimization_amd/csrc/kdpt_scene_prep.h"
 
 // the masked cull's box coefficient and mask resolution: the product's (cluster_margin, dir_mask_resolution)
 // unless MASK_KF / MASK_N say otherwise
@@ -233,9 +233,9 @@ struct MaskTables {
 // box at the masked cull's coefficient Kf; a missed pair's mask and danger_needs_test, under each of the three
 // reciprocal perturbations).  A pair a cull drops while a triangle passes glm's u/v tests, or a
 // passing triangle the masked cull does not test, is a violation.
-int sim(const char* path, const kdpt_node_bare* nodes, int nn, const kdpt_tri_bare* tris, int nt,
-        const std::vector<float4>& tv, const std::vector<float4>& e1, const std::vector<float4>& e2,
+int sim(const char* path, const kdpt_node_bare* nodes, int nn, const kdpt_tri_bare* tris, int nt, const TriArrays& T,
         const ClusterGrouping& grp) {
+  const std::vector<float4>&tv = T.tv0, &e1 = T.te1, &e2 = T.te2;
   FILE* f = fopen(path, "rb");
   if (!f) return 3;
   std::vector<float> r;
@@ -247,27 +247,15 @@ int sim(const char* path, const kdpt_node_bare* nodes, int nn, const kdpt_tri_ba
   build_cluster_set(nodes, nn, tris, tv, e1, e2, cs, grp);
   const CullMargin cm = cluster_margin(cs.cv0, cs.ce1, cs.ce2);
   const CullK ck{cm.K, cm.K_lo, cm.a, cm.b, cm.c};
-  std::vector<int4> nd4(4 * (size_t)nn);
-  for (int i = 0; i < nn; i++) {
-    const kdpt_node_bare& N = nodes[i];
-    nd4[4 * i] = int4{fbits(N.mins[0]), fbits(N.mins[1]), fbits(N.mins[2]), fbits(N.maxs[0])};
-    nd4[4 * i + 1] = int4{fbits(N.maxs[1]), fbits(N.maxs[2]), N.leftID, N.rightID};
-    nd4[4 * i + 2] = int4{N.parentID, N.triIdStart, N.triIdSize, N.axis};
-    nd4[4 * i + 3] = int4{0, 0, 0, 0};
-  }
-  std::vector<float4> n0(nt), n1(nt), n2(nt);
-  for (int i = 0; i < nt; i++) {
-    n0[i] = float4{tris[i].nx1, tris[i].ny1, tris[i].nz1, 0};
-    n1[i] = float4{tris[i].nx2, tris[i].ny2, tris[i].nz2, 0};
-    n2[i] = float4{tris[i].nx3, tris[i].ny3, tris[i].nz3, 0};
-  }
+  std::vector<int4> nd4;
+  pack_wide_nodes(nodes, nn, nd4);
   std::vector<int> offs(64, 0);
   DevScene S{};
   S.num_nodes = nn;
   S.root = 0;
   S.nodes = nd4.data();
   S.tv0 = tv.data(); S.te1 = e1.data(); S.te2 = e2.data();
-  S.tn0 = n0.data(); S.tn1 = n1.data(); S.tn2 = n2.data();
+  S.tn0 = T.tn0.data(); S.tn1 = T.tn1.data(); S.tn2 = T.tn2.data();
   S.obj_material_offsets = offs.data();
   S.n0_left = nodes[0].leftID; S.n0_right = nodes[0].rightID;
   S.n1_left = nn > 1 ? nodes[1].leftID : -1; S.n1_right = nn > 1 ? nodes[1].rightID : -1;
@@ -368,14 +356,10 @@ int main(int argc, char** argv) {
   const bool rays_mode = strcmp(argv[2], "--rays") == 0;
   const long long nlines = rays_mode ? 0 : atoll(argv[2]);
   const unsigned seed = (unsigned)atoi(argv[3]);
-  // the triangle records exactly as kdpt_create forms them (e1 = v1 - v0, e2 = v2 - v0 in float)
-  std::vector<float4> tv(nt), e1(nt), e2(nt);
-  for (int i = 0; i < nt; i++) {
-    const kdpt_tri_bare& T = tris[i];
-    tv[i] = make_float4(T.x1, T.y1, T.z1, ibits(T.mtlIdx));
-    e1[i] = make_float4(T.x2 - T.x1, T.y2 - T.y1, T.z2 - T.z1, 0.0f);
-    e2[i] = make_float4(T.x3 - T.x1, T.y3 - T.y1, T.z3 - T.z1, 0.0f);
-  }
+  // the triangle records kdpt_create uploads (e1 = v1 - v0, e2 = v2 - v0 in float)
+  TriArrays T;
+  pack_triangles(tris.data(), nt, T);
+  const std::vector<float4>&tv = T.tv0, &e1 = T.te1, &e2 = T.te2;
   if (strcmp(argv[2], "--masks") == 0) {
     // cull_diff TREE --masks OUT.bin: the masks kdpt_create builds on the device for this tree (the scene's
     // masked-cull coefficient and resolution), from the host builder: int32 n, int32 num_clusters, float Kf,
@@ -402,11 +386,11 @@ int main(int argc, char** argv) {
     grp.mode = argc > 4 ? atoi(argv[4]) : 0;
     grp.chord = argc > 5 ? atof(argv[5]) : 0.5;
     grp.min_split = argc > 6 ? atoi(argv[6]) : 8;
-    return sim(argv[3], nodes.data(), nn, tris.data(), nt, tv, e1, e2, grp);
+    return sim(argv[3], nodes.data(), nn, tris.data(), nt, T, grp);
   }
   ClusterSet cs;
   // CLUSTER_CHORD > 0: the normal-cone grouping kdpt_create uses for meshes with a rigorous margin
-  // (kdpt_runtime.hip build_clusters, CLUSTER_CHORD_EXACT)
+  // (kdpt_scene_prep.h choose_clusters, CLUSTER_CHORD_EXACT)
   ClusterGrouping grouping;
   if (getenv("CLUSTER_CHORD") && atof(getenv("CLUSTER_CHORD")) > 0) {
     grouping.mode = 1;

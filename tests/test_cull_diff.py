@@ -95,7 +95,7 @@ def test_c5_margin_is_rigorous_and_never_drops_a_pass(cull_diff, trees):
 
 def test_c5_normal_cone_clusters_never_drop_a_pass(cull_diff, trees):
     """The clusters kdpt_create builds for C5's icosphere (normal cones of chord CLUSTER_CHORD_EXACT = 0.03 before
-    the Morton runs, kdpt_runtime.hip build_clusters): other clusters, supers, slabs and oriented boxes, the same
+    the Morton runs, kdpt_scene_prep.h choose_clusters): other clusters, supers, slabs and oriented boxes, the same
     rigorous margin -- 3 * 10^6 adversarial lines find no dropped pass at any level."""
     r = run(cull_diff, trees("icosphere_8"), 3_000_000, 42, env={"CLUSTER_CHORD": "0.03"})
     assert r["exact"] == 1 and r["margin"] >= r["rigorous"], r

@@ -9,7 +9,10 @@ restatement under ASan/UBSan; the product's host code parses untrusted OBJ/MTL/s
   sanitizer report;
 - tests/native/traverse_diff.cpp linked with a sanitized build of the oracle (oracle/kdpt_oracle.c,
   whose literal visited bitmap is where the reference itself writes nodeIDs[-1]): the differential
-  traversal test runs clean and still finds no mismatch.
+  traversal test runs clean and still finds no mismatch;
+- tests/native/scene_prep_host.cpp: kdpt_create's scene validation and packing (csrc/kdpt_scene_prep.h), the
+  code that reads nodes[ch].parentID, obj_polysidxflat[j] and the like from caller memory -- every option set
+  on the edge OBJs, and every refusal provoked by one mutation of a private, exactly sized copy of the scene.
 """
 import json
 import os
@@ -116,3 +119,53 @@ def test_oracle_and_traversal_clean_under_sanitizers():
                                 "5", hybrid], capture_output=True, text=True, timeout=600, env=ENV)
             assert p.returncode == 0, p.stderr[-4000:]
             assert json.loads(p.stdout.strip().splitlines()[-1])["mismatches"] == 0
+
+
+@pytest.fixture(scope="module")
+def scene_prep_host():
+    exe = os.path.join(ROOT, "build", "scene_prep_host")
+    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    tmp = f"{exe}.{os.getpid()}"
+    subprocess.run(["g++", *SAN, "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-I", os.path.join(ROOT, "include"),
+                    os.path.join(TESTS, "native", "scene_prep_host.cpp"), os.path.join(TESTS, "native", "no_device_build.cpp"),
+                    os.path.join(CSRC, "scene_host.cpp"), "-o", tmp], check=True)
+    os.replace(tmp, exe)
+    return exe
+
+
+def _run_prep(exe, scene, obj):
+    p = subprocess.run([exe, scene, obj], capture_output=True, text=True, timeout=300, env=ENV)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    assert "runtime error" not in p.stderr and "Sanitizer" not in p.stderr, p.stderr[-4000:]
+    r = json.loads(p.stdout.strip().splitlines()[-1])
+    assert r["load_rc"] == 0 and r["failed"] == 0 and r["option_sets"] == 5
+    return r
+
+
+# every mutation of tests/native/scene_prep_host.cpp, one refusal of prepare_scene each (the accepted one: shade_oob)
+MUTATIONS = {
+    "root_parent_not_minus_1", "id_not_index", "child_not_above_parent", "child_parent_disagrees", "tri_range_past_end",
+    "leaf_with_child", "node_1_not_roots_left", "parent_not_below_index", "chain_of_17_levels", "mtlidx_negative",
+    "mtlidx_num_shapes", "mtlidx_1_of_two_shapes", "offsets_missing", "geom_type_2", "geom_material_out_of_range",
+    "materials_65", "resolution_0_by_n", "resolution_2_30_pixels", "bounce_cap_31", "block_size_128", "brute_null_norms",
+    "brute_offsets_not_multiple_of_3", "brute_material_offset_out_of_range", "brute_offsets_do_not_sum",
+    "brute_vertex_index_past_arrays", "brute_short_bboxes", "viz_kd_without_materials",
+}
+# the mutations that need a tree of two or three nodes (a one-leaf tree reports them as skipped)
+NEED_INNER_NODES = {"id_not_index", "child_not_above_parent", "child_parent_disagrees", "leaf_with_child",
+                    "node_1_not_roots_left", "parent_not_below_index"}
+
+
+@pytest.mark.parametrize("name", sorted(EDGE_OBJS))
+def test_scene_prep_clean_under_sanitizers(scene_prep_host, files, name):
+    d, scene = files
+    r = _run_prep(scene_prep_host, scene, str(d / f"{name}.obj"))
+    assert set(r["ran"]) | set(r["skipped"]) == MUTATIONS and set(r["skipped"]) <= NEED_INNER_NODES
+    if name == "random_2500":  # a real tree: every refusal is exercised, and the big leaves have clusters
+        assert r["nodes"] >= 3 and not r["skipped"] and r["clusters"] > 0
+
+
+@pytest.mark.skipif(not HAS_REFERENCE, reason="/root/reference not present")
+def test_scene_prep_reference_mesh_clean_under_sanitizers(scene_prep_host):
+    r = _run_prep(scene_prep_host, f"{REFERENCE}/scenes/cornell.txt", f"{REFERENCE}/scenes/sphere_low_1.obj")
+    assert not r["skipped"] and set(r["ran"]) == MUTATIONS
