@@ -110,6 +110,22 @@ struct IterState {
   float* image = nullptr;
   bool zero_partial = false;
   unsigned long long* total_segments = nullptr;
+
+  // The state's part of each launch's arguments (launch_batch's stages).
+  GenIter gen_iter(int iter) const { return {iter, buf[0], counts, work, trace_t, lb, zero_partial ? image : nullptr}; }
+  // (takes this use's bounce-0 counter and hands the other one over for zeroing: flips gen_parity)
+  GenGeomsIter gen_geoms_iter() {
+    cc0_cur = ccount0 + gen_parity;
+    gen_parity ^= 1;
+    return {cc0_cur, ccount0 + gen_parity, cray, hits, cand};
+  }
+  GeomsIter geoms_iter() const { return {buf[cur], counts, cray, hits, cand, ccount}; }
+  // The candidate counter of bounce `depth`, indexed by depth: k_gen_geoms_b counted bounce 0 into cc0_cur.
+  const int* cand_count(int depth, bool gen_geoms) const { return (depth == 0 && gen_geoms) ? cc0_cur : ccount; }
+  TraceIter trace_iter(int depth, bool gen_geoms) const { return {cand, cand_count(depth, gen_geoms), cray, hits}; }
+  // (compaction goes into the other path buffer)
+  FuseArgs fuse_args() const { return {buf[cur ^ 1], tickets, lb, counts, ccount, cray, hits, cand}; }
+  ScatterPrep scatter_prep(bool on) const { return {on ? 1 : 0, prep, cray, hits, cand, tile_coff}; }
 };
 
 // A pipeline group: `batch` iterations at a time in lockstep on the group's own stream; acc_ev: its last
@@ -178,6 +194,7 @@ struct kdpt_ctx {
   int next_group = 0;  // the group the next batch goes to
   bool profile_batches = false;
   bool profile_steps = false;  // "profile_batches" = 2
+  hipEvent_t entry_ev = nullptr;   // enqueue_iterations: what the context's own stream held when the call began
   hipEvent_t acc_last = nullptr;   // the most recent add (a group's acc_ev): the next add follows it
   hipEvent_t img_last = nullptr;   // the most recent frame reduce + image add (one of frame_ev)
   // intersect-kernel timing (testing_mode) of every iteration, read back at synchronisation
@@ -472,7 +489,8 @@ void dfree(kdpt_ctx* c, void* p) {
 
 // The direction masks of the scene's clusters at resolution n (cube-map cells per face edge), built on the device (k_build_masks) from the per-entry records and the bucket directions the host
 // computes (kdpt_clusters.h mask_entries / mask_buckets; tests/test_gpu_parity.py checks the cells against the
-// host builder).  A rebuild (knobs "cull_mask_n", "cull_fast_k") frees the previous tables.
+// host builder).  A rebuild (knobs "cull_mask_n", "cull_fast_k") frees the previous table once the new one is
+// filled; a failed one changes nothing in the context.
 int build_masks(kdpt_ctx* c, int n) {
   const auto t0 = std::chrono::steady_clock::now();
   const ClusterSet& cs = *c->mask_cs;
@@ -498,13 +516,9 @@ int build_masks(kdpt_ctx* c, int n) {
     ent[3 * ne + k] = me.beta[k];
     ent[4 * ne + k] = me.dthr[k];
   }
-  dfree(c, c->mask_dev);
-  c->mask_dev = nullptr;
-  c->S.cl_mask = nullptr;
+  // The new table is the context's only once it is filled: until then mask_dev, mask_n and S.cl_mask keep
+  // describing the previous one, which a failure below leaves in place.
   unsigned long long* dm = nullptr;
-  int rc;
-  if ((rc = dalloc(c, &dm, (size_t)nb * ncl))) return rc;
-  c->mask_dev = dm;
   double* d_ent = nullptr;
   float* d_krig = nullptr;
   double* d_bd = nullptr;
@@ -515,7 +529,8 @@ int build_masks(kdpt_ctx* c, int n) {
   };
   // (the uploads on the context's stream, ahead of the kernel; pageable sources are staged before each call
   // returns, and the stream is drained before the temporaries go)
-  if (hipMalloc(&d_ent, ent.size() * sizeof(double)) != hipSuccess ||
+  if (hipMalloc((void**)&dm, std::max<size_t>((size_t)nb * ncl, 1) * sizeof(unsigned long long)) != hipSuccess ||
+      hipMalloc(&d_ent, ent.size() * sizeof(double)) != hipSuccess ||
       hipMalloc(&d_krig, me.krig.size() * sizeof(float)) != hipSuccess ||
       hipMalloc(&d_bd, bd.size() * sizeof(double)) != hipSuccess ||
       hipMemcpyAsync(d_ent, ent.data(), ent.size() * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
@@ -524,45 +539,121 @@ int build_masks(kdpt_ctx* c, int n) {
       hipMemcpyAsync(d_bd, bd.data(), bd.size() * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess) {
     (void)hipStreamSynchronize(c->stream);
     release();
+    (void)hipFree(dm);
     return fail(KDPT_ERR_HIP, "mask build: device buffers");
   }
   hipLaunchKernelGGL(k_build_masks, dim3(ncl, (nb + 255) / 256), dim3(256), 0, c->stream, d_ent, d_krig, d_bd, ncl,
                      nb, Kf, dm);
   const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(c->stream);
   release();
-  if (e1 != hipSuccess || e2 != hipSuccess) return fail(KDPT_ERR_HIP, "k_build_masks failed");
-  if (!c->tn_dev) {
+  int rc = (e1 != hipSuccess || e2 != hipSuccess) ? fail(KDPT_ERR_HIP, "k_build_masks failed") : KDPT_OK;
+  if (!rc && !c->tn_dev) {
     std::vector<float4> tn;
     build_entry_normals(cs, tn);
-    if ((rc = dupload(c, &c->tn_dev, tn.data(), tn.size()))) return rc;
+    float4* d_tn = nullptr;
+    if ((rc = dupload(c, &d_tn, tn.data(), tn.size()))) dfree(c, d_tn);
+    else c->tn_dev = d_tn;
   }
+  if (rc) {
+    (void)hipFree(dm);
+    return rc;
+  }
+  // the swap: the previous table is freed before the call returns (the stream was drained above)
+  dfree(c, c->mask_dev);
+  c->allocs.push_back(dm);
+  c->mask_dev = dm;
   c->mask_n = n;
   c->mask_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   apply_cull_route(c);
   return KDPT_OK;
 }
 
-template <bool HYBRID, bool COUNT, int MODE>
-int trace_occupancy(kdpt_ctx* c, size_t lds, int* blocks) {
-  if (lds > 0)
-    HIP_TRY(hipFuncSetAttribute((const void*)k_trace<HYBRID, COUNT, MODE>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, k_trace<HYBRID, COUNT, MODE>, trace_block<MODE>(), lds));
-  return KDPT_OK;
+// ---------------------------------------------------------------------------
+// Kernel variants: the one place where run-time choices become template arguments.  Every launch, occupancy
+// query and attribute call takes its kernel from these tables as a typed pointer (a wrong argument struct stays
+// a compile error); a new tree route or template flag is a new table entry and nothing else.
+//
+// The GPU test that reaches each entry (H / B: the hybrid / bare walk, short_stack 1 / 0):
+//   k_trace, count off: TREE_WIDE, PACKED, LDS, LDS16 / LDS16G, H and B -- test_soup_cast_equals_oracle (rootleaf8200
+//     "tree_global", syn20000, "tree_format" 32, "tree_format" 16); LDS16G, LDS16S, H and B -- test_cast_equals_oracle
+//     (ico7, ico7-margin); in renders test_tuning_knobs_keep_parity, test_derived_box_tree_in_lds
+//   k_trace, count on: TREE_WIDE, PACKED, LDS, LDS16, H and B -- test_soup_counters_on_every_route; LDS, H also
+//     test_counters_match_oracle; LDS16G, LDS16S -- no test (bench.py --full counts C5 on LDS16S)
+//   k_shade: compact + sort -- test_iteration2_sort_order (H), test_bit_exact_vs_oracle dragon_96_bare (B); compact
+//     alone -- test_fused_shading_equals_scan_scatter (H); neither -- test_bit_exact_vs_oracle dragon_64_nocompact
+//     (H); sort alone -- test_brute_force_bit_exact_vs_oracle sphere_48_brute_nocompact (H); B, those three: no test
+//   k_shade_fused_b: STAGE -- every default render (H), dragon_96_bare (B); not STAGE (a scene of more than
+//     ORDERED_GEOMS geoms or STAGE_MATS materials) -- no test; k_shade_fused: H + STAGE --
+//     test_tuning_knobs_keep_parity "shade_batch"; the other three -- no test
+//   k_brute: count on -- test_brute_force_counters_match_oracle (use_bbox 0, 1); off --
+//     test_brute_force_bit_exact_vs_oracle (both); k_cast_resolve: H and B -- test_cast_equals_oracle
+// ---------------------------------------------------------------------------
+struct TraceKernel {
+  void (*fn)(TraceArgs);
+  int block;
+};
+template <bool H, bool C, int M>
+constexpr TraceKernel trace_variant() {
+  return {k_trace<H, C, M>, trace_block<M>()};
+}
+#define TRACE_MODES(H, C)                                                                                         \
+  {trace_variant<H, C, TREE_WIDE>(),  trace_variant<H, C, TREE_PACKED>(), trace_variant<H, C, TREE_LDS>(),        \
+   trace_variant<H, C, TREE_LDS16>(), trace_variant<H, C, TREE_LDS16G>(), trace_variant<H, C, TREE_LDS16S>()}
+// (mode: a TreeMode, the enum's values in order)
+TraceKernel trace_kernel(bool hybrid, bool count, int mode) {
+  static const TraceKernel table[2][2][6] = {{TRACE_MODES(false, false), TRACE_MODES(false, true)},
+                                             {TRACE_MODES(true, false), TRACE_MODES(true, true)}};
+  return table[hybrid][count][mode];
+}
+#undef TRACE_MODES
+
+// The shading kernels compute the hit point with the offset of the traversal that found it: 1e-4 for the hybrid
+// walk and the brute-force kernel, 1e-5 for traverseKDbare.
+bool hybrid_shading(const kdpt_ctx* c) { return c->opt.short_stack || c->brute; }
+
+using ShadeKernel = void (*)(ShadeArgs);
+ShadeKernel shade_kernel(bool hybrid, bool compact, bool sort) {
+  static const ShadeKernel table[2][2][2] = {{{k_shade<false, false, false>, k_shade<false, false, true>},
+                                              {k_shade<false, true, false>, k_shade<false, true, true>}},
+                                             {{k_shade<true, false, false>, k_shade<true, false, true>},
+                                              {k_shade<true, true, false>, k_shade<true, true, true>}}};
+  return table[hybrid][compact][sort];
+}
+// stage: the scene's geoms and materials fit the fused kernels' LDS copy
+using FusedKernel = void (*)(ShadeArgs, FuseArgs);
+FusedKernel shade_fused_kernel(bool hybrid, bool stage) {
+  static const FusedKernel table[2][2] = {{k_shade_fused<false, false>, k_shade_fused<false, true>},
+                                          {k_shade_fused<true, false>, k_shade_fused<true, true>}};
+  return table[hybrid][stage];
+}
+using FusedBatchKernel = void (*)(ShadeBatch);
+FusedBatchKernel shade_fused_batch_kernel(bool hybrid, bool stage) {
+  static const FusedBatchKernel table[2][2] = {{k_shade_fused_b<false, false>, k_shade_fused_b<false, true>},
+                                               {k_shade_fused_b<true, false>, k_shade_fused_b<true, true>}};
+  return table[hybrid][stage];
+}
+using BruteKernel = void (*)(BruteArgs);
+BruteKernel brute_kernel(bool use_bbox, bool count) {
+  static const BruteKernel table[2][2] = {{k_brute<false, false>, k_brute<false, true>},
+                                          {k_brute<true, false>, k_brute<true, true>}};
+  return table[use_bbox][count];
 }
 
-template <int MODE>
-int trace_occupancy_all(kdpt_ctx* c, size_t lds, int* blocks) {
-  int best = 0, rc = KDPT_OK;
-  for (int hyb = 0; hyb < 2 && !rc; hyb++)
-    for (int cnt = 0; cnt < 2 && !rc; cnt++) {
+// The workgroups of the route's intersect kernel that fit a CU with `lds` bytes of tree: the fewest over the
+// four (hybrid, count) variants, so that one grid serves whichever of them a launch picks.
+int trace_blocks_per_cu(int mode, size_t lds, int* blocks) {
+  int best = 0;
+  for (int hyb = 0; hyb < 2; hyb++)
+    for (int cnt = 0; cnt < 2; cnt++) {
+      const TraceKernel k = trace_kernel(hyb, cnt, mode);
       int b = 0;
-      rc = hyb ? (cnt ? trace_occupancy<true, true, MODE>(c, lds, &b) : trace_occupancy<true, false, MODE>(c, lds, &b))
-               : (cnt ? trace_occupancy<false, true, MODE>(c, lds, &b) : trace_occupancy<false, false, MODE>(c, lds, &b));
-      if (!rc && (best == 0 || b < best)) best = b;
+      if (lds > 0)
+        HIP_TRY(hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k.fn, k.block, lds));
+      if (best == 0 || b < best) best = b;
     }
   *blocks = best;
-  return rc;
+  return KDPT_OK;
 }
 
 // Pick where the intersect kernel reads the tree from, and its persistent grid: in LDS when it fits (the
@@ -600,12 +691,8 @@ int setup_trace(kdpt_ctx* c) {
   int blocks = 0, best_waves = 0, rc = KDPT_OK;
   for (const Cand& k : cands) {
     int b = 0;
-    rc = k.mode == TREE_LDS16 ? trace_occupancy_all<TREE_LDS16>(c, k.lds, &b)
-       : k.mode == TREE_LDS16G ? trace_occupancy_all<TREE_LDS16G>(c, k.lds, &b)
-       : k.mode == TREE_LDS16S ? trace_occupancy_all<TREE_LDS16S>(c, k.lds, &b)
-                                : trace_occupancy_all<TREE_LDS>(c, k.lds, &b);
-    if (rc) return rc;
-    const int waves = b * (k.mode == TREE_LDS ? TRACE_BLOCK : TRACE_BLOCK16) / 64;
+    if ((rc = trace_blocks_per_cu(k.mode, k.lds, &b))) return rc;
+    const int waves = b * trace_kernel(false, false, k.mode).block / 64;
     if (b > 0 && waves > best_waves) {
       best_waves = waves;
       blocks = b;
@@ -613,14 +700,26 @@ int setup_trace(kdpt_ctx* c) {
       c->tree_lds = k.lds;
     }
   }
-  if (c->tree_lds == 0) {
-    rc = c->tree_mode == TREE_PACKED ? trace_occupancy_all<TREE_PACKED>(c, 0, &blocks)
-                                     : trace_occupancy_all<TREE_WIDE>(c, 0, &blocks);
-    if (rc) return rc;
-  }
+  if (c->tree_lds == 0 && (rc = trace_blocks_per_cu(c->tree_mode, 0, &blocks))) return rc;
   if (blocks < 1) return fail(KDPT_ERR_UNSUPPORTED, "intersect kernel does not fit on a CU");
   c->trace_grid = blocks * prop.multiProcessorCount;
   c->full_trace_grid = c->trace_grid;
+  return KDPT_OK;
+}
+
+// setup_trace again after a knob that can change the route; a "trace_grid_frac" share of the grid is kept.
+int resetup_trace(kdpt_ctx* c) {
+  const double frac = (double)c->trace_grid / std::max(1, c->full_trace_grid);
+  int rc = setup_trace(c);
+  if (rc) return rc;
+  if (c->grid_env) c->trace_grid = std::max(1, (int)(c->full_trace_grid * frac));
+  return KDPT_OK;
+}
+
+// The "reduce_spin_us" knob of a context, or the process default of the contexts created later.
+int set_reduce_spin(double* spin_us, double value) {
+  if (!(value >= 0.0 && value <= 1e6)) return fail(KDPT_ERR_ARG, "reduce_spin_us must be in [0, 1e6]");
+  *spin_us = value;
   return KDPT_OK;
 }
 
@@ -724,6 +823,8 @@ int kdpt_create(const kdpt_scene* sc, const kdpt_options* opt, int device, kdpt_
   if (hipSetDevice(device) != hipSuccess) return bail(fail(KDPT_ERR_HIP, "hipSetDevice failed"));
   c->cu_mask_streams = g_cu_mask_streams;
   if (create_stream(c, &c->stream) != KDPT_OK) return bail(fail(KDPT_ERR_HIP, "hipStreamCreate failed"));
+  if (hipEventCreateWithFlags(&c->entry_ev, hipEventDisableTiming) != hipSuccess)
+    return bail(fail(KDPT_ERR_HIP, "hipEventCreate failed"));
   int rc;
   // the prepared arrays onto the device, DevScene pointed at them
   auto up = [&](auto** d, const auto& v) { return dupload(c, d, v.data(), v.size()); };
@@ -880,22 +981,19 @@ int kdpt_set_options(kdpt_ctx* c, const kdpt_options* o) {
 }
 
 int kdpt_set_tuning(kdpt_ctx* c, const char* name, double value) {
-  if (!c && name && std::string(name) == "reduce_spin_us") {  // the process default of contexts created later
-    if (!(value >= 0.0 && value <= 1e6)) return fail(KDPT_ERR_ARG, "reduce_spin_us must be in [0, 1e6]");
-    g_reduce_spin_us = value;
-    return KDPT_OK;
-  }
-  if (!c && name && std::string(name) == "cu_mask_streams") {  // ... the kind of their batch / reduce streams
+  const std::string k(name ? name : "");
+  if (!c && k == "reduce_spin_us") return set_reduce_spin(&g_reduce_spin_us, value);  // of contexts created later
+  if (!c && k == "cu_mask_streams") {  // ... the kind of their batch / reduce streams
     g_cu_mask_streams = value != 0.0;
     return KDPT_OK;
   }
-  if (!c && name && std::string(name) == "cluster_chord") {  // ... and their big-leaf cluster grouping
+  if (!c && k == "cluster_chord") {  // ... and their big-leaf cluster grouping
     if (!(value >= -1.0 && value <= 4.0)) return fail(KDPT_ERR_ARG, "cluster_chord must be in [-1, 4]");
     g_cluster_chord = value;
     return KDPT_OK;
   }
   if (!c || !name) return fail(KDPT_ERR_ARG, "null arg");
-  if (std::string(name) == "cast_chunk") {  // kdpt_cast_rays' chunk; its buffers are remade by the next call
+  if (k == "cast_chunk") {  // kdpt_cast_rays' chunk; its buffers are remade by the next call
     if (!(value >= 64.0 && value <= (double)(1 << 26))) return fail(KDPT_ERR_ARG, "cast_chunk must be in 64 .. 2^26");
     c->cast_chunk = (int)value;
     return KDPT_OK;
@@ -909,8 +1007,9 @@ int kdpt_set_tuning(kdpt_ctx* c, const char* name, double value) {
     if (rc) return rc;
     drop_groups(c);
   }
-  const std::string k(name);
   const int v = (int)value;
+  bool route = false;  // the knob can change the intersect kernel's route: setup_trace again
+  bool cull = false;   // ... and before that, which one-level cull it runs
   if (k == "shade_fused") {
     c->no_fuse = v == 0;
   } else if (k == "early_walk") {
@@ -933,71 +1032,70 @@ int kdpt_set_tuning(kdpt_ctx* c, const char* name, double value) {
     c->S.flat_obb = v != 0;
   } else if (k == "super_slab") {
     c->S.sup_slab = v != 0;
-  } else if (k == "tree_format" || k == "tree_global" || k == "super_cull" || k == "cluster_slab") {
-    if (k == "tree_format") {
-      if (v != 0 && v != 16 && v != 32) return fail(KDPT_ERR_ARG, "tree_format must be 0 (best), 16 or 32");
-      c->tree_format = v;
-    } else if (k == "super_cull") {
-      c->super_cull = v != 0;
-    } else if (k == "cluster_slab") {
-      c->S.cl_slab = v != 0;
-      return KDPT_OK;
-    } else {
-      c->force_global_tree = v != 0;
+  } else if (k == "cluster_slab") {
+    c->S.cl_slab = v != 0;
+  } else if (k == "tree_format") {
+    if (v != 0 && v != 16 && v != 32) return fail(KDPT_ERR_ARG, "tree_format must be 0 (best), 16 or 32");
+    c->tree_format = v;
+    route = true;
+  } else if (k == "super_cull") {
+    c->super_cull = v != 0;
+    route = true;
+  } else if (k == "tree_global") {
+    c->force_global_tree = v != 0;
+    route = true;
+  } else if (k == "cluster_cull") {
+    // 0: no cluster / chunk cull at all (every big-leaf cluster swept: exact by construction, whatever the
+    // scene's margin); 1: the scene's margins (and masks)
+    c->cull_scene = v != 0;
+    if (v != 0) set_cull(c, c->cull);
+    else fix_cull(c, __builtin_inff());
+    cull = true;
+  } else if (k == "cull_margin") {
+    // > 0: one fixed margin coefficient for every level (no masks: not exact in general); 0: the scene's
+    if (!(value >= 0.0)) return fail(KDPT_ERR_ARG, "cull_margin must be >= 0 (0: the scene's)");
+    c->cull_scene = value == 0.0;
+    if (value > 0.0) fix_cull(c, (float)value);
+    else set_cull(c, c->cull);
+    cull = true;
+  } else if (k == "cull_exact") {
+    // 0: the fast-margin one-level cull instead of the masked exact one (A/B; not exact for such scenes)
+    c->cull_exact = v != 0;
+    cull = true;
+  } else if (k == "cull_fast_k") {
+    // the masked cull's box coefficient (default CULL_MARGIN_MASKED), its direction masks rebuilt for it: a
+    // wider box sweeps more clusters, a narrower one leaves more danger triangles to decide
+    if (!(value > 0.0 && value < 1.0)) return fail(KDPT_ERR_ARG, "cull_fast_k must be in (0, 1)");
+    if (!c->mask_cs) return fail(KDPT_ERR_ARG, "cull_fast_k: this scene has no direction masks");
+    const CullMargin before = c->cull;
+    c->cull.K = c->cull.K_lo = (float)value;
+    if (c->cull_scene) set_cull(c, c->cull);
+    int rc = build_masks(c, c->mask_n);
+    if (rc) {  // the masks are still the old coefficient's: so is the margin again
+      c->cull = before;
+      if (c->cull_scene) set_cull(c, before);
+      return rc;
     }
-    const double frac = (double)c->trace_grid / std::max(1, c->full_trace_grid);
-    int rc = setup_trace(c);
+    cull = true;
+  } else if (k == "cull_mask_n") {
+    if (v < 1 || v > 512) return fail(KDPT_ERR_ARG, "cull_mask_n must be in 1 .. 512");
+    if (!c->mask_cs) return fail(KDPT_ERR_ARG, "cull_mask_n: this scene has no direction masks");
+    int rc = build_masks(c, v);
     if (rc) return rc;
-    if (c->grid_env) c->trace_grid = std::max(1, (int)(c->full_trace_grid * frac));
-  } else if (k == "cluster_cull" || k == "cull_margin" || k == "cull_exact" || k == "cull_mask_n" ||
-             k == "cull_fast_k") {
-    if (k == "cluster_cull") {
-      // 0: no cluster / chunk cull at all (every big-leaf cluster swept: exact by construction, whatever the
-      // scene's margin); 1: the scene's margins (and masks)
-      c->cull_scene = v != 0;
-      if (v != 0) set_cull(c, c->cull);
-      else fix_cull(c, __builtin_inff());
-    } else if (k == "cull_margin") {
-      // > 0: one fixed margin coefficient for every level (no masks: not exact in general); 0: the scene's
-      if (!(value >= 0.0)) return fail(KDPT_ERR_ARG, "cull_margin must be >= 0 (0: the scene's)");
-      c->cull_scene = value == 0.0;
-      if (value > 0.0) fix_cull(c, (float)value);
-      else set_cull(c, c->cull);
-    } else if (k == "cull_exact") {
-      // 0: the fast-margin one-level cull instead of the masked exact one (A/B; not exact for such scenes)
-      c->cull_exact = v != 0;
-    } else if (k == "cull_fast_k") {
-      // the masked cull's box coefficient (default CULL_MARGIN_MASKED), its direction masks rebuilt for it: a
-      // wider box sweeps more clusters, a narrower one leaves more danger triangles to decide
-      if (!(value > 0.0 && value < 1.0)) return fail(KDPT_ERR_ARG, "cull_fast_k must be in (0, 1)");
-      if (!c->mask_cs) return fail(KDPT_ERR_ARG, "cull_fast_k: this scene has no direction masks");
-      c->cull.K = c->cull.K_lo = (float)value;
-      if (c->cull_scene) set_cull(c, c->cull);
-      int rc = build_masks(c, c->mask_n);
-      if (rc) return rc;
-    } else {
-      if (v < 1 || v > 512) return fail(KDPT_ERR_ARG, "cull_mask_n must be in 1 .. 512");
-      if (!c->mask_cs) return fail(KDPT_ERR_ARG, "cull_mask_n: this scene has no direction masks");
-      int rc = build_masks(c, v);
-      if (rc) return rc;
-    }
-    apply_cull_route(c);
-    const double frac = (double)c->trace_grid / std::max(1, c->full_trace_grid);
-    int rc = setup_trace(c);  // the route may change (no super-cluster route under the masked cull)
-    if (rc) return rc;
-    if (c->grid_env) c->trace_grid = std::max(1, (int)(c->full_trace_grid * frac));
+    cull = true;
   } else if (k == "profile_batches") {
     c->profile_batches = v != 0;
     c->profile_steps = v >= 2;
   } else if (k == "sync_debug") {
     c->sync_debug = v != 0;
   } else if (k == "reduce_spin_us") {
-    if (!(value >= 0.0 && value <= 1e6)) return fail(KDPT_ERR_ARG, "reduce_spin_us must be in [0, 1e6]");
-    c->reduce_spin_us = value;
+    return set_reduce_spin(&c->reduce_spin_us, value);
   } else {
     return fail(KDPT_ERR_ARG, "unknown tuning knob " + k);
   }
-  return KDPT_OK;
+  // (the route may change with the cull too: no super-cluster route under the masked cull)
+  if (cull) apply_cull_route(c);
+  return (cull || route) ? resetup_trace(c) : KDPT_OK;
 }
 
 int kdpt_reset(kdpt_ctx* c) {
@@ -1086,9 +1184,9 @@ int enqueue_iterations(kdpt_ctx* c, int first_iter, int count, int stride, int p
   if (c->shade_oob) return refuse_shading();
   const int depth = std::min(16, std::max(1, pipeline));
   const int B = std::min(MAXB, std::max(1, batch));
-  // the first add follows everything already queued on the context's own stream (reset, ...)
-  hipEvent_t entry;
-  HIP_TRY(hipEventCreateWithFlags(&entry, hipEventDisableTiming));
+  // the first add follows everything already queued on the context's own stream (reset, ...); a wait of an
+  // earlier call that is still queued keeps the record it was queued after
+  const hipEvent_t entry = c->entry_ev;
   HIP_TRY(hipEventRecord(entry, c->stream));
   // `depth` groups of B iteration states; a group runs one batch at a time on its stream
   if ((int)c->groups.size() < depth || c->group_batch != B) {
@@ -1172,7 +1270,6 @@ int enqueue_iterations(kdpt_ctx* c, int first_iter, int count, int stride, int p
     HIP_TRY(hipEventRecord(grp.acc_ev, st));
     c->acc_last = grp.acc_ev;
   }
-  HIP_TRY(hipEventDestroy(entry));
   c->stats.iterations += count;
   return KDPT_OK;
 }
@@ -1198,8 +1295,7 @@ int kdpt_trace_config(kdpt_ctx* c, int* tree_mode, int* block, int* grid, long l
   if (!c) return fail(KDPT_ERR_ARG, "null ctx");
   const int m = c->tree_mode;
   if (tree_mode) *tree_mode = m;
-  if (block)
-    *block = m == TREE_LDS ? trace_block<TREE_LDS>() : (m >= TREE_LDS16 ? trace_block<TREE_LDS16>() : trace_block<TREE_PACKED>());
+  if (block) *block = trace_kernel(false, false, m).block;
   if (grid) *grid = c->full_trace_grid;
   if (lds_bytes) *lds_bytes = (long long)c->tree_lds;
   return KDPT_OK;
@@ -1349,6 +1445,7 @@ int kdpt_destroy(kdpt_ctx* c) {
   for (auto e : c->cast_ev)
     if (e) (void)hipEventDestroy(e);
   free_iter(&c->solo);
+  if (c->entry_ev) (void)hipEventDestroy(c->entry_ev);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return KDPT_OK;
@@ -1538,40 +1635,193 @@ int kdpt_selftest_fresnel(const float* cs, int n, float ior, float* f) {
 
 namespace {
 
-template <bool HYBRID, bool COUNT>
-void launch_trace_mode(kdpt_ctx* c, const TraceArgs& a, int grid, hipStream_t st) {
-  const dim3 g(grid);
-  if (c->tree_mode == TREE_LDS)
-    hipLaunchKernelGGL((k_trace<HYBRID, COUNT, TREE_LDS>), g, dim3(trace_block<TREE_LDS>()), c->tree_lds, st, a);
-  else if (c->tree_mode == TREE_LDS16)
-    hipLaunchKernelGGL((k_trace<HYBRID, COUNT, TREE_LDS16>), g, dim3(trace_block<TREE_LDS16>()), c->tree_lds, st, a);
-  else if (c->tree_mode == TREE_LDS16G)
-    hipLaunchKernelGGL((k_trace<HYBRID, COUNT, TREE_LDS16G>), g, dim3(trace_block<TREE_LDS16G>()), c->tree_lds, st, a);
-  else if (c->tree_mode == TREE_LDS16S)
-    hipLaunchKernelGGL((k_trace<HYBRID, COUNT, TREE_LDS16S>), g, dim3(trace_block<TREE_LDS16S>()), c->tree_lds, st, a);
-  else if (c->tree_mode == TREE_PACKED)
-    hipLaunchKernelGGL((k_trace<HYBRID, COUNT, TREE_PACKED>), g, dim3(trace_block<TREE_PACKED>()), 0, st, a);
-  else
-    hipLaunchKernelGGL((k_trace<HYBRID, COUNT, TREE_WIDE>), g, dim3(trace_block<TREE_WIDE>()), 0, st, a);
-}
-
-// grid: the launch's persistent workgroups (c->trace_grid, or a pipelined call's share of it)
+// grid: the launch's persistent workgroups (c->trace_grid, or a pipelined call's share of it); tree_lds is 0 on
+// the routes that read the tree from HBM
 void launch_trace(kdpt_ctx* c, const TraceArgs& a, bool count, int grid, hipStream_t st) {
-  const bool hyb = c->opt.short_stack != 0;
-  if (hyb) { if (count) launch_trace_mode<true, true>(c, a, grid, st); else launch_trace_mode<true, false>(c, a, grid, st); }
-  else { if (count) launch_trace_mode<false, true>(c, a, grid, st); else launch_trace_mode<false, false>(c, a, grid, st); }
+  const TraceKernel k = trace_kernel(c->opt.short_stack != 0, count, c->tree_mode);
+  hipLaunchKernelGGL(k.fn, dim3(grid), dim3(k.block), c->tree_lds, st, a);
 }
 
-template <bool HYBRID>
-void launch_shade_h(kdpt_ctx* c, const ShadeArgs& a, bool compact, bool sort, hipStream_t st) {
-  const dim3 g(c->ntiles), b(TILE);
-  if (compact) {
-    if (sort) hipLaunchKernelGGL((k_shade<HYBRID, true, true>), g, b, 0, st, a);
-    else hipLaunchKernelGGL((k_shade<HYBRID, true, false>), g, b, 0, st, a);
-  } else {
-    if (sort) hipLaunchKernelGGL((k_shade<HYBRID, false, true>), g, b, 0, st, a);
-    else hipLaunchKernelGGL((k_shade<HYBRID, false, false>), g, b, 0, st, a);
+// The fault word is the one per-iteration member of DevScene: the batch-wide launches (camera rays + geoms,
+// k_geoms, k_trace) report into the first state's word (Batch::S0), each iteration's own launches into its own.
+DevScene scene_of(const kdpt_ctx* c, const IterState* it) {
+  DevScene S = c->S;
+  S.fault = it->fault;
+  return S;
+}
+
+// What stays the same over a launch_batch call: its arguments and what follows from them and the context.
+struct Batch {
+  kdpt_ctx* c;
+  IterState* const* its;
+  const int* iters;
+  int nb;
+  hipStream_t st;
+  int trace_grid;
+  bool count;
+  DevScene S0;      // scene_of the first state
+  bool gen_geoms;   // camera rays and bounce 0's analytic geoms + root-box test in one launch (not for the
+                    // brute-force and box-view intersect kernels, which have no first part)
+  bool compact;
+  ShadeArgs shade;  // the shading arguments that neither the bounce nor the iteration changes
+};
+
+// The batch's camera rays in one launch (blockIdx.y = iteration), with bounce 0's geoms stage when gen_geoms.
+int camera_stage(const Batch& B) {
+  kdpt_ctx* c = B.c;
+  // (ncounts, nwork, nlb: the lengths of the counters, work counters and look-back records the launch zeroes)
+  GenBatch gb{{}, c->cam, c->traceDepth, c->opt.antialias, c->cap + 2, c->cap, c->cap * c->ntiles,
+              c->opt.focal_length, c->opt.dof_angle};
+  for (int b = 0; b < B.nb; b++) {
+    B.its[b]->cur = 0;
+    gb.it[b] = B.its[b]->gen_iter(c->opt.cacherays ? 1 : B.iters[b]);
   }
+  if (B.gen_geoms) {
+    GenGeomsBatch gg{gb, B.S0, {}, B.count ? c->counters : nullptr};
+    for (int b = 0; b < B.nb; b++) gg.it[b] = B.its[b]->gen_geoms_iter();
+    hipLaunchKernelGGL(k_gen_geoms_b, dim3((c->npix + GEN_BLOCK - 1) / GEN_BLOCK, B.nb), dim3(GEN_BLOCK), 0, B.st,
+                       gg);
+  } else {
+    hipLaunchKernelGGL(k_gen_rays_b, dim3((c->npix + 255) / 256, B.nb), dim3(256), 0, B.st, gb);
+  }
+  HIP_TRY(hipGetLastError());
+  return KDPT_OK;
+}
+
+// enable_kd = 0: one k_brute launch per iteration.
+int brute_stage(const Batch& B, int depth) {
+  kdpt_ctx* c = B.c;
+  const BruteKernel kernel = brute_kernel(c->opt.use_bbox != 0, B.count);
+  for (int b = 0; b < B.nb; b++) {
+    IterState* it = B.its[b];
+    const BruteArgs ba{scene_of(c, it), it->buf[it->cur], it->counts, depth, it->hits, c->shapes, c->num_shapes,
+                       c->chunk_lo, c->chunk_hi, c->counters, B.its[0]->trace_t};
+    hipLaunchKernelGGL(kernel, dim3(c->ntiles), dim3(TILE), 0, B.st, ba);
+    HIP_TRY(hipGetLastError());
+    if (c->sync_debug) {
+      BruteShape h0;
+      HIP_TRY(hipStreamSynchronize(B.st));  // (the null-stream copy below does not order after st)
+      HIP_TRY(hipMemcpy(&h0, c->shapes, sizeof h0, hipMemcpyDeviceToHost));
+      fprintf(stderr, "[kdpt] brute depth %d use_bbox %d shapes %d lo %g %g %g hi %g %g %g n %d mat %d\n", depth,
+              c->opt.use_bbox, c->num_shapes, h0.lo.x, h0.lo.y, h0.lo.z, h0.hi.x, h0.hi.y, h0.hi.z, fbits(h0.lo.w),
+              fbits(h0.hi.w));
+    }
+  }
+  return KDPT_OK;
+}
+
+// Bounce `depth`'s intersect kernel: k_viz or k_brute per iteration, else one k_trace over the whole batch,
+// after the intersect stage's first part (k_geoms_b) unless the camera stage (bounce 0 with gen_geoms) or the
+// previous bounce's shading (prep_ready: the hand-off) has done it already.
+int intersect_stage(const Batch& B, int depth, bool prep_ready) {
+  kdpt_ctx* c = B.c;
+  IterState* it0 = B.its[0];
+  if (c->viz) {
+    for (int b = 0; b < B.nb; b++) {
+      IterState* it = B.its[b];
+      hipLaunchKernelGGL(k_viz, dim3(c->ntiles), dim3(TILE), 0, B.st, scene_of(c, it), it->buf[it->cur], it->counts,
+                         depth, it->hits, it0->trace_t);
+      HIP_TRY(hipGetLastError());
+    }
+    return KDPT_OK;
+  }
+  if (c->brute) return brute_stage(B, depth);
+  if (!prep_ready && !(depth == 0 && B.gen_geoms)) {  // the batch's iterations in one launch (blockIdx.y = iteration)
+    GeomsBatch gb{B.S0, {}, depth, B.count ? c->counters : nullptr, it0->trace_t + 2 * c->cap};
+    for (int b = 0; b < B.nb; b++) gb.it[b] = B.its[b]->geoms_iter();
+    hipLaunchKernelGGL(k_geoms_b, dim3((c->npix + GEN_BLOCK - 1) / GEN_BLOCK, B.nb), dim3(GEN_BLOCK), 0, B.st, gb);
+    HIP_TRY(hipGetLastError());
+  }
+  TraceArgs t{B.S0, {}, B.nb, c->profile_steps ? 1 : 0, it0->work, depth, c->counters, it0->trace_t};
+  for (int b = 0; b < MAXB; b++) t.it[b] = B.its[b < B.nb ? b : 0]->trace_iter(depth, B.gen_geoms);
+  launch_trace(c, t, B.count, B.trace_grid, B.st);
+  HIP_TRY(hipGetLastError());
+  return KDPT_OK;
+}
+
+// Iteration b's shading arguments at bounce `depth`: the batch's base, then what the bounce and the state set.
+ShadeArgs shade_args(const Batch& B, int b, int depth, bool prep_next) {
+  const IterState* it = B.its[b];
+  ShadeArgs a = B.shade;
+  a.S.fault = it->fault;
+  a.paths = it->buf[it->cur];
+  a.hits = it->hits;
+  a.image = it->image;
+  a.image_zeroed = it->zero_partial ? 1 : 0;
+  a.counts = it->counts;
+  a.depth = depth;
+  a.iter = B.iters[b];
+  a.tile_counts = it->tile_counts;
+  a.total_segments = it->total_segments;
+  a.trace_total = b == 0 ? B.c->trace_total : nullptr;
+  a.ccount = it->cand_count(depth, B.gen_geoms);
+  a.prep_on = prep_next ? 1 : 0;
+  a.prep = it->prep;
+  a.tile_ccounts = it->tile_ccounts;
+  return a;
+}
+
+// The three-kernel route of one iteration (iteration 2's sort, "shade_fused" = 0, compaction = 0): k_shade, then
+// k_scan + k_scatter into the other path buffer, or with neither compaction nor sort the live count copied on.
+int shade_scan_scatter(const Batch& B, IterState* it, const ShadeArgs& a, bool sort, bool prep_next) {
+  kdpt_ctx* c = B.c;
+  const int depth = a.depth;
+  hipLaunchKernelGGL(shade_kernel(hybrid_shading(c), B.compact, sort), dim3(c->ntiles), dim3(TILE), 0, B.st, a);
+  HIP_TRY(hipGetLastError());
+  if (!B.compact && !sort) {  // the live range stays the whole image
+    HIP_TRY(hipMemcpyAsync(it->counts + depth + 1, it->counts + depth, sizeof(int), hipMemcpyDeviceToDevice, B.st));
+    return KDPT_OK;
+  }
+  // survivors' offsets + the next bounce's path count; with the hand-off also the candidate-list
+  // offsets per tile + the next bounce's candidate count (a second workgroup)
+  const ScanJob j0{it->tile_counts, it->tile_off, sort ? c->nkeys : 1, it->counts + depth + 1};
+  const ScanJob j1{it->tile_ccounts, it->tile_coff, 1, it->ccount + depth + 1};
+  hipLaunchKernelGGL(k_scan, dim3(prep_next ? 2 : 1), dim3(SCAN_TB), 0, B.st, j0, j1, it->counts, depth, c->ntiles);
+  HIP_TRY(hipGetLastError());
+  const auto scatter = sort ? k_scatter<true> : k_scatter<false>;
+  hipLaunchKernelGGL(scatter, dim3(c->ntiles), dim3(TILE), 0, B.st, it->buf[it->cur], it->buf[it->cur ^ 1],
+                     it->tile_off, it->counts, depth, c->ntiles, B.compact ? 1 : 0, it->scatter_prep(prep_next));
+  HIP_TRY(hipGetLastError());
+  it->cur ^= 1;
+  return KDPT_OK;
+}
+
+// Bounce `depth`'s shading of every iteration: the single pass (k_shade_fused: shading, compaction into the other
+// buffer and the hand-off), the batch's in one launch unless "shade_batch" = 0; the three-kernel route for
+// iteration 2, "shade_fused" = 0 and compaction = 0.
+int shade_stage(const Batch& B, int depth, bool prep_next) {
+  kdpt_ctx* c = B.c;
+  const bool hyb = hybrid_shading(c);
+  const bool stage = c->S.num_geoms + c->S.num_boxes <= ORDERED_GEOMS && c->S.num_materials <= STAGE_MATS;
+  const int shade_grid = (c->npix + SHADE_TB - 1) / SHADE_TB;
+  ShadeBatch sbatch;
+  int nfused = 0;
+  for (int b = 0; b < B.nb; b++) {
+    IterState* it = B.its[b];
+    const bool sort = (B.iters[b] == 2);
+    const ShadeArgs a = shade_args(B, b, depth, prep_next);
+    if (!B.compact || sort || c->no_fuse) {
+      int rc = shade_scan_scatter(B, it, a, sort, prep_next);
+      if (rc) return rc;
+      continue;
+    }
+    const FuseArgs f = it->fuse_args();
+    if (c->shade_batch) {  // launched below, with the batch's other fused iterations
+      sbatch.a[nfused] = a;
+      sbatch.f[nfused] = f;
+      nfused++;
+    } else {
+      hipLaunchKernelGGL(shade_fused_kernel(hyb, stage), dim3(shade_grid), dim3(SHADE_TB), 0, B.st, a, f);
+      HIP_TRY(hipGetLastError());
+    }
+    it->cur ^= 1;
+  }
+  if (nfused) {
+    hipLaunchKernelGGL(shade_fused_batch_kernel(hyb, stage), dim3(shade_grid, nfused), dim3(SHADE_TB), 0, B.st,
+                       sbatch);
+    HIP_TRY(hipGetLastError());
+  }
+  return KDPT_OK;
 }
 
 // One iteration in each state of its (nb <= MAXB), with the context's scene, options and knobs, in lockstep on
@@ -1581,228 +1831,35 @@ void launch_shade_h(kdpt_ctx* c, const ShadeArgs& a, bool compact, bool sort, hi
 int launch_batch(kdpt_ctx* c, IterState* const* its, const int* iters, int nb, hipStream_t st, int trace_grid,
                  int stop_depth, bool count, std::vector<hipEvent_t>* bev) {
   if (c->shade_oob) return refuse_shading();
-  IterState* it0 = its[0];
-  // The fault word is the one per-iteration member of DevScene: the batch-wide launches (camera rays + geoms,
-  // k_geoms, k_trace) report into the first state's word, each iteration's own launches into its own.
-  auto scene_of = [c](const IterState* it) {
-    DevScene S = c->S;
-    S.fault = it->fault;
-    return S;
-  };
-  const DevScene S0 = scene_of(it0);
-  // camera rays and bounce 0's analytic geoms + root-box test in one launch (not for the brute-force and box-view
-  // intersect kernels, which have no first part)
-  const bool gen_geoms = c->gen_geoms && !c->brute && !c->viz;
-  {  // the batch's camera rays in one launch (blockIdx.y = iteration)
-    GenBatch gb;
-    gb.cam = c->cam;
-    gb.traceDepth = c->traceDepth;
-    gb.focalLength = c->opt.focal_length;
-    gb.dofAngle = c->opt.dof_angle;
-    gb.antialias = c->opt.antialias;
-    gb.ncounts = c->cap + 2;
-    gb.nwork = c->cap;
-    gb.nlb = c->cap * c->ntiles;
-    for (int b = 0; b < nb; b++) {
-      IterState* it = its[b];
-      it->cur = 0;
-      gb.it[b] = GenIter{c->opt.cacherays ? 1 : iters[b], it->buf[0], it->counts, it->work, it->trace_t, it->lb,
-                         it->zero_partial ? it->image : nullptr};
-    }
-    if (gen_geoms) {
-      GenGeomsBatch gg;
-      gg.g = gb;
-      gg.S = S0;
-      gg.count_aabb = count ? c->counters : nullptr;
-      for (int b = 0; b < nb; b++) {
-        IterState* it = its[b];
-        it->cc0_cur = it->ccount0 + it->gen_parity;
-        gg.it[b] = GenGeomsIter{it->cc0_cur, it->ccount0 + (it->gen_parity ^ 1), it->cray, it->hits, it->cand};
-        it->gen_parity ^= 1;
-      }
-      hipLaunchKernelGGL(k_gen_geoms_b, dim3((c->npix + GEN_BLOCK - 1) / GEN_BLOCK, nb), dim3(GEN_BLOCK), 0, st,
-                         gg);
-    } else {
-      hipLaunchKernelGGL(k_gen_rays_b, dim3((c->npix + 255) / 256, nb), dim3(256), 0, st, gb);
-    }
-    HIP_TRY(hipGetLastError());
-  }
-  const bool compact = c->opt.compaction != 0;
-  bool prep_ready = false;  // this bounce's intersect-stage first part came with the previous scatter
+  const bool kd = !c->brute && !c->viz;
+  Batch B{c, its, iters, nb, st, trace_grid, count, scene_of(c, its[0]), c->gen_geoms && kd, c->opt.compaction != 0,
+          ShadeArgs{}};
+  B.shade.S = c->S;
+  B.shade.softness = c->opt.softness;
+  B.shade.enable_sss = c->opt.enable_sss;
+  B.shade.tile_kcounts = nullptr;
+  B.shade.ntiles = c->ntiles;
+  B.shade.nkeys = c->nkeys;
+  B.shade.trace_t = its[0]->trace_t;
+  B.shade.gspan = its[0]->trace_t + 2 * c->cap;
+  B.shade.trace_rays = kd ? c->trace_total + 2 : nullptr;
+  B.shade.count_aabb = count ? c->counters : nullptr;
+  int rc = camera_stage(B);
+  if (rc) return rc;
+  const bool timed = c->opt.testing_mode && bev;
+  bool prep_ready = false;  // this bounce's intersect-stage first part came with the previous bounce's shading
   for (int depth = 0; depth < c->cap; depth++) {
-    const bool prep_next = compact && depth + 1 < c->cap && !c->brute && !c->viz;
-    if (c->opt.testing_mode && bev) HIP_TRY(hipEventRecord((*bev)[2 * depth], st));
-    TraceArgs t;
-    t.S = S0;
-    t.nb = nb;
-    t.prof_steps = c->profile_steps ? 1 : 0;
-    for (int b = 0; b < MAXB; b++) {
-      IterState* it = its[b < nb ? b : 0];
-      t.it[b].cand = it->cand;
-      t.it[b].ccount = (depth == 0 && gen_geoms) ? it->cc0_cur : it->ccount;  // indexed by depth (0 here)
-      t.it[b].cray = it->cray;
-      t.it[b].hits = it->hits;
-    }
-    t.work = it0->work;
-    t.depth = depth;
-    t.counters = c->counters;
-    t.trace_t = it0->trace_t;
-    if (c->viz) {
-      for (int b = 0; b < nb; b++) {
-        IterState* it = its[b];
-        hipLaunchKernelGGL(k_viz, dim3(c->ntiles), dim3(TILE), 0, st, scene_of(it), it->buf[it->cur], it->counts, depth,
-                           it->hits, it0->trace_t);
-        HIP_TRY(hipGetLastError());
-      }
-    } else if (c->brute) {
-      for (int b = 0; b < nb; b++) {
-        IterState* it = its[b];
-        BruteArgs ba;
-        ba.S = scene_of(it);
-        ba.paths = it->buf[it->cur];
-        ba.counts = it->counts;
-        ba.depth = depth;
-        ba.hits = it->hits;
-        ba.shapes = c->shapes;
-        ba.num_shapes = c->num_shapes;
-        ba.chunk_lo = c->chunk_lo;
-        ba.chunk_hi = c->chunk_hi;
-        ba.counters = c->counters;
-        ba.trace_t = it0->trace_t;
-        const dim3 g(c->ntiles), bl(TILE);
-        if (c->opt.use_bbox) {
-          if (count) hipLaunchKernelGGL((k_brute<true, true>), g, bl, 0, st, ba);
-          else hipLaunchKernelGGL((k_brute<true, false>), g, bl, 0, st, ba);
-        } else {
-          if (count) hipLaunchKernelGGL((k_brute<false, true>), g, bl, 0, st, ba);
-          else hipLaunchKernelGGL((k_brute<false, false>), g, bl, 0, st, ba);
-        }
-        HIP_TRY(hipGetLastError());
-        if (c->sync_debug) {
-          BruteShape h0;
-          HIP_TRY(hipStreamSynchronize(st));  // (the null-stream copy below does not order after st)
-          HIP_TRY(hipMemcpy(&h0, c->shapes, sizeof h0, hipMemcpyDeviceToHost));
-          fprintf(stderr, "[kdpt] brute depth %d use_bbox %d shapes %d lo %g %g %g hi %g %g %g n %d mat %d\n", depth,
-                  c->opt.use_bbox, c->num_shapes, h0.lo.x, h0.lo.y, h0.lo.z, h0.hi.x, h0.hi.y, h0.hi.z, fbits(h0.lo.w),
-                  fbits(h0.hi.w));
-        }
-      }
-    } else {
-      // the intersect stage's first part: already done by the previous bounce's k_shade/k_scatter when it
-      // ran with the hand-off (prep_ready), else here
-      if (!prep_ready && !(depth == 0 && gen_geoms)) {  // the batch's iterations in one launch (blockIdx.y = iteration)
-        GeomsBatch gb;
-        gb.S = S0;
-        gb.depth = depth;
-        gb.count_aabb = count ? c->counters : nullptr;
-        gb.gspan = it0->trace_t + 2 * c->cap;
-        for (int b = 0; b < nb; b++) {
-          IterState* it = its[b];
-          gb.it[b] = GeomsIter{it->buf[it->cur], it->counts, it->cray, it->hits, it->cand, it->ccount};
-        }
-        hipLaunchKernelGGL(k_geoms_b, dim3((c->npix + GEN_BLOCK - 1) / GEN_BLOCK, nb), dim3(GEN_BLOCK), 0, st, gb);
-        HIP_TRY(hipGetLastError());
-      }
-      launch_trace(c, t, count, trace_grid, st);
-      HIP_TRY(hipGetLastError());
-    }
+    const bool prep_next = B.compact && depth + 1 < c->cap && kd;
+    if (timed) HIP_TRY(hipEventRecord((*bev)[2 * depth], st));
+    if ((rc = intersect_stage(B, depth, prep_ready))) return rc;
     if (c->sync_debug) {
       fprintf(stderr, "[kdpt] trace depth %d launched (grid %d, mode %d, lds %zu, batch %d)\n", depth,
               trace_grid, c->tree_mode, c->tree_lds, nb);
       HIP_TRY(hipStreamSynchronize(st));
       fprintf(stderr, "[kdpt] trace depth %d done\n", depth);
     }
-    if (c->opt.testing_mode && bev) HIP_TRY(hipEventRecord((*bev)[2 * depth + 1], st));
-    ShadeBatch sbatch;
-    int nfused = 0, fused_grid = 0;
-    bool fused_hyb = false, fused_stage = false;
-    for (int b = 0; b < nb; b++) {
-      IterState* it = its[b];
-      const bool sort = (iters[b] == 2);
-      ShadeArgs a;
-      a.S = scene_of(it);
-      a.paths = it->buf[it->cur];
-      a.hits = it->hits;
-      a.image = it->image;
-      a.image_zeroed = it->zero_partial ? 1 : 0;
-      a.counts = it->counts;
-      a.depth = depth;
-      a.iter = iters[b];
-      a.softness = c->opt.softness;
-      a.enable_sss = c->opt.enable_sss;
-      a.tile_counts = it->tile_counts;
-      a.tile_kcounts = nullptr;
-      a.ntiles = c->ntiles;
-      a.nkeys = c->nkeys;
-      a.total_segments = it->total_segments;
-      a.trace_t = it0->trace_t;
-      a.gspan = it0->trace_t + 2 * c->cap;
-      a.trace_total = b == 0 ? c->trace_total : nullptr;
-      a.trace_rays = (c->brute || c->viz) ? nullptr : c->trace_total + 2;
-      a.ccount = (depth == 0 && gen_geoms) ? it->cc0_cur : it->ccount;
-      a.prep_on = prep_next ? 1 : 0;
-      a.prep = it->prep;
-      a.tile_ccounts = it->tile_ccounts;
-      a.count_aabb = count ? c->counters : nullptr;
-      if (compact && !sort && !c->no_fuse) {
-        // single pass: shading, compaction into the other buffer and the hand-off (k_shade_fused)
-        const int nxt = it->cur ^ 1;
-        const FuseArgs f{it->buf[nxt], it->tickets, it->lb, it->counts, it->ccount, it->cray, it->hits, it->cand};
-        const bool stage = c->S.num_geoms + c->S.num_boxes <= ORDERED_GEOMS && c->S.num_materials <= STAGE_MATS;
-        const bool hyb = c->opt.short_stack || c->brute;
-        const int shade_grid = (c->npix + SHADE_TB - 1) / SHADE_TB;
-        if (c->shade_batch) {  // launched below, with the batch's other fused iterations
-          sbatch.a[nfused] = a;
-          sbatch.f[nfused] = f;
-          nfused++;
-          fused_hyb = hyb;
-          fused_stage = stage;
-          fused_grid = shade_grid;
-          it->cur = nxt;
-          continue;
-        }
-        if (hyb && stage) hipLaunchKernelGGL((k_shade_fused<true, true>), dim3(shade_grid), dim3(SHADE_TB), 0, st, a, f);
-        else if (hyb) hipLaunchKernelGGL((k_shade_fused<true, false>), dim3(shade_grid), dim3(SHADE_TB), 0, st, a, f);
-        else if (stage) hipLaunchKernelGGL((k_shade_fused<false, true>), dim3(shade_grid), dim3(SHADE_TB), 0, st, a, f);
-        else hipLaunchKernelGGL((k_shade_fused<false, false>), dim3(shade_grid), dim3(SHADE_TB), 0, st, a, f);
-        HIP_TRY(hipGetLastError());
-        it->cur = nxt;
-        continue;
-      }
-      // hit point offset: 1e-4 for the hybrid traversal and the brute-force kernel, 1e-5 for traverseKDbare
-      if (c->opt.short_stack || c->brute) launch_shade_h<true>(c, a, compact, sort, st);
-      else launch_shade_h<false>(c, a, compact, sort, st);
-      HIP_TRY(hipGetLastError());
-      if (compact || sort) {
-        // survivors' offsets + the next bounce's path count; with the hand-off also the candidate-list
-        // offsets per tile + the next bounce's candidate count (a second workgroup)
-        const ScanJob j0{it->tile_counts, it->tile_off, sort ? c->nkeys : 1, it->counts + depth + 1};
-        const ScanJob j1{it->tile_ccounts, it->tile_coff, 1, it->ccount + depth + 1};
-        hipLaunchKernelGGL(k_scan, dim3(prep_next ? 2 : 1), dim3(SCAN_TB), 0, st, j0, j1, it->counts, depth, c->ntiles);
-        HIP_TRY(hipGetLastError());
-        const int nxt = it->cur ^ 1;
-        ScatterPrep sp{prep_next ? 1 : 0, it->prep, it->cray, it->hits, it->cand, it->tile_coff};
-        if (sort)
-          hipLaunchKernelGGL(k_scatter<true>, dim3(c->ntiles), dim3(TILE), 0, st, it->buf[it->cur], it->buf[nxt],
-                             it->tile_off, it->counts, depth, c->ntiles, compact ? 1 : 0, sp);
-        else
-          hipLaunchKernelGGL(k_scatter<false>, dim3(c->ntiles), dim3(TILE), 0, st, it->buf[it->cur], it->buf[nxt],
-                             it->tile_off, it->counts, depth, c->ntiles, compact ? 1 : 0, sp);
-        HIP_TRY(hipGetLastError());
-        it->cur = nxt;
-      } else {
-        // no compaction, no sort: the live range stays the whole image
-        HIP_TRY(hipMemcpyAsync(it->counts + depth + 1, it->counts + depth, sizeof(int), hipMemcpyDeviceToDevice, st));
-      }
-    }
-    if (nfused) {  // the batch's fused iterations in one launch
-      const dim3 g(fused_grid, nfused), bl(SHADE_TB);
-      if (fused_hyb && fused_stage) hipLaunchKernelGGL((k_shade_fused_b<true, true>), g, bl, 0, st, sbatch);
-      else if (fused_hyb) hipLaunchKernelGGL((k_shade_fused_b<true, false>), g, bl, 0, st, sbatch);
-      else if (fused_stage) hipLaunchKernelGGL((k_shade_fused_b<false, true>), g, bl, 0, st, sbatch);
-      else hipLaunchKernelGGL((k_shade_fused_b<false, false>), g, bl, 0, st, sbatch);
-      HIP_TRY(hipGetLastError());
-    }
+    if (timed) HIP_TRY(hipEventRecord((*bev)[2 * depth + 1], st));
+    if ((rc = shade_stage(B, depth, prep_next))) return rc;
     if (c->sync_debug) {
       HIP_TRY(hipStreamSynchronize(st));
       fprintf(stderr, "[kdpt] shade depth %d done\n", depth);
@@ -1810,7 +1867,7 @@ int launch_batch(kdpt_ctx* c, IterState* const* its, const int* iters, int nb, h
     if (stop_depth == depth) return KDPT_OK;
     prep_ready = prep_next;
   }
-  if (!compact) {
+  if (!B.compact) {
     for (int b = 0; b < nb; b++) {
       IterState* it = its[b];
       hipLaunchKernelGGL(k_final_gather, dim3((c->npix + 255) / 256), dim3(256), 0, st, it->buf[it->cur], it->counts,
@@ -2281,15 +2338,10 @@ int kdpt_cast_rays(kdpt_ctx* c, const float* origins, const float* directions, l
   a.cand = c->cast_cand;
   a.cnt = c->cast_cnt;
   a.tt = c->cast_tt;
-  TraceArgs t;
-  t.S = c->S;
-  t.nb = 1;
-  t.prof_steps = 0;
-  for (int b = 0; b < MAXB; b++) t.it[b] = TraceIter{c->cast_cand, c->cast_cnt + 1, c->cast_cray, c->cast_hits};
-  t.work = c->cast_cnt;
-  t.depth = 0;
-  t.counters = c->counters;
-  t.trace_t = c->cast_tt;
+  // (one "iteration" at bounce 0: the query's own queue, its length in cast_cnt[1], the chunk counter in [0])
+  TraceArgs t{c->S, {}, 1, 0, c->cast_cnt, 0, c->counters, c->cast_tt};
+  std::fill_n(t.it, MAXB, TraceIter{c->cast_cand, c->cast_cnt + 1, c->cast_cray, c->cast_hits});
+  void (*const resolve)(CastArgs) = hybrid_shading(c) ? k_cast_resolve<true> : k_cast_resolve<false>;
   for (long long off = 0; off < n; off += chunk) {
     const int m = (int)std::min<long long>(chunk, n - off);
     a.n = m;
@@ -2309,8 +2361,7 @@ int kdpt_cast_rays(kdpt_ctx* c, const float* origins, const float* directions, l
     HIP_TRY(hipGetLastError());
     launch_trace(c, t, false, c->trace_grid, st);
     HIP_TRY(hipGetLastError());
-    if (c->opt.short_stack) hipLaunchKernelGGL(k_cast_resolve<true>, dim3((m + 255) / 256), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_cast_resolve<false>, dim3((m + 255) / 256), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(resolve, dim3((m + 255) / 256), dim3(256), 0, st, a);
     HIP_TRY(hipGetLastError());
     if (!out_dev)
       HIP_TRY(hipMemcpyAsync(out + off, c->cast_out, sizeof(kdpt_ray_hit) * (size_t)m, hipMemcpyDeviceToHost, st));

@@ -189,6 +189,36 @@ def test_soup_counters_match_oracle(kdpt, oracle, soup):
     assert st.tri_hits > 1000 and st.tri_tests > st.segments  # (measured hits: 6 337 and 6 720)
 
 
+# the counting intersect kernel (k_trace<.., COUNT = true, ..>) on the routes the two tests above do not take:
+# (soup, knobs, WANT_TREE tag)
+COUNT_ROUTES = [("rootleaf8200", {"tree_global": 1}, "tree_global"),
+                ("rootleaf8200", {"tree_format": 16}, "tree_format16"), ("syn20000", {}, ""),
+                ("growth", {"tree_format": 32}, "tree_format32"), ("growth", {"tree_format": 16}, "tree_format16")]
+_oracle_counts = {}
+
+
+@pytest.mark.parametrize("short_stack", [1, 0], ids=["hybrid", "bare"])
+@pytest.mark.parametrize("route", COUNT_ROUTES, ids=["-".join([r[0], r[2] or "default"]) for r in COUNT_ROUTES])
+def test_soup_counters_on_every_route(kdpt, oracle, route, short_stack):
+    """Iteration 1's AABB tests, triangle tests and hits at 40 x 24, depth 8, are the oracle's on the hbm-64B, hbm-32B,
+    lds-32B and lds-16B routes too, on both walks: the counters do not depend on where the tree is read from."""
+    soup, knobs, tag = route
+    desc = soups.soup_scene(soup, res=(40, 24), depth=8)
+    with kdpt.PathTracer(kdpt.SceneData.from_description(desc), kdpt.default_options(short_stack=short_stack)) as pt:
+        for k, v in knobs.items():
+            pt.set_tuning(k, v)
+        tree = pt.trace_config()["tree"]
+        got = pt.count_iteration(1)
+    if (soup, short_stack) not in _oracle_counts:
+        _, st = oracle.OracleScene.from_description(desc).render(1, 1, shortstack=short_stack)
+        _oracle_counts[(soup, short_stack)] = (st.aabb_tests, st.tri_tests, st.tri_hits)
+    want = _oracle_counts[(soup, short_stack)]
+    print(f"counters {soup} short_stack={short_stack} {knobs} on {tree}: {got} (oracle {want})")
+    assert tree in WANT_TREE[(soup, tag)], (soup, knobs, tree)
+    assert got == want
+    assert want[2] > 0
+
+
 def test_shading_past_the_materials_is_refused(kdpt, oracle):
     """`coincident` has three shapes.  The KD traversal reports material mtlIdx + num_materials - 1 for a triangle
     hit (src/pathtrace.cu:1142): 7, 8 and 9 here, in a materials array of 8.  The ray query only reports the
