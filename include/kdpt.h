@@ -374,6 +374,58 @@ int kdpt_cast_rays(kdpt_ctx *ctx, const float *origins, const float *directions,
  * launches and staging copies on the context's stream). */
 int kdpt_cast_stats(kdpt_ctx *ctx, long long *rays, long long *traced, double *device_ms);
 
+/* ---- Caller-defined views: set the camera, read its rays, or path trace rays of your own ----
+ * kdpt_set_camera replaces the pinhole camera the context was created with, from the next enqueued iteration
+ * on (launches take the camera by value, so iterations already queued keep theirs; no device work, no
+ * synchronisation).  The accumulation image, kdpt_stats and the iteration counter are kept, as kdpt_set_options
+ * keeps them: kdpt_reset clears them.  camera->resolution must equal the context's (everything sized by W*H
+ * stays) and every float must be finite; anything else is KDPT_ERR_ARG and the old camera stays.
+ *
+ * kdpt_camera_rays returns the W*H rays generateRayFromCamera (src/pathtrace.cu:315-397) produces for iteration
+ * `iter` (>= 1) with the context's current camera and options (antialias, dof_angle, focal_length; with
+ * cacherays, iteration 1's rays whatever `iter`), as the device computes them: 3*W*H floats each, ray
+ * y*W + x at [3 (y*W + x)].  Each output may be host memory or memory of the context's device.  Synchronous;
+ * the render state is left alone.
+ *
+ * kdpt_trace_rays path traces n caller-supplied rays.  For each iteration first_iter + k (k < count) it runs
+ * what kdpt_trace_iteration runs with the camera stage replaced: path i starts as {origins[i], directions[i],
+ * colour (1, 1, 1), pixelIndex i, remainingBounces traceDepth}, there are n paths instead of W*H, and everything
+ * after that is the context's own pipeline -- its options (compaction, iteration 2's sort, softness, SSS,
+ * short_stack, bounce_cap), its tree route, cull and knobs, and the RNG seeds (iteration, slot, depth) as they
+ * fall.  The result is the reference's render of an n-pixel image whose camera had produced these rays: fed
+ * kdpt_camera_rays' output, it reproduces kdpt_trace_iteration's image bit for bit.  radiance (3*n floats, host
+ * or device memory) is overwritten with the sum over the iterations, in iteration order, of what the gathers add
+ * to pixel i.
+ *
+ * n <= W*H of the context, else KDPT_ERR_ARG: the path buffers hold W*H paths, and the shading seeds its RNG
+ * with a path's compacted slot, so tracing more rays in chunks would not give the result of tracing them
+ * together.  A caller who needs more rays per call creates a context of a larger resolution.  n == 0 or
+ * count == 0 returns KDPT_OK and touches nothing; n < 0, count < 0, first_iter < 1, a null pointer with work to
+ * do or an unknown flag bit is KDPT_ERR_ARG, reported before any device call.
+ *
+ * flags: KDPT_CAST_NORMALIZE, with kdpt_cast_rays' meaning, and without it the same acceptance rule
+ * (|dot(d, d) - 1| <= 1e-6 in float, finite components; kdpt_camera_rays' directions pass it).  A rejected ray
+ * is never traced: its path is born finished with a NaN colour, which the gather adds, so its radiance is NaN in
+ * all three channels (the analogue of KDPT_HIT_INVALID); the other rays' results do not depend on it when
+ * compaction is off, and with compaction on only through the slots the survivors are compacted into.
+ *
+ * Supported wherever kdpt_trace_iteration is (KD hybrid and bare walks, enable_kd = 0, viz_kd = 1), with the
+ * same KDPT_ERR_UNSUPPORTED refusal.  Synchronous, as kdpt_cast_rays is: waits for the work queued on the
+ * context, runs on the context's stream, and returns with radiance filled.  The accumulation image, kdpt_stats
+ * (total_segments, total_trace_rays and the intersect totals included), the iteration counter, the pipeline
+ * slots and kdpt_cast_rays' buffers are left alone: the query has an iteration state of its own, allocated on
+ * first use.  As in a render with compaction = 0, iteration 2's sort orders finished paths by the material id
+ * their slot last held, which for a query is what the query state's previous use left there. */
+int kdpt_set_camera(kdpt_ctx *ctx, const kdpt_camera *camera);
+int kdpt_camera_rays(kdpt_ctx *ctx, int iter, float *origins, float *directions);
+int kdpt_trace_rays(kdpt_ctx *ctx, const float *origins, const float *directions, long long n,
+                    int first_iter, int count, int flags, float *radiance);
+/* Of the last kdpt_trace_rays on the context (the query's own totals; kdpt_stats never sees them): the path
+ * segments launched into the intersect stage summed over its iterations (kdpt_stats.total_segments' meaning),
+ * those of them handed to the KD traversal kernel (total_trace_rays' meaning), and the call's time on the device
+ * (hipEvents on the context's stream, from the zeroing of the radiance buffer to the copy out of it). */
+int kdpt_trace_rays_stats(kdpt_ctx *ctx, long long *segments, long long *traced, double *device_ms);
+
 int kdpt_destroy(kdpt_ctx *ctx);
 const char *kdpt_last_error(void);
 

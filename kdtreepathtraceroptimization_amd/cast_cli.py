@@ -10,6 +10,11 @@ field) and writes BASE.depth.npy (H x W float32, t; -1 where nothing is hit), BA
 BASE.prim.npy (H x W x 2 int32: kind, prim).  Rows are in the path tracer's pixel order (index = y W + x; the
 saved PNGs are that image flipped in x).  One JSON line reports the counts and the rate.
 
+With --radiance SPP the rays are path traced instead (kdpt_trace_rays, iterations 1 .. SPP): --rays writes the mean
+radiance (n x 3 float32; n at most the context's W H, which --res sets) to --out, and --camera traces the rays the
+device itself generates for each iteration (kdpt_camera_rays: jitter and depth of field included) and writes
+BASE.radiance.npy (H x W x 3), the render's image divided by SPP.  A rejected ray's radiance is NaN.
+
 Directions are normalised with the reference's glm::normalize unless --no-normalize is given; then a direction
 that is not unit length (|dot(d, d) - 1| > 1e-6) is rejected, like any ray with a non-finite component (kind -1).
 """
@@ -58,10 +63,43 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--res", type=int, nargs=2, default=None, metavar=("W", "H"), help="camera resolution override")
     ap.add_argument("--bare", action="store_true", help="traverseKDbare instead of the short-stack hybrid")
     ap.add_argument("--no-normalize", action="store_true", help="directions are unit length already")
+    ap.add_argument("--radiance", type=int, default=None, metavar="SPP",
+                    help="path trace the rays instead (kdpt_trace_rays): mean radiance over SPP iterations, written "
+                         "as float32 .npy -- n x 3 to --out with --rays (n <= W H of the context: see --res), "
+                         "H x W x 3 to BASE.radiance.npy with --camera (the device's own camera rays)")
     ap.add_argument("--chunk", type=int, default=None, help="rays per chunk (knob cast_chunk)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--kd-build", choices=["gpu", "host"], default="gpu")
     return ap.parse_args(argv)
+
+
+def radiance_main(a: argparse.Namespace, sd, rays) -> int:
+    """--radiance SPP: the mean over iterations 1 .. SPP of kdpt_trace_rays' radiance, for the given rays (o, d) or,
+    with rays = None, for the rays kdpt_camera_rays reports for each iteration (jitter and depth of field included:
+    the render's own rays, so the result is the render's image)."""
+    from .runtime import PathTracer, default_options
+    if a.radiance < 1:
+        raise SystemExit("--radiance: SPP must be >= 1")
+    W, H = sd.resolution
+    with PathTracer(sd, default_options(short_stack=0 if a.bare else 1), device=a.device) as pt:
+        t0 = time.perf_counter()
+        if rays is not None:
+            if len(rays[0]) > W * H:
+                raise SystemExit(f"--radiance: {len(rays[0])} rays exceed the context's {W} x {H} paths (raise --res)")
+            total = pt.trace_rays(rays[0], rays[1], 1, a.radiance, normalize=not a.no_normalize)
+        else:
+            total = np.zeros((W * H, 3), np.float32)
+            for it in range(1, a.radiance + 1):
+                o, d = pt.camera_rays(it)
+                total += pt.trace_rays(o, d, it, 1, normalize=False)
+        dt = time.perf_counter() - t0
+    mean = total / np.float32(a.radiance)
+    out = a.out if rays is not None else a.out + ".radiance.npy"
+    np.save(out, mean if rays is not None else mean.reshape(H, W, 3))
+    print(json.dumps({"scene": a.scene, "mesh": a.mesh, "n": len(mean), "spp": a.radiance,
+                      "invalid": int(np.sum(np.isnan(mean).all(axis=1))), "seconds": round(dt, 4),
+                      "written": [out]}), flush=True)
+    return 0
 
 
 def main(argv=None) -> int:
@@ -79,6 +117,8 @@ def main(argv=None) -> int:
         o, d = camera_rays(sd.camera_bytes())
     else:
         o, d = rays[:, :3], rays[:, 3:]
+    if a.radiance is not None:
+        return radiance_main(a, sd, None if a.camera else (o, d))
     with PathTracer(sd, default_options(short_stack=0 if a.bare else 1), device=a.device) as pt:
         if a.chunk:
             pt.set_tuning("cast_chunk", a.chunk)

@@ -1,13 +1,15 @@
 // kdpt_runtime.hip -- the runtime behind the C ABI (include/kdpt.h): the context and its device memory,
 // kdpt_create (upload of what kdpt_scene_prep.h prepared), the knobs, the launch sequence of an iteration
-// (launch_batch), pipelined / batched iterations, the multi-GPU frame path and the ray queries.  One HIP
+// (launch_batch), pipelined / batched iterations, the multi-GPU frame path, the ray queries and the
+// caller-defined views (kdpt_set_camera, kdpt_camera_rays, kdpt_trace_rays).  One HIP
 // translation unit: the kernels live in the kernels_*.h headers included below, one per stage; scene
 // validation and packing live in kdpt_scene_prep.h and run before any device call.
 //
 // One iteration of the reference's per-sample hot path (src/pathtrace.cu:2405-2635 `pathtrace`), as queued by
 // launch_batch for a batch of up to MAXB iterations in lockstep (blockIdx.y / the batch records = iteration):
 //   k_gen_geoms_b   : camera rays + bounce 0's analytic geoms and root-box test, which queue the rays that
-//                     meet the KD root box (k_gen_rays_b alone on the brute-force / viz routes)
+//                     meet the KD root box (k_gen_rays_b alone on the brute-force / viz routes); a path-traced ray
+//                     query (kdpt_trace_rays) starts from the caller's rays instead: k_user_geoms_b / k_user_rays_b
 //   then per bounce (cap 8, src/pathtrace.cu:2608):
 //   k_trace         : the intersect kernel -- KD traversal of the queued rays, persistent waves pulling
 //                     64-ray chunks, the tree read from LDS when a record format fits (setup_trace); k_brute /
@@ -72,6 +74,7 @@ int fail(int code, const std::string& msg) {
 #include "kernels_shade.h"
 #include "kernels_image.h"
 #include "kernels_cast.h"
+#include "kernels_rays.h"
 #include "kernels_selftest.h"
 
 // ---------------------------------------------------------------------------
@@ -237,6 +240,17 @@ struct kdpt_ctx {
   hipEvent_t cast_ev[2] = {nullptr, nullptr};
   long long cast_rays = 0, cast_traced = 0;  // since create/reset (kdpt_cast_stats)
   double cast_ms = 0;                        // the last call's device time
+  // path-traced ray queries (kdpt_trace_rays, kdpt_camera_rays): an iteration state of their own, made on first
+  // use (query_state) -- its image is the query's radiance buffer, its segment and intersect totals go to
+  // query_totals instead of the context's -- and a staging buffer for host arrays; nothing here is shared with
+  // the render path or with kdpt_cast_rays
+  IterState query;
+  bool query_ready = false;
+  float* query_image = nullptr;  // [3 npix]
+  float* query_stage = nullptr;  // [6 npix] origins, then directions (inputs of host callers, camera rays on their way out)
+  unsigned long long* query_totals = nullptr;  // [0] ShadeArgs::total_segments, [1..3] trace_total / trace_rays
+  long long query_segments = 0, query_traced = 0;  // of the last kdpt_trace_rays (kdpt_trace_rays_stats)
+  double query_ms = 0;                             // ... and its device time
 };
 
 namespace {
@@ -290,8 +304,15 @@ int launch_iteration(kdpt_ctx* c, int iter, int stop_depth, bool count);
 void release_comm(kdpt_ctx* c);  // (multi-GPU section, end of file)
 void unregister_host(kdpt_ctx* c);
 void free_cast_buffers(kdpt_ctx* c);  // (ray queries, end of file)
+// A batch that starts from caller-supplied rays instead of the camera's (kdpt_trace_rays; one iteration per
+// batch): the rays in device memory, and where the shading adds what it would add to the context's intersect
+// totals (kdpt_ctx::trace_total's layout).
+struct RaySource {
+  UserRays rays;
+  unsigned long long* trace_total;
+};
 int launch_batch(kdpt_ctx* c, IterState* const* its, const int* iters, int nb, hipStream_t st, int trace_grid,
-                 int stop_depth, bool count, std::vector<hipEvent_t>* bev);
+                 int stop_depth, bool count, std::vector<hipEvent_t>* bev, const RaySource* rays = nullptr);
 
 // Work queued on the context's own stream that reads or writes `image` must follow the pipelined
 // accumulation (kdpt_trace_iterations adds partial images on the batch streams without a host sync) and the
@@ -1445,6 +1466,7 @@ int kdpt_destroy(kdpt_ctx* c) {
   for (auto e : c->cast_ev)
     if (e) (void)hipEventDestroy(e);
   free_iter(&c->solo);
+  free_iter(&c->query);  // (its image, staging buffer and totals were among c->allocs)
   if (c->entry_ev) (void)hipEventDestroy(c->entry_ev);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
@@ -1664,14 +1686,40 @@ struct Batch {
                     // brute-force and box-view intersect kernels, which have no first part)
   bool compact;
   ShadeArgs shade;  // the shading arguments that neither the bounce nor the iteration changes
+  const RaySource* rays = nullptr;  // a ray query's batch (nb = 1): bounce 0 loads these instead of the camera's
+  unsigned long long* trace_total = nullptr;  // the intersect totals the shading adds to (the context's, or the query's)
 };
+
+// The camera-ray launch's arguments but for the iteration records: the context's current camera and options.
+// (ncounts, nwork, nlb: the lengths of the counters, work counters and look-back records the launch zeroes)
+GenBatch gen_batch(const kdpt_ctx* c) {
+  return GenBatch{{}, c->cam, c->traceDepth, c->opt.antialias, c->cap + 2, c->cap, c->cap * c->ntiles,
+                  c->opt.focal_length, c->opt.dof_angle};
+}
+
+// A ray query's bounce 0: its rays loaded into the state's paths (k_user_rays_b), with bounce 0's geoms stage when
+// gen_geoms (k_user_geoms_b).  The grid covers the rays, not the image.
+int user_rays_stage(const Batch& B) {
+  kdpt_ctx* c = B.c;
+  IterState* it = B.its[0];
+  it->cur = 0;
+  const UserBatch ub{it->gen_iter(B.iters[0]), B.rays->rays, c->traceDepth, c->cap + 2, c->cap, c->cap * c->ntiles};
+  const dim3 grid((ub.src.n + GEN_BLOCK - 1) / GEN_BLOCK);
+  if (B.gen_geoms) {
+    const UserGeomsBatch ug{ub, B.S0, it->gen_geoms_iter(), B.count ? c->counters : nullptr};
+    hipLaunchKernelGGL(k_user_geoms_b, grid, dim3(GEN_BLOCK), 0, B.st, ug);
+  } else {
+    hipLaunchKernelGGL(k_user_rays_b, grid, dim3(GEN_BLOCK), 0, B.st, ub);
+  }
+  HIP_TRY(hipGetLastError());
+  return KDPT_OK;
+}
 
 // The batch's camera rays in one launch (blockIdx.y = iteration), with bounce 0's geoms stage when gen_geoms.
 int camera_stage(const Batch& B) {
+  if (B.rays) return user_rays_stage(B);
   kdpt_ctx* c = B.c;
-  // (ncounts, nwork, nlb: the lengths of the counters, work counters and look-back records the launch zeroes)
-  GenBatch gb{{}, c->cam, c->traceDepth, c->opt.antialias, c->cap + 2, c->cap, c->cap * c->ntiles,
-              c->opt.focal_length, c->opt.dof_angle};
+  GenBatch gb = gen_batch(c);
   for (int b = 0; b < B.nb; b++) {
     B.its[b]->cur = 0;
     gb.it[b] = B.its[b]->gen_iter(c->opt.cacherays ? 1 : B.iters[b]);
@@ -1753,7 +1801,7 @@ ShadeArgs shade_args(const Batch& B, int b, int depth, bool prep_next) {
   a.iter = B.iters[b];
   a.tile_counts = it->tile_counts;
   a.total_segments = it->total_segments;
-  a.trace_total = b == 0 ? B.c->trace_total : nullptr;
+  a.trace_total = b == 0 ? B.trace_total : nullptr;
   a.ccount = it->cand_count(depth, B.gen_geoms);
   a.prep_on = prep_next ? 1 : 0;
   a.prep = it->prep;
@@ -1829,11 +1877,11 @@ int shade_stage(const Batch& B, int depth, bool prep_next) {
 // them, then each one's shading and compaction.  The iterations stay independent: only the intersect launch is
 // shared.
 int launch_batch(kdpt_ctx* c, IterState* const* its, const int* iters, int nb, hipStream_t st, int trace_grid,
-                 int stop_depth, bool count, std::vector<hipEvent_t>* bev) {
+                 int stop_depth, bool count, std::vector<hipEvent_t>* bev, const RaySource* rays) {
   if (c->shade_oob) return refuse_shading();
   const bool kd = !c->brute && !c->viz;
   Batch B{c, its, iters, nb, st, trace_grid, count, scene_of(c, its[0]), c->gen_geoms && kd, c->opt.compaction != 0,
-          ShadeArgs{}};
+          ShadeArgs{}, rays, rays ? rays->trace_total : c->trace_total};
   B.shade.S = c->S;
   B.shade.softness = c->opt.softness;
   B.shade.enable_sss = c->opt.enable_sss;
@@ -1842,7 +1890,7 @@ int launch_batch(kdpt_ctx* c, IterState* const* its, const int* iters, int nb, h
   B.shade.nkeys = c->nkeys;
   B.shade.trace_t = its[0]->trace_t;
   B.shade.gspan = its[0]->trace_t + 2 * c->cap;
-  B.shade.trace_rays = kd ? c->trace_total + 2 : nullptr;
+  B.shade.trace_rays = kd ? B.trace_total + 2 : nullptr;
   B.shade.count_aabb = count ? c->counters : nullptr;
   int rc = camera_stage(B);
   if (rc) return rc;
@@ -2383,5 +2431,139 @@ int kdpt_cast_stats(kdpt_ctx* c, long long* rays, long long* traced, double* dev
   if (rays) *rays = c->cast_rays;
   if (traced) *traced = c->cast_traced;
   if (device_ms) *device_ms = c->cast_ms;
+  return KDPT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Caller-defined views (include/kdpt.h "Caller-defined views"): kdpt_set_camera, kdpt_camera_rays and
+// kdpt_trace_rays.  The two queries run in the context's query state (kdpt_ctx::query), on its stream, after
+// everything already queued; kernels: k_gen_rays_b, or k_user_rays_b / k_user_geoms_b and then launch_batch's.
+// ---------------------------------------------------------------------------
+namespace {
+
+// The query's iteration state and buffers, made on first use (the caller has synchronised the context).
+int query_state(kdpt_ctx* c) {
+  if (c->query_ready) return KDPT_OK;
+  int rc;
+  if (!c->query.counts && (rc = alloc_iter(c, &c->query, c->stream, false))) {
+    free_iter(&c->query);
+    return rc;
+  }
+  const size_t npix = (size_t)c->npix;
+  if ((!c->query_image && (rc = dalloc(c, &c->query_image, 3 * npix))) ||
+      (!c->query_stage && (rc = dalloc(c, &c->query_stage, 6 * npix))) ||
+      (!c->query_totals && (rc = dalloc(c, &c->query_totals, 4))))
+    return rc;
+  c->query.image = c->query_image;
+  c->query.total_segments = c->query_totals;
+  c->query_ready = true;
+  return KDPT_OK;
+}
+
+}  // namespace
+
+int kdpt_set_camera(kdpt_ctx* c, const kdpt_camera* cam) {
+  if (!c) return fail(KDPT_ERR_ARG, "kdpt_set_camera: null ctx");
+  if (!cam) return fail(KDPT_ERR_ARG, "kdpt_set_camera: null camera");
+  // prepare_scene's checks of a scene's camera are on its resolution, which here must be the context's
+  if (cam->resolution[0] != c->W || cam->resolution[1] != c->H)
+    return fail(KDPT_ERR_ARG, "kdpt_set_camera: resolution " + std::to_string(cam->resolution[0]) + "x" +
+                                  std::to_string(cam->resolution[1]) + " is not the context's " +
+                                  std::to_string(c->W) + "x" + std::to_string(c->H));
+  const float* const vecs[] = {cam->position, cam->lookAt, cam->view, cam->up, cam->right};
+  bool finite = std::isfinite(cam->fov[0]) && std::isfinite(cam->fov[1]) && std::isfinite(cam->pixelLength[0]) &&
+                std::isfinite(cam->pixelLength[1]);
+  for (const float* v : vecs) finite = finite && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]);
+  if (!finite) return fail(KDPT_ERR_ARG, "kdpt_set_camera: a camera value is not finite");
+  c->cam = *cam;  // launches take the camera by value: what is already queued keeps the one it was queued with
+  return KDPT_OK;
+}
+
+int kdpt_camera_rays(kdpt_ctx* c, int iter, float* origins, float* directions) {
+  if (!c) return fail(KDPT_ERR_ARG, "kdpt_camera_rays: null ctx");
+  if (iter < 1) return fail(KDPT_ERR_ARG, "kdpt_camera_rays: iter must be >= 1");
+  if (!origins) return fail(KDPT_ERR_ARG, "kdpt_camera_rays: null origins");
+  if (!directions) return fail(KDPT_ERR_ARG, "kdpt_camera_rays: null directions");
+  int rc = kdpt_synchronize(c);  // everything queued on the context first
+  if (rc || (rc = query_state(c))) return rc;
+  const hipStream_t st = c->stream;
+  IterState& q = c->query;
+  q.cur = 0;
+  GenBatch gb = gen_batch(c);
+  gb.it[0] = q.gen_iter(c->opt.cacherays ? 1 : iter);
+  hipLaunchKernelGGL(k_gen_rays_b, dim3((c->npix + 255) / 256, 1), dim3(256), 0, st, gb);
+  HIP_TRY(hipGetLastError());
+  // xyz of p0 / p1 (float4 records) into packed triples: a strided copy each, straight into device memory of the
+  // caller's, through the staging buffer into host memory
+  const size_t npix = (size_t)c->npix, row = 3 * sizeof(float);
+  float* const outs[2] = {origins, directions};
+  const float4* const srcs[2] = {q.buf[0].p0, q.buf[0].p1};
+  for (int k = 0; k < 2; k++) {
+    const bool dev = on_context_device(c, outs[k]);
+    float* const packed = dev ? outs[k] : c->query_stage + 3 * npix * k;
+    HIP_TRY(hipMemcpy2DAsync(packed, row, srcs[k], sizeof(float4), row, npix, hipMemcpyDeviceToDevice, st));
+    if (!dev) HIP_TRY(hipMemcpyAsync(outs[k], packed, row * npix, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  return KDPT_OK;
+}
+
+int kdpt_trace_rays(kdpt_ctx* c, const float* origins, const float* directions, long long n, int first_iter,
+                    int count, int flags, float* radiance) {
+  if (n < 0) return fail(KDPT_ERR_ARG, "kdpt_trace_rays: n must be >= 0");
+  if (count < 0) return fail(KDPT_ERR_ARG, "kdpt_trace_rays: count must be >= 0");
+  if (first_iter < 1) return fail(KDPT_ERR_ARG, "kdpt_trace_rays: first_iter must be >= 1");
+  if (flags & ~KDPT_CAST_NORMALIZE) return fail(KDPT_ERR_ARG, "kdpt_trace_rays: unknown bit in flags");
+  if (!c) return fail(KDPT_ERR_ARG, "kdpt_trace_rays: null ctx");
+  if (n > (long long)c->npix)
+    return fail(KDPT_ERR_ARG, "kdpt_trace_rays: n = " + std::to_string(n) + " exceeds the context's W * H = " +
+                                  std::to_string(c->npix) + " paths (create a context of a larger resolution)");
+  const bool work = n > 0 && count > 0;
+  if (work && !origins) return fail(KDPT_ERR_ARG, "kdpt_trace_rays: null origins");
+  if (work && !directions) return fail(KDPT_ERR_ARG, "kdpt_trace_rays: null directions");
+  if (work && !radiance) return fail(KDPT_ERR_ARG, "kdpt_trace_rays: null radiance");
+  if (!work) return KDPT_OK;
+  if (c->shade_oob) return refuse_shading();
+  int rc = kdpt_synchronize(c);  // everything queued on the context first
+  if (rc || (rc = query_state(c))) return rc;
+  const hipStream_t st = c->stream;
+  IterState* q = &c->query;
+  const size_t m = (size_t)n, npix = (size_t)c->npix;
+  RaySource src{{origins, directions, (int)n, (flags & KDPT_CAST_NORMALIZE) ? 1 : 0}, c->query_totals + 1};
+  if (!on_context_device(c, origins)) {
+    HIP_TRY(hipMemcpyAsync(c->query_stage, origins, sizeof(float) * 3 * m, hipMemcpyHostToDevice, st));
+    src.rays.o = c->query_stage;
+  }
+  if (!on_context_device(c, directions)) {
+    HIP_TRY(hipMemcpyAsync(c->query_stage + 3 * npix, directions, sizeof(float) * 3 * m, hipMemcpyHostToDevice, st));
+    src.rays.d = c->query_stage + 3 * npix;
+  }
+  HIP_TRY(hipEventRecord(q->ev0, st));
+  // pixel i of the query's image is ray i: the gathers add into it in iteration order, from zero
+  HIP_TRY(hipMemsetAsync(c->query_image, 0, sizeof(float) * 3 * m, st));
+  HIP_TRY(hipMemsetAsync(c->query_totals, 0, sizeof(unsigned long long) * 4, st));
+  for (int k = 0; k < count; k++) {
+    const int iter = first_iter + k;
+    if ((rc = launch_batch(c, &q, &iter, 1, st, c->trace_grid, -1, false, nullptr, &src))) return rc;
+  }
+  HIP_TRY(hipMemcpyAsync(radiance, c->query_image, sizeof(float) * 3 * m,
+                         on_context_device(c, radiance) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipEventRecord(q->ev1, st));
+  unsigned long long totals[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(totals, c->query_totals, sizeof totals, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  float ms = 0;
+  HIP_TRY(hipEventElapsedTime(&ms, q->ev0, q->ev1));
+  c->query_ms = ms;
+  c->query_segments = (long long)totals[0];
+  c->query_traced = (long long)totals[3];
+  return check_fault(q, st);
+}
+
+int kdpt_trace_rays_stats(kdpt_ctx* c, long long* segments, long long* traced, double* device_ms) {
+  if (!c) return fail(KDPT_ERR_ARG, "kdpt_trace_rays_stats: null ctx");
+  if (segments) *segments = c->query_segments;
+  if (traced) *traced = c->query_traced;
+  if (device_ms) *device_ms = c->query_ms;
   return KDPT_OK;
 }

@@ -30,7 +30,9 @@ constexpr int CAST_REJECTED = (int)0x80000000;  // hits[i].y of a rejected ray (
 
 // The chunk's ray i as it is traced: false = rejected (a non-finite component, a zero direction or one whose
 // normalisation is not finite, or a direction that is not unit length: |dot(d, d) - 1| > 1e-6 in float).
-__device__ __attribute__((always_inline)) inline bool cast_load(const CastArgs& A, int i, f3& o, f3& d) {
+// (RayArgs: CastArgs, or kernels_rays.h's UserRays -- anything with o, d and normalize.)
+template <typename RayArgs>
+__device__ __attribute__((always_inline)) inline bool cast_load(const RayArgs& A, int i, f3& o, f3& d) {
   o = mk3(A.o[3 * (size_t)i], A.o[3 * (size_t)i + 1], A.o[3 * (size_t)i + 2]);
   d = mk3(A.d[3 * (size_t)i], A.d[3 * (size_t)i + 1], A.d[3 * (size_t)i + 2]);
   bool ok = fabsf(o.x) < FLT_INFV && fabsf(o.y) < FLT_INFV && fabsf(o.z) < FLT_INFV && fabsf(d.x) < FLT_INFV &&

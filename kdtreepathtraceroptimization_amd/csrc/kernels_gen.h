@@ -34,14 +34,14 @@ struct Counters {
 // ---------------------------------------------------------------------------
 // generateRayFromCamera (src/pathtrace.cu:315-397)
 // ---------------------------------------------------------------------------
-__device__ __attribute__((always_inline)) inline bool gen_rays_body(
-    const kdpt_camera& cam, int iter, int traceDepth, PathBuf out, float focalLength, float dofAngle, int antialias,
-    int* counts, int ncounts, int* work, int nwork, unsigned long long* trace_t, unsigned long long* lb, int nlb,
-    float* zero_image, f3& ray_o, f3& ray_d) {
-  const int W = cam.resolution[0], H = cam.resolution[1];
-  const int index = blockIdx.x * blockDim.x + threadIdx.x;
+// What the first kernel of an iteration zeroes for the later ones, whichever kernel that is (the camera's, or a
+// ray query's k_user_rays_b / k_user_geoms_b): lane 0 sets the path count and clears the per-bounce counters and
+// launch records, every lane its share of the look-back records.
+__device__ __attribute__((always_inline)) inline void gen_prologue(int index, int npaths, int* counts, int ncounts,
+                                                                   int* work, int nwork, unsigned long long* trace_t,
+                                                                   unsigned long long* lb, int nlb) {
   if (index == 0) {
-    counts[0] = W * H;
+    counts[0] = npaths;
     for (int k = 1; k < ncounts; k++) counts[k] = 0;
     for (int k = 0; k < nwork; k++) {
       work[k] = 0;
@@ -54,6 +54,15 @@ __device__ __attribute__((always_inline)) inline bool gen_rays_body(
     }
   }
   for (int e = index; e < nlb; e += gridDim.x * blockDim.x) lb[e] = 0ull;  // k_shade_fused's look-back records
+}
+
+__device__ __attribute__((always_inline)) inline bool gen_rays_body(
+    const kdpt_camera& cam, int iter, int traceDepth, PathBuf out, float focalLength, float dofAngle, int antialias,
+    int* counts, int ncounts, int* work, int nwork, unsigned long long* trace_t, unsigned long long* lb, int nlb,
+    float* zero_image, f3& ray_o, f3& ray_d) {
+  const int W = cam.resolution[0], H = cam.resolution[1];
+  const int index = blockIdx.x * blockDim.x + threadIdx.x;
+  gen_prologue(index, W * H, counts, ncounts, work, nwork, trace_t, lb, nlb);
   if (index >= W * H) return false;
   if (zero_image) {  // batched iterations: this iteration's partial image starts at zero (no separate fill)
     zero_image[3 * index] = 0.0f;

@@ -1,7 +1,7 @@
 // kernels_selftest.h -- the kdpt_selftest_* entry points' kernels (device math, RNG, glm, Fresnel).
 //
 // A section of kdpt_runtime.hip's translation unit, not a stand-alone header: kdpt_runtime.hip includes it
-// after kernels_cast.h, and the kernels keep that order in the code object.  Device code and launch-argument
+// after kernels_rays.h, and the kernels keep that order in the code object.  Device code and launch-argument
 // structs only: no HIP host call lives here (tests/test_stream_discipline.py reads kdpt_runtime.hip).
 #pragma once
 

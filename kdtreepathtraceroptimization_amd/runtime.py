@@ -120,6 +120,12 @@ class CastStats(NamedTuple):  # kdpt_cast_stats
     traced: int       # ... of which reached the KD traversal kernel
     device_ms: float  # the last cast's device time
 
+
+class TraceRaysStats(NamedTuple):  # kdpt_trace_rays_stats: of the last kdpt_trace_rays
+    segments: int     # path segments launched into the intersect stage, summed over its iterations
+    traced: int       # ... of which were handed to the KD traversal kernel
+    device_ms: float  # the call's device time
+
 assert C.sizeof(Geom) == 236 and C.sizeof(Material) == 56 and C.sizeof(Camera) == 84
 assert C.sizeof(NodeBare) == 64 and C.sizeof(TriBare) == 76 and C.sizeof(PathSegment) == 56
 
@@ -133,6 +139,7 @@ EXPORTS = [
     "kdpt_scene_kd_build_ms", "kdpt_build_kd_device", "kdpt_scene_load_device", "kdpt_trace_config",
     "kdpt_cull_margin", "kdpt_comm_unique_id", "kdpt_comm_init", "kdpt_render_frames", "kdpt_render_sharded",
     "kdpt_comm_library", "kdpt_cull_masks", "kdpt_cast_rays", "kdpt_cast_stats",
+    "kdpt_set_camera", "kdpt_camera_rays", "kdpt_trace_rays", "kdpt_trace_rays_stats",
 ]
 
 REDUCE_RCCL, REDUCE_COPY = 0, 1  # kdpt_render_sharded's reduce (KDPT_REDUCE_*)
@@ -229,6 +236,12 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     if hasattr(lib, "kdpt_cast_rays"):  # absent from older builds used in A/B runs
         lib.kdpt_cast_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]
         lib.kdpt_cast_stats.argtypes = [C.c_void_p, P(C.c_longlong), P(C.c_longlong), P(C.c_double)]
+    if hasattr(lib, "kdpt_trace_rays"):  # absent from older builds used in A/B runs
+        lib.kdpt_set_camera.argtypes = [C.c_void_p, P(Camera)]
+        lib.kdpt_camera_rays.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.kdpt_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int,
+                                        C.c_void_p]
+        lib.kdpt_trace_rays_stats.argtypes = [C.c_void_p, P(C.c_longlong), P(C.c_longlong), P(C.c_double)]
     _lib = lib
     return lib
 
@@ -514,6 +527,56 @@ class PathTracer:
         r, t, ms = C.c_longlong(), C.c_longlong(), C.c_double()
         _check(self.lib.kdpt_cast_stats(self._ctx, C.byref(r), C.byref(t), C.byref(ms)), "kdpt_cast_stats")
         return CastStats(int(r.value), int(t.value), float(ms.value))
+
+    def set_camera(self, camera):
+        """kdpt_set_camera: the pinhole camera of the iterations enqueued from now on (a Camera, or a SceneData
+        whose camera is taken).  Its resolution must be the context's; the image, stats and iteration counter are
+        kept (reset() clears them)."""
+        cam = camera.view.camera if isinstance(camera, SceneData) else camera
+        _check(self.lib.kdpt_set_camera(self._ctx, C.byref(cam)), "kdpt_set_camera")
+
+    def camera_rays(self, iteration: int):
+        """kdpt_camera_rays: the W*H rays the device generates for `iteration` with the context's current camera
+        and options, as (origins, directions), each (W*H, 3) float32 with index = y*W + x."""
+        n = self.width * self.height
+        o, d = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
+        self.camera_rays_ptr(iteration, o.ctypes.data, d.ctypes.data)
+        return o, d
+
+    def camera_rays_ptr(self, iteration: int, origins_ptr: int, directions_ptr: int):
+        """kdpt_camera_rays into raw pointers (host memory or memory of the context's device): 3*W*H floats each."""
+        _check(self.lib.kdpt_camera_rays(self._ctx, int(iteration), C.c_void_p(int(origins_ptr)),
+                                         C.c_void_p(int(directions_ptr))), "kdpt_camera_rays")
+
+    def trace_rays(self, origins, directions, first_iter: int = 1, count: int = 1,
+                   normalize: bool = True) -> np.ndarray:
+        """kdpt_trace_rays on host arrays: the radiance the path tracer gathers for each of n <= W*H rays
+        (origins, directions: n x 3 float32), summed over iterations first_iter .. first_iter + count - 1, as an
+        (n, 3) float32 array.  Ray i is traced as pixel i of an n-pixel image whose camera produced these rays.
+        normalize as in cast_rays; a rejected ray's radiance is NaN in all three channels."""
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError(f"{len(o)} origins but {len(d)} directions")
+        out = np.empty((len(o), 3), dtype=np.float32)
+        self.trace_rays_ptr(o.ctypes.data, d.ctypes.data, len(o), out.ctypes.data, first_iter=first_iter,
+                            count=count, normalize=normalize)
+        return out
+
+    def trace_rays_ptr(self, origins_ptr: int, directions_ptr: int, n: int, radiance_ptr: int, first_iter: int = 1,
+                       count: int = 1, normalize: bool = True):
+        """kdpt_trace_rays on raw pointers, each host memory or memory of the context's device (e.g. a torch
+        tensor's data_ptr()): 3 n floats each.  Synchronous."""
+        _check(self.lib.kdpt_trace_rays(self._ctx, C.c_void_p(int(origins_ptr)), C.c_void_p(int(directions_ptr)),
+                                        int(n), int(first_iter), int(count), CAST_NORMALIZE if normalize else 0,
+                                        C.c_void_p(int(radiance_ptr))), "kdpt_trace_rays")
+
+    def trace_rays_stats(self) -> "TraceRaysStats":
+        """kdpt_trace_rays_stats: the last trace_rays' segments, rays handed to the KD traversal kernel and device
+        time in ms (the query's own totals: stats() never sees them)."""
+        s, t, ms = C.c_longlong(), C.c_longlong(), C.c_double()
+        _check(self.lib.kdpt_trace_rays_stats(self._ctx, C.byref(s), C.byref(t), C.byref(ms)), "kdpt_trace_rays_stats")
+        return TraceRaysStats(int(s.value), int(t.value), float(ms.value))
 
     def reset(self):
         _check(self.lib.kdpt_reset(self._ctx), "kdpt_reset")

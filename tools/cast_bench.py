@@ -5,6 +5,10 @@
   bounce3  ... after bounce 3 (fewer, and as incoherent as the path tracer's rays get)
   random   uniformly random origins and unit directions inside the room
 
+  radiance the device's own 800 x 800 camera rays of iteration 1 path traced by one kdpt_trace_rays(count = 16), next
+           to 16 kdpt_trace_iteration calls on the same context (cacherays = 1: both legs trace those rays, and the
+           line says whether the two images are bit-equal): wall and device ms of each leg
+
 One JSON line per set: rays, the share that reached the KD traversal, the best and median wall time of --reps
 synchronous calls (host clock around kdpt_cast_rays, which returns with the records written), rays per second
 from the median, and kdpt_cast_stats' device time of the last call; then a line with the library's code-object
@@ -70,6 +74,42 @@ with kdpt.PathTracer(sd, kdpt.default_options(short_stack=0 if a.bare else 1), d
                           "wall_ms_best": round(1e3 * min(times), 4), "wall_ms_median": round(1e3 * med, 4),
                           "mrays_per_s": round(n / med / 1e6, 1), "device_ms_last": round(st.device_ms, 4)}),
               flush=True)
+    # The radiance set: the render's own 800 x 800 camera rays of iteration 1 (cacherays, so that every iteration
+    # of both legs traces them) through one kdpt_trace_rays(count = 16), next to 16 kdpt_trace_iteration calls --
+    # the same launches behind another bounce-0 kernel, plus the query's 24 bytes in and 12 out per ray.  Wall: the
+    # host clock around the synchronous calls; device: kdpt_trace_rays_stats / the sum of ms_last_iteration.
+    spp = 16
+    pt.set_options(kdpt.default_options(short_stack=0 if a.bare else 1, cacherays=1))
+    n = 800 * 800
+    to = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    td = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    rad = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize(dev)
+    pt.camera_rays_ptr(1, to.data_ptr(), td.data_ptr())
+    legs = {"query": [], "solo": []}
+    for rep in range(a.reps + 1):  # the first round allocates the query's state: not timed
+        t0 = time.perf_counter()
+        pt.trace_rays_ptr(to.data_ptr(), td.data_ptr(), n, rad.data_ptr(), first_iter=1, count=spp, normalize=False)
+        t1 = time.perf_counter()
+        q_dev = pt.trace_rays_stats().device_ms
+        pt.reset()
+        t2 = time.perf_counter()
+        for it in range(1, spp + 1):
+            pt.trace_iteration(it)
+        t3 = time.perf_counter() - t2
+        pt.reset()
+        s_dev = 0.0
+        for it in range(1, spp + 1):  # (again for the device times: reading the stats is not part of the wall time)
+            pt.trace_iteration(it)
+            s_dev += pt.stats().ms_last_iteration
+        if rep:
+            legs["query"].append((t1 - t0, q_dev))
+            legs["solo"].append((t3, s_dev))
+    same = bool(np.array_equal(rad.cpu().numpy().view(np.uint32).reshape(-1), pt.image().view(np.uint32).reshape(-1)))
+    print(json.dumps({"set": "radiance", "rays": n, "iterations": spp, "query_equals_solo_image": same,
+                      **{f"{leg}_{what}_ms_{stat}": round(f([1e3 * t[0] if k == 0 else t[1] for t in ts]), 4)
+                         for leg, ts in legs.items() for k, what in enumerate(("wall", "device"))
+                         for stat, f in (("best", min), ("median", statistics.median))}}), flush=True)
     print(json.dumps({"scene": "cornell+dragon_5", "tree": cfg["tree"], "cull_exact": cfg.get("cull_exact"),
                       "short_stack": 0 if a.bare else 1, "chunk": a.chunk or (1 << 20), "reps": a.reps,
                       "code_object_sha": _build.code_object_sha(kdpt.LIB_PATH)}), flush=True)

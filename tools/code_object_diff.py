@@ -1,7 +1,8 @@
 """Per-symbol comparison of the gfx950 code objects of two builds of the library.
    python tools/code_object_diff.py OLD.so NEW.so
 Unbundles each library's .hip_fatbin, disassembles it and compares, symbol by symbol, the instruction text
-(addresses dropped: the order of the kernels in the object follows their first use in the host code).  Prints
+(addresses dropped: the order of the kernels in the object follows their first use in the host code; a pc-relative
+target is named by function + offset, or by section + offset when it lies outside the code).  Prints
 the symbol counts, the symbols on one side only and the ones whose bodies differ; exit status 1 when any do."""
 import os
 import re
@@ -51,11 +52,23 @@ def symbols(lib, tmp, tag):
             else:
                 cur.append(ins)
             prev = ins
-    # (a target inside a function as function + offset, anything else -- .rodata, .got -- as its address)
+    # (a target inside a function as function + offset, anything else -- .rodata, .got -- as section + offset: a
+    # table keeps its place in its section when kernels are added, while its address moves with the code before it)
     starts.sort()
+    sections = []
+    for line in subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-h", co], check=True, capture_output=True,
+                               text=True).stdout.splitlines():
+        f = line.split()
+        if len(f) >= 4 and f[0].isdigit() and f[1].startswith("."):
+            sections.append((f[1], int(f[3], 16), int(f[2], 16)))  # name, address, size
     def place(addr):
         inside = [(a, s) for a, s in starts if a <= addr]
-        return f"{inside[-1][1]}+{addr - inside[-1][0]:#x}" if inside and addr < starts[-1][0] else f"@{addr:#x}"
+        if inside and addr < starts[-1][0]:
+            return f"{inside[-1][1]}+{addr - inside[-1][0]:#x}"
+        for name, base, size in sections:
+            if name != ".text" and base <= addr < base + size:
+                return f"{name}+{addr - base:#x}"
+        return f"@{addr:#x}"
     return {s: [i if isinstance(i, str) else f"{i[0]} {place(i[1])}" for i in body] for s, body in out.items()}
 
 
