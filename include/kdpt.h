@@ -284,6 +284,10 @@ int kdpt_trace_config(kdpt_ctx *ctx, int *tree_mode, int *block, int *grid, long
  * culled at the box coefficient (1e-3) without masks: the cull is then conservative except for rays nearly
  * coplanar with a triangle. */
 int kdpt_cull_margin(kdpt_ctx *ctx, float *margin, double *rigorous, int *exact);
+/* Report only: *staged = 1 when the fused shading kernels run with the scene's analytic geoms and materials copied
+ * to LDS (at most 8 geoms, KD boxes of viz_kd included, and at most 32 materials), 0 when they read them from
+ * memory. */
+int kdpt_shade_staged(kdpt_ctx *ctx, int *staged);
 /* The masked cull's danger masks as the device built them (bucket-major: cell b * num_clusters + c, 6 mask_n^2
  * buckets).  *mask_n = 0 when the scene has none (its cull is exact without them).  masks may be NULL (sizes
  * only); otherwise 6 mask_n^2 num_clusters entries.  For parity tests against the host builder

@@ -49,15 +49,57 @@ struct DevGeom {
   float transform[16];
   float inverseTransform[16];
   float invTranspose[16];
-  // world-space bounds of the unit cube / sphere under `transform`, enlarged by a margin far above
-  // float rounding: a ray that misses them cannot hit the object (used to skip the exact test)
+  // world-space bounds of the unit cube / sphere under `transform`, enlarged by a margin, and in wlo[3] the
+  // Chebyshev distance from them within which a ray origin may rely on them (geom_may_hit, below)
   float wlo[4], whi[4];
 };
 
-// Conservative skip test for the analytic geoms (invdir finite).  The exact object-space test
-// (boxIntersectionTest / sphereIntersectionTest) reports a hit only for rays passing within rounding
-// distance of the object, ahead of the origin; the bounds carry a margin far above that.
-KDPT_HD bool geom_may_hit(const DevGeom& G, f3 o, f3 invdir) {
+// The analytic geoms' bounds: what a ray may conclude from them, and when.
+//
+// boxIntersectionTest / sphereIntersectionTest work in object space, in float: they transform the origin by the
+// float inverseTransform, intersect the unit cube / the sphere of radius 0.5 there, step back 1e-4 along the
+// object-space direction, transform that point by `transform` and report t = |origin - point|.  The reported
+// point is a point of the ray and of the object only up to rounding, and that rounding is not small everywhere:
+//   (a) the object-space origin is formed from products of size |inverse| x |coordinate|, so it -- and through
+//       `transform` the reported point -- is off by u x (the magnitude of the world coordinates involved),
+//       u = 2^-24, whatever the size of the object: a geom translated far from the world origin, or a ray that
+//       starts far away, is tested against an object displaced by that much;
+//   (b) the float inverse is not the inverse of the float transform: E = inverse x transform - 1 (linear part)
+//       and e = inverse x translation + inverse's translation displace the object by E q + e at object-space
+//       distance q;
+//   (c) the sphere test's radicand (ro.rd)^2 - (ro.ro - 0.25) cancels two terms of size D^2 (D the origin's
+//       object-space distance): its rounding, <= 16 u (D + 1)^2 (6 u for the squared dot product, 3 u for ro.ro,
+//       2 u for the two differences, 3 u for |rd|^2 - 1, rounded up), is a ray reported to hit a sphere of
+//       radius^2 0.25 + that much -- at D = 1e4 a radius of up to 10 instead of 0.5 -- and a hit point up to the
+//       square root of it before the true one along the ray (sqrt(u) x D x scale in world units);
+//   (d) the 1e-4 step back, up to 1e-4 x the world extent;
+//   (e) a direction cast without the normalize flag has |d|^2 = 1 +- 1e-6, so the parameter of a point exceeds
+//       its distance by up to 5.1e-7 of it.
+// So "the exact test hits only rays that enter the bounds, at a t no smaller than the entry parameter" holds
+// only where the sum of these stays below the bounds' margin, 1e-3 x extent + 1e-3 (a sphere's, whose radicand
+// needs the room and which fills only half of its bounds anyway: 1e-2 x extent + 1e-3).  prepare_geom
+// (kdpt_scene_prep.h, geom_safe_range) evaluates that sum in double from the geom's own float matrices for
+// origins within Chebyshev distance R of the bounds, and stores in wlo[3] the largest R (of a halving sequence)
+// for which
+//     4 x (a + b + c + e, mapped to world axes through |transform|, + 16 u x coordinates) + (d) <= margin;
+// the factor: a point X within `a` of the ray's point at parameter s and within `b` of the true box puts that
+// ray point inside the box enlarged by a + b, whose entry parameter exceeds the entry into the box enlarged by
+// the margin m by at least m - a - b (each slab plane moves by that much, and |d_k| <= 1), while |o - X| >=
+// s - sqrt(3) a: t >= entry needs m >= (1 + sqrt(3)) a + b.  R = -inf when not even R = 0 satisfies it (a geom
+// whose translation is large against its size, matrices that are not each other's inverse).
+//
+// A ray whose origin lies farther than R from the bounds concludes nothing from them: geom_may_hit says true,
+// and the geom is tested as the reference tests every geom.  prep_ray decides once per ray instead of once per
+// geom: for an origin inside DevScene::gc +- gh, the intersection of the geoms' ranges (each its bounds grown
+// by R; empty when some R is -inf) it runs as before -- the nearest-first loop, or the index-order loop with the
+// skip test -- and for any other origin every geom is tested, in index order.  The fixture scenes keep
+// R >= 24 around their 10-unit room, so their rays all stay on the nearest-first path.  tests/test_geom_diff.py
+// compares the loops built on this with the reference's index-order loop on 400 000 rays per generator of
+// tests/geoms.py, origins up to 3 000 units away and scenes at 1e5 included.
+
+// The ray against the geom's enlarged bounds (invdir finite): false = it misses them.  For an origin within the
+// geom's proven range (above) the exact test then misses as well.
+KDPT_HD bool geom_bounds_hit(const DevGeom& G, f3 o, f3 invdir) {
   const float t1x = (G.wlo[0] - o.x) * invdir.x, t2x = (G.whi[0] - o.x) * invdir.x;
   const float t1y = (G.wlo[1] - o.y) * invdir.y, t2y = (G.whi[1] - o.y) * invdir.y;
   const float t1z = (G.wlo[2] - o.z) * invdir.z, t2z = (G.whi[2] - o.z) * invdir.z;
@@ -66,10 +108,18 @@ KDPT_HD bool geom_may_hit(const DevGeom& G, f3 o, f3 invdir) {
   return tmax >= tmin && tmax >= 0.0f;
 }
 
-// Entry distance of the ray into the geom's enlarged world bounds: a lower bound of the exact test's t
-// whenever that test hits (the bounds' margin, >= 1e-3 x extent + 1e-3, exceeds the exact test's 1e-4
-// pull-back along the object-space direction, <= 1e-4 x the largest scale, plus rounding).  false: the
-// exact test would miss (as geom_may_hit).
+// Conservative skip test for one analytic geom (invdir finite), for any origin: false only when the exact test
+// would miss (k_brute, k_viz; prep_ray decides once per ray, geoms_hold_for).
+KDPT_HD bool geom_may_hit(const DevGeom& G, f3 o, f3 invdir) {
+  // the origin's Chebyshev distance from the bounds (negative inside) against the proven range
+  const float away = fmaxf(fmaxf(fmaxf(G.wlo[0] - o.x, o.x - G.whi[0]), fmaxf(G.wlo[1] - o.y, o.y - G.whi[1])),
+                           fmaxf(G.wlo[2] - o.z, o.z - G.whi[2]));
+  return !(away <= G.wlo[3]) || geom_bounds_hit(G, o, invdir);
+}
+
+// Entry parameter of the ray into the geom's enlarged world bounds: a lower bound of the exact test's t
+// whenever that test hits, for an origin within the geom's proven range (above; prep_ray asks
+// geoms_hold_for).  false: the exact test would miss.
 KDPT_HD bool geom_entry_bound(const DevGeom& G, f3 o, f3 invdir, float& lo) {
   const float t1x = (G.wlo[0] - o.x) * invdir.x, t2x = (G.whi[0] - o.x) * invdir.x;
   const float t1y = (G.wlo[1] - o.y) * invdir.y, t2y = (G.whi[1] - o.y) * invdir.y;
@@ -164,6 +214,9 @@ struct DevScene {
   const float4* c_e1;
   const float4* c_e2;
   float4 rlo, rhi;  // the KD root's box (trace-order classes only; not used for results)
+  // the ray origins for which every analytic geom's bounds hold (geoms_hold_for): the box of centre gc and
+  // half-sizes gh; a negative half-size: none
+  float4 gc, gh;
   int trace_mode;   // 1 class+octant, 2 octant, 3 class (experiments)
   int early_walk, early_leaf;  // leaf phase starts when <= early_walk lanes walk and >= early_leaf wait
   int trip_limit;  // bound on node steps per ray (a valid tree needs < 4 per node)
@@ -276,6 +329,85 @@ __device__ inline bool intersectAABB_fast(f3 o, f3 invdir, float4 b0, float4 b1,
   return !(dmax < 0.0f) && !(dmin > dmax);
 }
 #endif
+
+// The intersect stage's first part for one ray: the analytic geoms of pathTraceOneBounceKDbare (tested
+// before the KD tree; src/pathtrace.cu:1600-1640) -> t_min / hit, and the traversal's first step, the
+// KD root's box (same intersectAABB, same invdir): false = the traversal ends there.
+KDPT_HD bool geoms_hold_for(const DevScene& S, f3 o) {
+  return fmaxf(fmaxf(fabsf(o.x - S.gc.x) - S.gh.x, fabsf(o.y - S.gc.y) - S.gh.y), fabsf(o.z - S.gc.z) - S.gh.z) <= 0.0f;
+}
+constexpr int ORDERED_GEOMS = 8;  // scenes with at most this many analytic geoms test them nearest-first
+KDPT_HDI bool prep_ray(const DevScene& S, bool kd, f3 o, f3 d, float& t_min, int& hit) {
+  Ray ray;
+  ray.origin = o;
+  ray.direction = d;
+  ray.isinside = false;
+  ray.sdepth = 0.0f;
+  t_min = FLT_MAXV;
+  hit = -1;
+  f3 tmp_i = mk3(0, 0, 0), tmp_n = mk3(0, 0, 0);
+  const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+  const bool finite = fabsf(inv.x) < FLT_INFV && fabsf(inv.y) < FLT_INFV && fabsf(inv.z) < FLT_INFV;
+  const int ng = S.num_geoms;
+  const bool held = geoms_hold_for(S, o);  // the geoms' bounds say something about this ray
+  if (finite && ng <= ORDERED_GEOMS) {
+    // Nearest-first: the reference keeps the first geom (index order) reaching the smallest t > 0; here
+    // the geoms whose bounds the ray enters are tested in order of their entry bound, stopping once that
+    // bound exceeds the best t, and ties go to the lower index -- the same winner and the same t, with
+    // typically one or two exact tests per ray instead of one per geom the wave's rays come near.
+    // An origin the bounds do not hold for enters every geom at -inf: all are tested, in index order.
+    float lo[ORDERED_GEOMS];
+    uint32_t pending = 0;
+#pragma unroll
+    for (int g = 0; g < ORDERED_GEOMS; g++) {
+      lo[g] = FLT_INFV;
+      if (g < ng) {
+        const bool enters = geom_entry_bound(S.geoms[g], o, inv, lo[g]);
+        if (!held) lo[g] = -FLT_INFV;
+        if (enters || !held) pending |= 1u << g;
+      }
+    }
+    while (pending) {
+      int gb = 0;
+      float lb = FLT_INFV;
+#pragma unroll
+      for (int g = 0; g < ORDERED_GEOMS; g++)
+        if (((pending >> g) & 1u) && lo[g] < lb) {
+          lb = lo[g];
+          gb = g;
+        }
+      if (lb > t_min) break;  // every remaining geom's exact t exceeds the best
+      pending &= ~(1u << gb);
+      const DevGeom& G = S.geoms[gb];
+      const float t = G.type == 1 ? boxIntersectionTest(G, ray, tmp_i, tmp_n)
+                                  : sphereIntersectionTest(G, ray, tmp_i, tmp_n);
+      if (t > 0.0f && (t < t_min || (t == t_min && gb < hit))) {
+        t_min = t;
+        hit = gb;
+      }
+    }
+  } else {
+    float t = 0;
+    for (int g = 0; g < ng; g++) {
+      const DevGeom& G = S.geoms[g];
+      if (finite && held && !geom_bounds_hit(G, o, inv)) {
+        t = -1.0f;  // the exact test would miss
+      } else if (G.type == 1) {
+        t = boxIntersectionTest(G, ray, tmp_i, tmp_n);
+      } else if (G.type == 0) {
+        t = sphereIntersectionTest(G, ray, tmp_i, tmp_n);
+      }
+      if (t > 0.0f && t_min > t) {
+        t_min = t;
+        hit = g;
+      }
+    }
+  }
+  if (!kd) return false;
+  float dist;
+  return intersectAABB(o, inv, make_float4(S.rlo.x, S.rlo.y, S.rlo.z, S.rhi.x),
+                       make_float4(S.rhi.y, S.rhi.z, 0.0f, 0.0f), dist);
+}
 
 struct Hit {
   float t_min;

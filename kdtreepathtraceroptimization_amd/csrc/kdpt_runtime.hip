@@ -599,13 +599,15 @@ int build_masks(kdpt_ctx* c, int n) {
 //     "tree_global", syn20000, "tree_format" 32, "tree_format" 16); LDS16G, LDS16S, H and B -- test_cast_equals_oracle
 //     (ico7, ico7-margin); in renders test_tuning_knobs_keep_parity, test_derived_box_tree_in_lds
 //   k_trace, count on: TREE_WIDE, PACKED, LDS, LDS16, H and B -- test_soup_counters_on_every_route; LDS, H also
-//     test_counters_match_oracle; LDS16G, LDS16S -- no test (bench.py --full counts C5 on LDS16S)
+//     test_counters_match_oracle; LDS16G, LDS16S, H -- test_counters_on_the_cluster_routes (B: no test)
 //   k_shade: compact + sort -- test_iteration2_sort_order (H), test_bit_exact_vs_oracle dragon_96_bare (B); compact
 //     alone -- test_fused_shading_equals_scan_scatter (H); neither -- test_bit_exact_vs_oracle dragon_64_nocompact
-//     (H); sort alone -- test_brute_force_bit_exact_vs_oracle sphere_48_brute_nocompact (H); B, those three: no test
+//     (H); sort alone -- test_brute_force_bit_exact_vs_oracle sphere_48_brute_nocompact (H); B, those three --
+//     test_geom_render_equals_oracle ("shade_fused" 0 and compaction 0 with short_stack 0, iterations 1 and 2)
 //   k_shade_fused_b: STAGE -- every default render (H), dragon_96_bare (B); not STAGE (a scene of more than
-//     ORDERED_GEOMS geoms or STAGE_MATS materials) -- no test; k_shade_fused: H + STAGE --
-//     test_tuning_knobs_keep_parity "shade_batch"; the other three -- no test
+//     ORDERED_GEOMS geoms or STAGE_MATS materials) -- test_geom_render_equals_oracle nine, mats33, mats64 (H and B);
+//     k_shade_fused: H + STAGE -- test_tuning_knobs_keep_parity "shade_batch"; the other three --
+//     test_geom_render_equals_oracle "shade_batch" 0 (tilted, nested, glass: STAGE; nine, mats33, mats64: not)
 //   k_brute: count on -- test_brute_force_counters_match_oracle (use_bbox 0, 1); off --
 //     test_brute_force_bit_exact_vs_oracle (both); k_cast_resolve: H and B -- test_cast_equals_oracle
 // ---------------------------------------------------------------------------
@@ -652,6 +654,10 @@ FusedBatchKernel shade_fused_batch_kernel(bool hybrid, bool stage) {
   static const FusedBatchKernel table[2][2] = {{k_shade_fused_b<false, false>, k_shade_fused_b<false, true>},
                                                {k_shade_fused_b<true, false>, k_shade_fused_b<true, true>}};
   return table[hybrid][stage];
+}
+// the fused kernels' STAGE argument: the scene's geoms and materials fit their LDS copy
+bool shade_staged(const kdpt_ctx* c) {
+  return c->S.num_geoms + c->S.num_boxes <= ORDERED_GEOMS && c->S.num_materials <= STAGE_MATS;
 }
 using BruteKernel = void (*)(BruteArgs);
 BruteKernel brute_kernel(bool use_bbox, bool count) {
@@ -868,6 +874,8 @@ int kdpt_create(const kdpt_scene* sc, const kdpt_options* opt, int device, kdpt_
   S.n1_right = p.n1_right;
   S.rlo = p.rlo;
   S.rhi = p.rhi;
+  S.gc = p.gc;
+  S.gh = p.gh;
   set_cull(c, p.cull);
   if (p.kd || p.brute) {
     float4 *dtv, *de1, *de2, *dn0, *dn1, *dn2;
@@ -1319,6 +1327,12 @@ int kdpt_trace_config(kdpt_ctx* c, int* tree_mode, int* block, int* grid, long l
   if (block) *block = trace_kernel(false, false, m).block;
   if (grid) *grid = c->full_trace_grid;
   if (lds_bytes) *lds_bytes = (long long)c->tree_lds;
+  return KDPT_OK;
+}
+
+int kdpt_shade_staged(kdpt_ctx* c, int* staged) {
+  if (!c || !staged) return fail(KDPT_ERR_ARG, "null arg");
+  *staged = shade_staged(c) ? 1 : 0;
   return KDPT_OK;
 }
 
@@ -1840,7 +1854,7 @@ int shade_scan_scatter(const Batch& B, IterState* it, const ShadeArgs& a, bool s
 int shade_stage(const Batch& B, int depth, bool prep_next) {
   kdpt_ctx* c = B.c;
   const bool hyb = hybrid_shading(c);
-  const bool stage = c->S.num_geoms + c->S.num_boxes <= ORDERED_GEOMS && c->S.num_materials <= STAGE_MATS;
+  const bool stage = shade_staged(c);
   const int shade_grid = (c->npix + SHADE_TB - 1) / SHADE_TB;
   ShadeBatch sbatch;
   int nfused = 0;

@@ -9,7 +9,9 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <utility>
 #include <vector>
@@ -61,6 +63,7 @@ struct PreparedScene {
   int num_supers = 0;        // 0 as well when a super box is not finite in half precision
   int cl_counts = 0;         // DevScene::cl_counts
   float4 rlo = make_float4(0, 0, 0, 0), rhi = make_float4(0, 0, 0, 0);  // the root's box
+  float4 gc = make_float4(0, 0, 0, 0), gh = make_float4(0, 0, 0, 0);  // geoms_safe_region of the scene's geoms
   int n0_left = -1, n0_right = -1, n1_left = -1, n1_right = -1;
   std::vector<BruteShape> shapes;         // brute
   std::vector<float4> chunk_lo, chunk_hi;  // brute: boxes of 64 file-order triangles
@@ -206,8 +209,63 @@ inline void choose_clusters(const kdpt_node_bare* nodes, int nn, const kdpt_tri_
   }
 }
 
+// The Chebyshev distance from a geom's enlarged bounds within which a ray origin may rely on them: the largest R
+// of a halving sequence for which the exact test's error, bounded as kdpt_device.h derives it ("The analytic
+// geoms' bounds"), fits the margin; -inf when none does.  m, mi: transform and inverseTransform (column-major);
+// lo, hi: the exact world bounds.
+inline float geom_safe_range(int type, const float* m, const float* mi, const double* lo, const double* hi,
+                             double margin) {
+  const double u = 5.9604644775390625e-8;  // 2^-24
+  const double inf = std::numeric_limits<double>::infinity();
+  for (int k = 0; k < 16; k++)
+    if (!std::isfinite(m[k]) || !std::isfinite(mi[k])) return (float)-inf;
+  // (the exact tests read the first three rows of either matrix only: mulMV)
+  double A[3][3], Ai[3][3], E[3][3], e[3], gi[3], ext = 0, cmax = 0, fro = 0, emax = 0;
+  for (int r = 0; r < 3; r++)
+    for (int j = 0; j < 3; j++) {
+      A[r][j] = m[4 * j + r];
+      Ai[r][j] = mi[4 * j + r];
+    }
+  for (int r = 0; r < 3; r++) {
+    gi[r] = std::fabs(Ai[r][0]) + std::fabs(Ai[r][1]) + std::fabs(Ai[r][2]);
+    fro += Ai[r][0] * Ai[r][0] + Ai[r][1] * Ai[r][1] + Ai[r][2] * Ai[r][2];
+    e[r] = Ai[r][0] * m[12] + Ai[r][1] * m[13] + Ai[r][2] * m[14] + mi[12 + r];
+    for (int j = 0; j < 3; j++)
+      E[r][j] = Ai[r][0] * A[0][j] + Ai[r][1] * A[1][j] + Ai[r][2] * A[2][j] - (r == j ? 1.0 : 0.0);
+    ext = std::max(ext, hi[r] - lo[r]);
+    cmax = std::max(cmax, std::max(std::fabs(lo[r]), std::fabs(hi[r])) + margin);
+    emax = std::max(emax, std::fabs(e[r]));
+  }
+  fro = std::sqrt(fro);
+  auto fits = [&](double R) {
+    const double reach = R + margin + ext;  // of the origin from any point of the object, per axis
+    const double W = cmax + R;              // magnitude of every world coordinate involved
+    const double Dw = 2.0 * reach;          // >= sqrt(3) reach: the world distance from the origin to the hit
+    double Dq[3];
+    for (int j = 0; j < 3; j++) Dq[j] = gi[j] * reach + std::fabs(e[j]) + 1.0;  // object-space coordinates up to the hit
+    // (c): the origin's object-space distance, |inverse (o - centre)| <= |inverse|_F sqrt(3) (R + margin + ext / 2);
+    // radius^2 grows by at most 16 u (D + 1)^2 (kdpt_device.h), the radius 0.5 by no more than that
+    const double D2 = 1.7320508075688772 * (fro * (R + margin + 0.5 * ext) + emax) + 1.0;
+    const double radicand = type == 0 ? 16.0 * u * D2 * D2 : 0.0;
+    double dq[3];
+    for (int j = 0; j < 3; j++)
+      dq[j] = 8.0 * u * (gi[j] * (W + Dw) + std::fabs((double)mi[12 + j]) + Dq[j])                     // (a)
+              + std::fabs(E[j][0]) * Dq[0] + std::fabs(E[j][1]) * Dq[1] + std::fabs(E[j][2]) * Dq[2]  // (b)
+              + std::fabs(e[j]) + radicand;
+    double err = 0;
+    for (int r = 0; r < 3; r++)
+      err = std::max(err, std::fabs(A[r][0]) * dq[0] + std::fabs(A[r][1]) * dq[1] + std::fabs(A[r][2]) * dq[2]);
+    err += 16.0 * u * W + 5.1e-7 * Dw;  // the point through `transform`, t = |o - point|, the entry parameter; (e)
+    return 4.0 * err + 1.0001e-4 * ext <= margin;  // (d)
+  };
+  if (!(margin > 0) || !fits(0.0)) return (float)-inf;
+  double R = 1024.0 * (ext + 1.0);
+  while (!fits(R) && R > 1e-30) R *= 0.5;
+  return fits(R) ? (float)R : 0.0f;
+}
+
 // DevGeom of a kdpt_geom: its matrices and the world bounds of the transformed unit cube (which contains the
-// transformed unit sphere), + margin.
+// transformed unit sphere), + margin, and the range of ray origins the bounds hold for.
 inline DevGeom prepare_geom(const kdpt_geom& g) {
   DevGeom d{};
   d.type = g.type;
@@ -226,13 +284,37 @@ inline DevGeom prepare_geom(const kdpt_geom& g) {
     }
   }
   const double ext = std::max(std::max(hi[0] - lo[0], hi[1] - lo[1]), hi[2] - lo[2]);
-  const double margin = 1e-3 * ext + 1e-3;
+  // (a sphere fills half of these bounds; its wider margin buys the range the sphere test's radicand needs)
+  const double margin = (g.type == 0 ? 1e-2 : 1e-3) * ext + 1e-3;
   for (int r = 0; r < 3; r++) {
     d.wlo[r] = (float)(lo[r] - margin);
     d.whi[r] = (float)(hi[r] + margin);
   }
-  d.wlo[3] = d.whi[3] = 0.0f;
+  d.wlo[3] = geom_safe_range(g.type, g.transform, g.inverseTransform, lo, hi, margin);
+  d.whi[3] = 0.0f;
   return d;
+}
+
+// The ray origins for which the bounds of all n geoms hold: the intersection of their bounds grown by their
+// ranges (wlo[3]), as centre and half-sizes (shrunk by more than their and the test's rounding); a negative
+// half-size when there is none.
+inline void geoms_safe_region(const DevGeom* g, int n, float4& centre, float4& half) {
+  const double inf = std::numeric_limits<double>::infinity();
+  float c[3], h[3];
+  for (int r = 0; r < 3; r++) {
+    double l = -1e30, u = 1e30;  // (no geoms: every finite origin)
+    for (int i = 0; i < n; i++) {
+      l = std::max(l, (double)g[i].wlo[r] - (double)g[i].wlo[3]);
+      u = std::min(u, (double)g[i].whi[r] + (double)g[i].wlo[3]);
+    }
+    const bool none = !(l <= u) || l == inf || u == -inf;
+    c[r] = none ? 0.0f : (float)(0.5 * (l + u));
+    // |o - c| - h in float is off by a few 2^-24 of |o| + |c| + h, and |o| <= |c| + h where it matters
+    const double hh = 0.5 * (u - l) - 1e-6 * (std::fabs(0.5 * (l + u)) + 0.5 * (u - l));
+    h[r] = none || !(hh >= 0) ? -1.0f : (float)hh;
+  }
+  centre = make_float4(c[0], c[1], c[2], 0.0f);
+  half = make_float4(h[0], h[1], h[2], 0.0f);
 }
 
 inline DevMaterial prepare_material(const kdpt_material& m) {
@@ -413,6 +495,7 @@ inline int prepare_scene(const kdpt_scene* sc, const kdpt_options* opt, double c
   p.num_boxes = p.viz ? sc->num_nodes : 0;
   p.geoms.reserve((size_t)std::max(0, p.num_geoms) + (size_t)p.num_boxes);
   for (int i = 0; i < sc->num_geoms; i++) p.geoms.push_back(prepare_geom(sc->geoms[i]));
+  geoms_safe_region(p.geoms.data(), p.num_geoms, p.gc, p.gh);
   for (int k = 0; k < p.num_boxes; k++) {
     kdpt_geom g{};
     g.type = 1;

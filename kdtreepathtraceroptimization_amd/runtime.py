@@ -139,7 +139,7 @@ EXPORTS = [
     "kdpt_scene_kd_build_ms", "kdpt_build_kd_device", "kdpt_scene_load_device", "kdpt_trace_config",
     "kdpt_cull_margin", "kdpt_comm_unique_id", "kdpt_comm_init", "kdpt_render_frames", "kdpt_render_sharded",
     "kdpt_comm_library", "kdpt_cull_masks", "kdpt_cast_rays", "kdpt_cast_stats",
-    "kdpt_set_camera", "kdpt_camera_rays", "kdpt_trace_rays", "kdpt_trace_rays_stats",
+    "kdpt_set_camera", "kdpt_camera_rays", "kdpt_trace_rays", "kdpt_trace_rays_stats", "kdpt_shade_staged",
 ]
 
 REDUCE_RCCL, REDUCE_COPY = 0, 1  # kdpt_render_sharded's reduce (KDPT_REDUCE_*)
@@ -193,6 +193,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.kdpt_trace_config.argtypes = [C.c_void_p, P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_longlong)]
     if hasattr(lib, "kdpt_cull_margin"):  # absent from older builds used in A/B runs
         lib.kdpt_cull_margin.argtypes = [C.c_void_p, P(C.c_float), P(C.c_double), P(C.c_int)]
+    if hasattr(lib, "kdpt_shade_staged"):
+        lib.kdpt_shade_staged.argtypes = [C.c_void_p, P(C.c_int)]
     if hasattr(lib, "kdpt_cull_masks"):
         lib.kdpt_cull_masks.argtypes = [C.c_void_p, P(C.c_int), P(C.c_int), C.c_void_p]
     if hasattr(lib, "kdpt_render_frames"):
@@ -635,6 +637,10 @@ class PathTracer:
             n, ncl = C.c_int(), C.c_int()
             _check(self.lib.kdpt_cull_masks(self._ctx, C.byref(n), C.byref(ncl), None), "kdpt_cull_masks")
             out["cull_mask_n"] = n.value
+        if hasattr(self.lib, "kdpt_shade_staged"):
+            st = C.c_int()
+            _check(self.lib.kdpt_shade_staged(self._ctx, C.byref(st)), "kdpt_shade_staged")
+            out["shade_staged"] = bool(st.value)  # the fused shading kernels' geoms and materials in LDS
         return out
 
     def cull_margin(self) -> dict:
