@@ -431,6 +431,9 @@ int kdpt_trace_rays(kdpt_ctx *ctx, const float *origins, const float *directions
 int kdpt_trace_rays_stats(kdpt_ctx *ctx, long long *segments, long long *traced, double *device_ms);
 
 int kdpt_destroy(kdpt_ctx *ctx);
+/* The message of the most recent failing call of any kdpt_* function on the calling thread (each thread has its
+ * own; "" before the first failure).  A successful call leaves it alone, so read it only after a non-OK return.
+ * The pointer is valid until that thread's next failing call. */
 const char *kdpt_last_error(void);
 
 /* Device pointer of the accumulation image (for an in-place RCCL reduce). */

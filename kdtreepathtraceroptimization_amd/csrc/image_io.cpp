@@ -13,14 +13,19 @@
 //   HDR: Radiance RGBE ("32-bit_rle_rgbe"), stb's header, per-channel RLE scanlines for
 //        8 <= width < 32768, raw RGBE otherwise; RGBE from frexp of the largest component.
 // stb_image_write v0.98 (Sean Barrett) is public domain: THIRD_PARTY_NOTICES.md.
+#include <cerrno>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "../../include/kdpt.h"
+#include "kdpt_error.h"
+
+using kdpt::fail;
 
 namespace {
 
@@ -313,9 +318,10 @@ std::vector<uint8_t> hdr_encode(const float* rgb, int w, int h) {
 }
 
 int to_caller(const std::vector<uint8_t>& v, uint8_t** out, size_t* len) {
-  if (!out || !len) return KDPT_ERR_ARG;
+  if (!out) return fail(KDPT_ERR_ARG, "image encode: null out");
+  if (!len) return fail(KDPT_ERR_ARG, "image encode: null len");
   *out = (uint8_t*)malloc(v.size() ? v.size() : 1);
-  if (!*out) return KDPT_ERR_IO;
+  if (!*out) return fail(KDPT_ERR_IO, "image encode: cannot allocate " + std::to_string(v.size()) + " bytes");
   memcpy(*out, v.data(), v.size());
   *len = v.size();
   return KDPT_OK;
@@ -323,10 +329,20 @@ int to_caller(const std::vector<uint8_t>& v, uint8_t** out, size_t* len) {
 
 int to_file(const std::vector<uint8_t>& v, const char* path) {
   FILE* f = fopen(path, "wb");
-  if (!f) return KDPT_ERR_IO;
+  if (!f) return fail(KDPT_ERR_IO, std::string("cannot open ") + path + " for writing: " + strerror(errno));
+  errno = 0;
   const size_t n = fwrite(v.data(), 1, v.size(), f);
-  const int rc = fclose(f);
-  return (n == v.size() && rc == 0) ? KDPT_OK : KDPT_ERR_IO;
+  const int werr = errno, rc = fclose(f);
+  if (n == v.size() && rc == 0) return KDPT_OK;
+  return fail(KDPT_ERR_IO, std::string("cannot write ") + path + ": " + strerror(werr ? werr : errno));
+}
+
+// the arguments every encoder takes
+int bad_image(const char* fn, const void* rgb, int w, int h) {
+  if (!rgb) return fail(KDPT_ERR_ARG, std::string(fn) + ": null rgb");
+  if (w <= 0) return fail(KDPT_ERR_ARG, std::string(fn) + ": w must be positive, got " + std::to_string(w));
+  if (h <= 0) return fail(KDPT_ERR_ARG, std::string(fn) + ": h must be positive, got " + std::to_string(h));
+  return KDPT_OK;
 }
 
 }  // namespace
@@ -334,22 +350,24 @@ int to_file(const std::vector<uint8_t>& v, const char* path) {
 extern "C" {
 
 int kdpt_png_encode(const uint8_t* rgb, int w, int h, uint8_t** out, size_t* len) {
-  if (!rgb || w <= 0 || h <= 0) return KDPT_ERR_ARG;
+  if (int rc = bad_image("kdpt_png_encode", rgb, w, h)) return rc;
   return to_caller(png_encode(rgb, w, h, 3), out, len);
 }
 
 int kdpt_write_png(const char* path, const uint8_t* rgb, int w, int h) {
-  if (!path || !rgb || w <= 0 || h <= 0) return KDPT_ERR_ARG;
+  if (!path) return fail(KDPT_ERR_ARG, "kdpt_write_png: null path");
+  if (int rc = bad_image("kdpt_write_png", rgb, w, h)) return rc;
   return to_file(png_encode(rgb, w, h, 3), path);
 }
 
 int kdpt_hdr_encode(const float* rgb, int w, int h, uint8_t** out, size_t* len) {
-  if (!rgb || w <= 0 || h <= 0) return KDPT_ERR_ARG;
+  if (int rc = bad_image("kdpt_hdr_encode", rgb, w, h)) return rc;
   return to_caller(hdr_encode(rgb, w, h), out, len);
 }
 
 int kdpt_write_hdr(const char* path, const float* rgb, int w, int h) {
-  if (!path || !rgb || w <= 0 || h <= 0) return KDPT_ERR_ARG;
+  if (!path) return fail(KDPT_ERR_ARG, "kdpt_write_hdr: null path");
+  if (int rc = bad_image("kdpt_write_hdr", rgb, w, h)) return rc;
   return to_file(hdr_encode(rgb, w, h), path);
 }
 

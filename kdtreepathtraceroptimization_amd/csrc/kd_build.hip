@@ -28,26 +28,17 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdint>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <type_traits>
+#include <string>
 #include <vector>
 
 #include "kdpt.h"
 #include "kd_build.h"
+#define KDPT_HIP_STAGE "device KD build: "  // what this file's HIP_TRY messages begin with
+#include "kdpt_error.h"
 
 namespace {
-
-// (the failing call and HIP's reason on stderr: the scene-build entry points return only the code)
-#define KD_TRY(x)                                                                                       \
-  do {                                                                                                  \
-    hipError_t e_ = (x);                                                                                \
-    if (e_ != hipSuccess) {                                                                             \
-      fprintf(stderr, "[kdpt] device KD build: %s failed: %s\n", #x, hipGetErrorString(e_));           \
-      return KDPT_ERR_HIP;                                                                              \
-    }                                                                                                   \
-  } while (0)
 
 constexpr int BLK = 256;
 inline int blocks(long long n) { return (int)std::max(1ll, (n + BLK - 1) / BLK); }
@@ -318,19 +309,25 @@ __global__ void k_iota(int* a, int n) {
   if (i < n) a[i] = i;
 }
 
+// ---------------------------------------------------------------- host side
+// Helpers that wrap HIP calls return hipError_t and are called under HIP_TRY, whose message names the call;
+// the stages of the build return the library's int status.
+
 // Device memory owned by one build; freed on every exit path.
 struct Arena {
   std::vector<void*> p;
   ~Arena() {
     for (void* q : p) (void)hipFree(q);
   }
+  hipError_t alloc_bytes(void** out, size_t bytes) {
+    *out = nullptr;
+    hipError_t e = hipMalloc(out, std::max<size_t>(bytes, 1));
+    if (e == hipSuccess) p.push_back(*out);
+    return e;
+  }
   template <typename T>
   hipError_t alloc(T** out, size_t n) {
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T));
-    if (e == hipSuccess) p.push_back(q);
-    *out = (T*)q;
-    return e;
+    return alloc_bytes((void**)out, n * sizeof(T));
   }
   // frees one of the arena's buffers now (the caller has synchronised every use of it)
   hipError_t release(void* q) {
@@ -358,9 +355,253 @@ struct Scanner {
   }
 };
 
-int read_int(const int* d, int* h, hipStream_t st) {
-  KD_TRY(hipMemcpyAsync(h, d, sizeof(int), hipMemcpyDeviceToHost, st));
-  KD_TRY(hipStreamSynchronize(st));
+// The device buffers sized by one capacity (cap + extra elements each).  A buffer is named once, where it is
+// added; allocation and growth are loops over the list, so no buffer can be left at the old size.
+struct BufferGroup {
+  struct Buf {
+    void** p;
+    size_t elem;
+    int extra;
+    size_t bytes(long long cap) const { return (size_t)(cap + extra) * elem; }
+  };
+  long long cap = 0;
+  std::vector<Buf> bufs;
+  template <typename... T>
+  void add(int extra, T**... p) {
+    (bufs.push_back(Buf{(void**)p, sizeof(T), extra}), ...);
+  }
+  hipError_t alloc_all(Arena& A, long long capacity) {
+    cap = capacity;
+    for (const Buf& b : bufs)
+      if (hipError_t e = A.alloc_bytes(b.p, b.bytes(cap))) return e;
+    return hipSuccess;
+  }
+  // Every buffer's contents move to a buffer of the new capacity.  Each old buffer is freed once its own copy
+  // has run, so the peak device memory is the new capacity plus one old buffer, not the sum of every size.
+  hipError_t grow(Arena& A, hipStream_t st, long long new_cap) {
+    for (const Buf& b : bufs) {
+      void* q;
+      hipError_t e = A.alloc_bytes(&q, b.bytes(new_cap));
+      if (e == hipSuccess) e = hipMemcpyAsync(q, *b.p, b.bytes(cap), hipMemcpyDeviceToDevice, st);
+      if (e == hipSuccess) e = hipStreamSynchronize(st);
+      if (e == hipSuccess) e = A.release(*b.p);
+      if (e != hipSuccess) return e;
+      *b.p = q;
+    }
+    cap = new_cap;
+    return hipSuccess;
+  }
+};
+
+// One build, handed from stage to stage.  The groups hold the addresses of its pointers: it is not copied.
+struct Build {
+  const float *v9, *n9;
+  const int* mtl;
+  const int ntri, maxdepth;
+  const hipStream_t st;
+  Arena& A;
+  Scanner scan{nullptr, 0, st, &A};
+  float *d_v9, *d_n9;  // the triangles and their bounds
+  int* d_mtl;
+  float4 *d_tlo, *d_thi;
+  float4 rlo, rhi, rctr;  // the root's box and centre
+  Nodes N{};
+  int *cl, *cr, *nsplit, *npair, *nleaf, *nsplit_ex, *npair_ex, *nleaf_ex;  // a level's nodes: counts, scans
+  int *ptri, *pnode, *ntri_, *nnode;  // (triangle, node) pairs of the current and the next level
+  int *fl, *fr, *sl, *sr;             // a level's pairs: side flags and their scans
+  int *leaf_tri, *leaf_node;          // leaf store
+  BufferGroup nodes, pairs, leaves;
+  std::vector<int> lvl_begin{0}, lvl_count{1};
+  long long leaf_total = 0;
+  int nnodes = 1;
+
+  Build(const float* v9_, const float* n9_, const int* mtl_, int ntri_in, int maxdepth_, hipStream_t st_, Arena& A_)
+      : v9(v9_), n9(n9_), mtl(mtl_), ntri(ntri_in), maxdepth(maxdepth_), st(st_), A(A_) {
+    nodes.add(0, &N.lo, &N.hi, &N.ctr, &N.parent, &N.left, &N.right, &N.axis, &N.split_pos, &N.pstart, &N.pcnt,
+              &N.leaf_start, &N.leaf_cnt, &N.size, &N.id, &cl, &cr);
+    nodes.add(1, &nsplit, &npair, &nleaf, &nsplit_ex, &npair_ex, &nleaf_ex);  // scans: a total slot each
+    pairs.add(0, &ptri, &pnode, &ntri_, &nnode);
+    pairs.add(1, &fl, &fr, &sl, &sr);
+    leaves.add(0, &leaf_tri, &leaf_node);
+  }
+  Build(const Build&) = delete;
+};
+
+int upload_stage(Build& B) {
+  const size_t n = (size_t)B.ntri;
+  HIP_TRY(B.A.alloc(&B.d_v9, 9 * n));
+  HIP_TRY(B.A.alloc(&B.d_n9, 9 * n));
+  HIP_TRY(B.A.alloc(&B.d_mtl, n));
+  HIP_TRY(B.A.alloc(&B.d_tlo, n));
+  HIP_TRY(B.A.alloc(&B.d_thi, n));
+  HIP_TRY(hipMemcpyAsync(B.d_v9, B.v9, 36 * n, hipMemcpyHostToDevice, B.st));
+  HIP_TRY(hipMemcpyAsync(B.d_n9, B.n9, 36 * n, hipMemcpyHostToDevice, B.st));
+  HIP_TRY(hipMemcpyAsync(B.d_mtl, B.mtl, 4 * n, hipMemcpyHostToDevice, B.st));
+  hipLaunchKernelGGL(k_tri_bounds, dim3(blocks(B.ntri)), dim3(BLK), 0, B.st, B.d_v9, B.ntri, B.d_tlo, B.d_thi);
+  HIP_TRY(hipGetLastError());
+  return KDPT_OK;
+}
+
+// Root box (KDnode::updateBbox): first-occurrence min / max, then the pad (centre not refreshed).
+int root_box_stage(Build& B) {
+  unsigned long long* d_keys;
+  HIP_TRY(B.A.alloc(&d_keys, 6));
+  const unsigned long long init[6] = {~0ull, ~0ull, ~0ull, 0ull, 0ull, 0ull};
+  HIP_TRY(hipMemcpyAsync(d_keys, init, sizeof init, hipMemcpyHostToDevice, B.st));
+  hipLaunchKernelGGL(k_root_keys, dim3(blocks(B.ntri)), dim3(BLK), 0, B.st, B.d_tlo, B.d_thi, B.ntri, d_keys);
+  HIP_TRY(hipGetLastError());
+  unsigned long long keys[6];
+  float4 ext[6];  // per component the bounds that hold its minimum [0..2] and its maximum [3..5]
+  HIP_TRY(hipMemcpyAsync(keys, d_keys, sizeof keys, hipMemcpyDeviceToHost, B.st));
+  HIP_TRY(hipMemcpyAsync(&ext[0], B.d_tlo, sizeof ext[0], hipMemcpyDeviceToHost, B.st));
+  HIP_TRY(hipMemcpyAsync(&ext[3], B.d_thi, sizeof ext[3], hipMemcpyDeviceToHost, B.st));
+  HIP_TRY(hipStreamSynchronize(B.st));
+  ext[1] = ext[2] = ext[0];
+  ext[4] = ext[5] = ext[3];
+  for (int k = 0; k < 6; k++) {
+    // the fold starts from triangle 0 and replaces only on a strict improvement: a NaN at triangle 0 stays;
+    // otherwise the first triangle holding the extreme value
+    const float4 t0 = ext[k];
+    const float v0 = k % 3 == 0 ? t0.x : (k % 3 == 1 ? t0.y : t0.z);
+    const uint32_t t = k < 3 ? (uint32_t)keys[k] : ~(uint32_t)keys[k];
+    if (v0 != v0 || keys[k] == init[k] || t == 0) continue;
+    if (t >= (uint32_t)B.ntri)
+      return kdpt::fail(KDPT_ERR_HIP, "device KD build: root box: the key reduction names triangle " +
+                                          std::to_string(t) + " of " + std::to_string(B.ntri));
+    HIP_TRY(hipMemcpyAsync(&ext[k], (k < 3 ? B.d_tlo : B.d_thi) + t, sizeof ext[k], hipMemcpyDeviceToHost, B.st));
+  }
+  HIP_TRY(hipStreamSynchronize(B.st));
+  float rmin[3], rmax[3], ctr[3];
+  for (int c = 0; c < 3; c++) {
+    rmin[c] = c == 0 ? ext[c].x : (c == 1 ? ext[c].y : ext[c].z);
+    rmax[c] = c == 0 ? ext[3 + c].x : (c == 1 ? ext[3 + c].y : ext[3 + c].z);
+    ctr[c] = (float)((double)(rmin[c] + rmax[c]) / 2.0);  // before the pad
+  }
+  const float pad = (float)0.001;
+  B.rlo = make_float4(rmin[0] - pad, rmin[1] - pad, rmin[2] - pad, 0.0f);
+  B.rhi = make_float4(rmax[0] + pad, rmax[1] + pad, rmax[2] + pad, 0.0f);
+  B.rctr = make_float4(ctr[0], ctr[1], ctr[2], 0.0f);
+  return KDPT_OK;
+}
+
+// The node store, the pair lists and the leaf store at their initial capacities, and the root in them.
+int init_store(Build& B) {
+  const int ntri = B.ntri;
+  // every split makes two non-empty children and levels stop past maxdepth: < 2^(maxdepth + 2) nodes
+  HIP_TRY(B.nodes.alloc_all(
+      B.A, std::max<long long>(1024, std::min<long long>(4ll * ntri + 16, 1ll << std::min(B.maxdepth + 2, 20)))));
+  HIP_TRY(B.pairs.alloc_all(B.A, std::max<long long>(3 * (long long)ntri, 1024)));
+  HIP_TRY(B.leaves.alloc_all(B.A, std::max<long long>(3 * (long long)ntri, 1024)));
+  // root: KDnode defaults (axis 0, splitPos 0, parent -1), all triangles in file order
+  const int m1 = -1, z = 0;
+  const float zf = 0.0f;
+  const Nodes& N = B.N;
+  HIP_TRY(hipMemcpyAsync(N.lo, &B.rlo, sizeof B.rlo, hipMemcpyHostToDevice, B.st));
+  HIP_TRY(hipMemcpyAsync(N.hi, &B.rhi, sizeof B.rhi, hipMemcpyHostToDevice, B.st));
+  HIP_TRY(hipMemcpyAsync(N.ctr, &B.rctr, sizeof B.rctr, hipMemcpyHostToDevice, B.st));
+  HIP_TRY(hipMemcpyAsync(N.parent, &m1, 4, hipMemcpyHostToDevice, B.st));
+  HIP_TRY(hipMemcpyAsync(N.axis, &z, 4, hipMemcpyHostToDevice, B.st));
+  HIP_TRY(hipMemcpyAsync(N.split_pos, &zf, 4, hipMemcpyHostToDevice, B.st));
+  HIP_TRY(hipMemcpyAsync(N.pstart, &z, 4, hipMemcpyHostToDevice, B.st));
+  HIP_TRY(hipMemcpyAsync(N.pcnt, &ntri, 4, hipMemcpyHostToDevice, B.st));
+  HIP_TRY(hipMemcpyAsync(N.id, &z, 4, hipMemcpyHostToDevice, B.st));
+  hipLaunchKernelGGL(k_iota, dim3(blocks(ntri)), dim3(BLK), 0, B.st, B.ptri, ntri);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemsetAsync(B.pnode, 0, 4 * (size_t)ntri, B.st));
+  return KDPT_OK;
+}
+
+// The level loop, breadth first.  A level's node count and pair count are known before its children are made, so
+// the stores grow inside the loop (capacity doubling): the level's flags and scans are already in place, only
+// the next level's outputs need the larger capacity (rare: the initial capacities cover the reference meshes).
+int levels_stage(Build& B) {
+  if (int rc = init_store(B)) return rc;
+  const hipStream_t st = B.st;
+  long long npairs = B.ntri;
+  for (int level = 0;; level++) {
+    const int nl = B.lvl_count.back(), lb = B.lvl_begin.back();
+    if (nl == 0) break;
+    LevelArgs L{level, level % 3, B.maxdepth, lb, nl, npairs};
+    hipLaunchKernelGGL(k_side, dim3(blocks(npairs + 1)), dim3(BLK), 0, st, L, B.ptri, B.pnode, B.N, B.d_tlo, B.d_thi,
+                       B.fl, B.fr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(B.scan.exclusive(B.fl, B.sl, npairs + 1));
+    HIP_TRY(B.scan.exclusive(B.fr, B.sr, npairs + 1));
+    hipLaunchKernelGGL(k_decide, dim3(blocks(nl + 1)), dim3(BLK), 0, st, L, B.N, B.sl, B.sr, B.nsplit, B.npair, B.nleaf,
+                       B.cl, B.cr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(B.scan.exclusive(B.nsplit, B.nsplit_ex, nl + 1));
+    HIP_TRY(B.scan.exclusive(B.npair, B.npair_ex, nl + 1));
+    HIP_TRY(B.scan.exclusive(B.nleaf, B.nleaf_ex, nl + 1));
+    int tot[3];
+    HIP_TRY(hipMemcpyAsync(&tot[0], B.nsplit_ex + nl, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&tot[1], B.npair_ex + nl, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&tot[2], B.nleaf_ex + nl, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const long long nnodes_next = B.nnodes + 2ll * tot[0], npairs_next = tot[1], nleaf_next = B.leaf_total + tot[2];
+    if (nnodes_next > B.nodes.cap) HIP_TRY(B.nodes.grow(B.A, st, std::max(2 * B.nodes.cap, nnodes_next + 16)));
+    if (npairs_next > B.pairs.cap) HIP_TRY(B.pairs.grow(B.A, st, std::max(2 * B.pairs.cap, npairs_next + 16)));
+    if (nleaf_next > B.leaves.cap) HIP_TRY(B.leaves.grow(B.A, st, std::max(2 * B.leaves.cap, nleaf_next + 16)));
+    hipLaunchKernelGGL(k_children, dim3(blocks(nl)), dim3(BLK), 0, st, L, B.N, B.nsplit_ex, B.npair_ex, B.nleaf_ex,
+                       B.nsplit, B.cl, B.cr, (int)B.leaf_total);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_scatter, dim3(blocks(npairs)), dim3(BLK), 0, st, L, B.N, B.ptri, B.pnode, B.fl, B.fr, B.sl,
+                       B.sr, B.nsplit, B.ntri_, B.nnode, B.leaf_tri, B.leaf_node);
+    HIP_TRY(hipGetLastError());
+    std::swap(B.ptri, B.ntri_);
+    std::swap(B.pnode, B.nnode);
+    npairs = npairs_next;
+    B.leaf_total = nleaf_next;
+    B.lvl_begin.push_back(lb + nl);
+    B.lvl_count.push_back(2 * tot[0]);
+    B.nnodes = (int)nnodes_next;
+  }
+  return KDPT_OK;
+}
+
+// Pre-order IDs: subtree sizes bottom-up, then IDs top-down.
+int preorder_stage(Build& B) {
+  const int nlev = (int)B.lvl_count.size();
+  for (int l = nlev - 1; l >= 0; l--) {
+    if (B.lvl_count[l] == 0) continue;
+    hipLaunchKernelGGL(k_sizes, dim3(blocks(B.lvl_count[l])), dim3(BLK), 0, B.st, B.N, B.lvl_begin[l], B.lvl_count[l]);
+    HIP_TRY(hipGetLastError());
+  }
+  for (int l = 0; l < nlev; l++) {
+    if (B.lvl_count[l] == 0) continue;
+    hipLaunchKernelGGL(k_ids, dim3(blocks(B.lvl_count[l])), dim3(BLK), 0, B.st, B.N, B.lvl_begin[l], B.lvl_count[l]);
+    HIP_TRY(hipGetLastError());
+  }
+  return KDPT_OK;
+}
+
+// The leaves' triangles in ID order, then the NodeBare / TriBare arrays and their read-back.
+int emit_stage(Build& B, std::vector<kdpt_node_bare>& nodes_out, std::vector<kdpt_tri_bare>& tris_out) {
+  const int nnodes = B.nnodes;
+  const long long leaf_total = B.leaf_total;
+  int *by_id, *tstart;
+  HIP_TRY(B.A.alloc(&by_id, (size_t)nnodes + 1));
+  HIP_TRY(B.A.alloc(&tstart, (size_t)nnodes + 1));
+  hipLaunchKernelGGL(k_leaf_sizes_by_id, dim3(blocks(nnodes + 1)), dim3(BLK), 0, B.st, B.N, nnodes, by_id);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(B.scan.exclusive(by_id, tstart, nnodes + 1));
+  kdpt_node_bare* d_nodes;
+  kdpt_tri_bare* d_tris;
+  HIP_TRY(B.A.alloc(&d_nodes, (size_t)nnodes));
+  HIP_TRY(B.A.alloc(&d_tris, (size_t)leaf_total));
+  hipLaunchKernelGGL(k_write_nodes, dim3(blocks(nnodes)), dim3(BLK), 0, B.st, B.N, nnodes, tstart, d_nodes);
+  if (leaf_total > 0)
+    hipLaunchKernelGGL(k_write_tris, dim3(blocks(leaf_total)), dim3(BLK), 0, B.st, B.N, leaf_total, B.leaf_tri,
+                       B.leaf_node, tstart, B.d_v9, B.d_n9, B.d_mtl, d_tris);
+  HIP_TRY(hipGetLastError());
+  nodes_out.resize(nnodes);
+  tris_out.resize((size_t)leaf_total);
+  HIP_TRY(hipMemcpyAsync(nodes_out.data(), d_nodes, sizeof(kdpt_node_bare) * (size_t)nnodes, hipMemcpyDeviceToHost,
+                         B.st));
+  if (leaf_total > 0)
+    HIP_TRY(hipMemcpyAsync(tris_out.data(), d_tris, sizeof(kdpt_tri_bare) * (size_t)leaf_total, hipMemcpyDeviceToHost,
+                           B.st));
+  HIP_TRY(hipStreamSynchronize(B.st));
   return KDPT_OK;
 }
 
@@ -374,242 +615,19 @@ int build_kd_device(const float* v9, const float* n9, const int* mtl, int ntri, 
   tris_out.clear();
   if (ntri <= 0) return KDPT_OK;
   const auto t0 = std::chrono::steady_clock::now();
-  KD_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   hipStream_t st;
-  KD_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
   struct StreamGuard {
     hipStream_t s;
     ~StreamGuard() { (void)hipStreamDestroy(s); }
   } sg{st};
   Arena A;
-  float *d_v9, *d_n9;
-  int* d_mtl;
-  float4 *d_tlo, *d_thi;
-  KD_TRY(A.alloc(&d_v9, 9 * (size_t)ntri));
-  KD_TRY(A.alloc(&d_n9, 9 * (size_t)ntri));
-  KD_TRY(A.alloc(&d_mtl, (size_t)ntri));
-  KD_TRY(A.alloc(&d_tlo, (size_t)ntri));
-  KD_TRY(A.alloc(&d_thi, (size_t)ntri));
-  KD_TRY(hipMemcpyAsync(d_v9, v9, 36 * (size_t)ntri, hipMemcpyHostToDevice, st));
-  KD_TRY(hipMemcpyAsync(d_n9, n9, 36 * (size_t)ntri, hipMemcpyHostToDevice, st));
-  KD_TRY(hipMemcpyAsync(d_mtl, mtl, 4 * (size_t)ntri, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_tri_bounds, dim3(blocks(ntri)), dim3(BLK), 0, st, d_v9, ntri, d_tlo, d_thi);
-  KD_TRY(hipGetLastError());
-  // ---- root box (KDnode::updateBbox): first-occurrence min / max, then the pad (centre not refreshed)
-  unsigned long long* d_keys;
-  KD_TRY(A.alloc(&d_keys, 6));
-  {
-    const unsigned long long init[6] = {~0ull, ~0ull, ~0ull, 0ull, 0ull, 0ull};
-    KD_TRY(hipMemcpyAsync(d_keys, init, sizeof init, hipMemcpyHostToDevice, st));
-  }
-  hipLaunchKernelGGL(k_root_keys, dim3(blocks(ntri)), dim3(BLK), 0, st, d_tlo, d_thi, ntri, d_keys);
-  KD_TRY(hipGetLastError());
-  unsigned long long keys[6];
-  float4 lo0, hi0;
-  KD_TRY(hipMemcpyAsync(keys, d_keys, sizeof keys, hipMemcpyDeviceToHost, st));
-  KD_TRY(hipMemcpyAsync(&lo0, d_tlo, sizeof lo0, hipMemcpyDeviceToHost, st));
-  KD_TRY(hipMemcpyAsync(&hi0, d_thi, sizeof hi0, hipMemcpyDeviceToHost, st));
-  KD_TRY(hipStreamSynchronize(st));
-  float rmin[3], rmax[3];
-  {
-    const float l0[3] = {lo0.x, lo0.y, lo0.z}, h0[3] = {hi0.x, hi0.y, hi0.z};
-    for (int c = 0; c < 3; c++) {
-      // the fold starts from triangle 0 and replaces only on a strict improvement: a NaN at triangle 0
-      // stays; otherwise the first triangle holding the extreme value
-      if (l0[c] != l0[c] || keys[c] == ~0ull) {
-        rmin[c] = l0[c];
-      } else {
-        float4 v;
-        KD_TRY(hipMemcpy(&v, d_tlo + (uint32_t)keys[c], sizeof v, hipMemcpyDeviceToHost));
-        rmin[c] = c == 0 ? v.x : (c == 1 ? v.y : v.z);
-      }
-      if (h0[c] != h0[c] || keys[3 + c] == 0ull) {
-        rmax[c] = h0[c];
-      } else {
-        float4 v;
-        KD_TRY(hipMemcpy(&v, d_thi + (uint32_t)~(uint32_t)keys[3 + c], sizeof v, hipMemcpyDeviceToHost));
-        rmax[c] = c == 0 ? v.x : (c == 1 ? v.y : v.z);
-      }
-    }
-  }
-  float4 rlo, rhi, rctr;
-  {
-    float ctr[3];
-    for (int c = 0; c < 3; c++) ctr[c] = (float)((double)(rmin[c] + rmax[c]) / 2.0);  // before the pad
-    const float pad = (float)0.001;
-    rlo = make_float4(rmin[0] - pad, rmin[1] - pad, rmin[2] - pad, 0.0f);
-    rhi = make_float4(rmax[0] + pad, rmax[1] + pad, rmax[2] + pad, 0.0f);
-    rctr = make_float4(ctr[0], ctr[1], ctr[2], 0.0f);
-  }
-  // ---- node store: at most 2 children per split node; a level's node count and pair count are known
-  // before its children are made, so the store grows per level (capacity doubling)
-  // every split makes two non-empty children and levels stop past maxdepth: < 2^(maxdepth + 2) nodes
-  long long cap = std::max<long long>(1024, std::min<long long>(4ll * ntri + 16, 1ll << std::min(maxdepth + 2, 20)));
-  Nodes N{};
-  KD_TRY(A.alloc(&N.lo, cap));
-  KD_TRY(A.alloc(&N.hi, cap));
-  KD_TRY(A.alloc(&N.ctr, cap));
-  KD_TRY(A.alloc(&N.parent, cap));
-  KD_TRY(A.alloc(&N.left, cap));
-  KD_TRY(A.alloc(&N.right, cap));
-  KD_TRY(A.alloc(&N.axis, cap));
-  KD_TRY(A.alloc(&N.split_pos, cap));
-  KD_TRY(A.alloc(&N.pstart, cap));
-  KD_TRY(A.alloc(&N.pcnt, cap));
-  KD_TRY(A.alloc(&N.leaf_start, cap));
-  KD_TRY(A.alloc(&N.leaf_cnt, cap));
-  KD_TRY(A.alloc(&N.size, cap));
-  KD_TRY(A.alloc(&N.id, cap));
-  {  // root: KDnode defaults (axis 0, splitPos 0, parent -1), all triangles in file order
-    const int m1 = -1, z = 0, nt = ntri;
-    const float zf = 0.0f;
-    KD_TRY(hipMemcpyAsync(N.lo, &rlo, sizeof rlo, hipMemcpyHostToDevice, st));
-    KD_TRY(hipMemcpyAsync(N.hi, &rhi, sizeof rhi, hipMemcpyHostToDevice, st));
-    KD_TRY(hipMemcpyAsync(N.ctr, &rctr, sizeof rctr, hipMemcpyHostToDevice, st));
-    KD_TRY(hipMemcpyAsync(N.parent, &m1, 4, hipMemcpyHostToDevice, st));
-    KD_TRY(hipMemcpyAsync(N.axis, &z, 4, hipMemcpyHostToDevice, st));
-    KD_TRY(hipMemcpyAsync(N.split_pos, &zf, 4, hipMemcpyHostToDevice, st));
-    KD_TRY(hipMemcpyAsync(N.pstart, &z, 4, hipMemcpyHostToDevice, st));
-    KD_TRY(hipMemcpyAsync(N.pcnt, &nt, 4, hipMemcpyHostToDevice, st));
-    KD_TRY(hipMemcpyAsync(N.id, &z, 4, hipMemcpyHostToDevice, st));
-  }
-  // pairs of the current and next level (grown as needed), leaf store
-  long long pcap = std::max<long long>(3 * (long long)ntri, 1024), lcap = std::max<long long>(3 * (long long)ntri, 1024);
-  int *ptri, *pnode, *ntri_, *nnode, *fl, *fr, *sl, *sr, *leaf_tri, *leaf_node;
-  KD_TRY(A.alloc(&ptri, pcap));
-  KD_TRY(A.alloc(&pnode, pcap));
-  KD_TRY(A.alloc(&ntri_, pcap));
-  KD_TRY(A.alloc(&nnode, pcap));
-  KD_TRY(A.alloc(&fl, pcap + 1));
-  KD_TRY(A.alloc(&fr, pcap + 1));
-  KD_TRY(A.alloc(&sl, pcap + 1));
-  KD_TRY(A.alloc(&sr, pcap + 1));
-  KD_TRY(A.alloc(&leaf_tri, lcap));
-  KD_TRY(A.alloc(&leaf_node, lcap));
-  hipLaunchKernelGGL(k_iota, dim3(blocks(ntri)), dim3(BLK), 0, st, ptri, ntri);
-  KD_TRY(hipMemsetAsync(pnode, 0, 4 * (size_t)ntri, st));
-  // per-level node scratch (sized for the widest level: < number of nodes)
-  int *nsplit, *npair, *nleaf, *nsplit_ex, *npair_ex, *nleaf_ex, *cl, *cr;
-  KD_TRY(A.alloc(&nsplit, cap + 1));
-  KD_TRY(A.alloc(&npair, cap + 1));
-  KD_TRY(A.alloc(&nleaf, cap + 1));
-  KD_TRY(A.alloc(&nsplit_ex, cap + 1));
-  KD_TRY(A.alloc(&npair_ex, cap + 1));
-  KD_TRY(A.alloc(&nleaf_ex, cap + 1));
-  KD_TRY(A.alloc(&cl, cap));
-  KD_TRY(A.alloc(&cr, cap));
-  Scanner scan{nullptr, 0, st, &A};
-  std::vector<int> lvl_begin{0}, lvl_count{1};
-  long long npairs = ntri, leaf_total = 0;
-  int nnodes = 1;
-  for (int level = 0;; level++) {
-    const int nl = lvl_count.back(), lb = lvl_begin.back();
-    if (nl == 0) break;
-    LevelArgs L{level, level % 3, maxdepth, lb, nl, npairs};
-    hipLaunchKernelGGL(k_side, dim3(blocks(npairs + 1)), dim3(BLK), 0, st, L, ptri, pnode, N, d_tlo, d_thi, fl, fr);
-    KD_TRY(hipGetLastError());
-    KD_TRY(scan.exclusive(fl, sl, npairs + 1));
-    KD_TRY(scan.exclusive(fr, sr, npairs + 1));
-    hipLaunchKernelGGL(k_decide, dim3(blocks(nl + 1)), dim3(BLK), 0, st, L, N, sl, sr, nsplit, npair, nleaf, cl, cr);
-    KD_TRY(hipGetLastError());
-    KD_TRY(scan.exclusive(nsplit, nsplit_ex, nl + 1));
-    KD_TRY(scan.exclusive(npair, npair_ex, nl + 1));
-    KD_TRY(scan.exclusive(nleaf, nleaf_ex, nl + 1));
-    int tot[3];
-    KD_TRY(hipMemcpyAsync(&tot[0], nsplit_ex + nl, 4, hipMemcpyDeviceToHost, st));
-    KD_TRY(hipMemcpyAsync(&tot[1], npair_ex + nl, 4, hipMemcpyDeviceToHost, st));
-    KD_TRY(hipMemcpyAsync(&tot[2], nleaf_ex + nl, 4, hipMemcpyDeviceToHost, st));
-    KD_TRY(hipStreamSynchronize(st));
-    const int nsplit_tot = tot[0];
-    const long long npairs_next = tot[1], nleaf_tot = tot[2];
-    if (nnodes + 2ll * nsplit_tot > cap || npairs_next > pcap || leaf_total + nleaf_tot > lcap) {
-      // grow the buffers and carry on with this level: the level's flags and scans are already in place,
-      // only the next level's outputs need the larger capacity (rare: the initial capacities cover the
-      // reference meshes).  Each replaced buffer is freed once its copy has run, so the peak device
-      // memory is the new capacity plus one old buffer, not the sum of every size.
-      auto grow = [&](auto*& ptr, long long oldn, long long newn) -> hipError_t {
-        using T = std::remove_reference_t<decltype(*ptr)>;
-        T* q;
-        hipError_t e = A.alloc(&q, (size_t)newn);
-        if (e != hipSuccess) return e;
-        e = hipMemcpyAsync(q, ptr, sizeof(T) * (size_t)oldn, hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e == hipSuccess) e = A.release(ptr);
-        ptr = q;
-        return e;
-      };
-      if (nnodes + 2ll * nsplit_tot > cap) {
-        const long long nc = std::max(2 * cap, nnodes + 2ll * nsplit_tot + 16);
-        KD_TRY(grow(N.lo, cap, nc)); KD_TRY(grow(N.hi, cap, nc)); KD_TRY(grow(N.ctr, cap, nc));
-        KD_TRY(grow(N.parent, cap, nc)); KD_TRY(grow(N.left, cap, nc)); KD_TRY(grow(N.right, cap, nc));
-        KD_TRY(grow(N.axis, cap, nc)); KD_TRY(grow(N.split_pos, cap, nc)); KD_TRY(grow(N.pstart, cap, nc));
-        KD_TRY(grow(N.pcnt, cap, nc)); KD_TRY(grow(N.leaf_start, cap, nc)); KD_TRY(grow(N.leaf_cnt, cap, nc));
-        KD_TRY(grow(N.size, cap, nc)); KD_TRY(grow(N.id, cap, nc));
-        KD_TRY(grow(nsplit, cap + 1, nc + 1)); KD_TRY(grow(npair, cap + 1, nc + 1)); KD_TRY(grow(nleaf, cap + 1, nc + 1));
-        KD_TRY(grow(nsplit_ex, cap + 1, nc + 1)); KD_TRY(grow(npair_ex, cap + 1, nc + 1));
-        KD_TRY(grow(nleaf_ex, cap + 1, nc + 1)); KD_TRY(grow(cl, cap, nc)); KD_TRY(grow(cr, cap, nc));
-        cap = nc;
-      }
-      if (npairs_next > pcap) {
-        const long long nc = std::max(2 * pcap, npairs_next + 16);
-        KD_TRY(grow(ntri_, pcap, nc)); KD_TRY(grow(nnode, pcap, nc));
-        KD_TRY(grow(ptri, pcap, nc)); KD_TRY(grow(pnode, pcap, nc));
-        KD_TRY(grow(fl, pcap + 1, nc + 1)); KD_TRY(grow(fr, pcap + 1, nc + 1));
-        KD_TRY(grow(sl, pcap + 1, nc + 1)); KD_TRY(grow(sr, pcap + 1, nc + 1));
-        pcap = nc;
-      }
-      if (leaf_total + nleaf_tot > lcap) {
-        const long long nc = std::max(2 * lcap, leaf_total + nleaf_tot + 16);
-        KD_TRY(grow(leaf_tri, lcap, nc)); KD_TRY(grow(leaf_node, lcap, nc));
-        lcap = nc;
-      }
-    }
-    hipLaunchKernelGGL(k_children, dim3(blocks(nl)), dim3(BLK), 0, st, L, N, nsplit_ex, npair_ex, nleaf_ex, nsplit,
-                       cl, cr, (int)leaf_total);
-    KD_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_scatter, dim3(blocks(npairs)), dim3(BLK), 0, st, L, N, ptri, pnode, fl, fr, sl, sr, nsplit,
-                       ntri_, nnode, leaf_tri, leaf_node);
-    KD_TRY(hipGetLastError());
-    std::swap(ptri, ntri_);
-    std::swap(pnode, nnode);
-    npairs = npairs_next;
-    leaf_total += nleaf_tot;
-    lvl_begin.push_back(lb + nl);
-    lvl_count.push_back(2 * nsplit_tot);
-    nnodes += 2 * nsplit_tot;
-  }
-  // ---- pre-order IDs: subtree sizes bottom-up, then IDs top-down
-  const int nlev = (int)lvl_count.size();
-  for (int l = nlev - 1; l >= 0; l--)
-    if (lvl_count[l] > 0)
-      hipLaunchKernelGGL(k_sizes, dim3(blocks(lvl_count[l])), dim3(BLK), 0, st, N, lvl_begin[l], lvl_count[l]);
-  for (int l = 0; l < nlev; l++)
-    if (lvl_count[l] > 0)
-      hipLaunchKernelGGL(k_ids, dim3(blocks(lvl_count[l])), dim3(BLK), 0, st, N, lvl_begin[l], lvl_count[l]);
-  KD_TRY(hipGetLastError());
-  // ---- leaves' triangles in ID order, then the NodeBare / TriBare arrays
-  int *by_id, *tstart;
-  KD_TRY(A.alloc(&by_id, (size_t)nnodes + 1));
-  KD_TRY(A.alloc(&tstart, (size_t)nnodes + 1));
-  hipLaunchKernelGGL(k_leaf_sizes_by_id, dim3(blocks(nnodes + 1)), dim3(BLK), 0, st, N, nnodes, by_id);
-  KD_TRY(hipGetLastError());
-  KD_TRY(scan.exclusive(by_id, tstart, nnodes + 1));
-  kdpt_node_bare* d_nodes;
-  kdpt_tri_bare* d_tris;
-  KD_TRY(A.alloc(&d_nodes, (size_t)nnodes));
-  KD_TRY(A.alloc(&d_tris, (size_t)leaf_total));
-  hipLaunchKernelGGL(k_write_nodes, dim3(blocks(nnodes)), dim3(BLK), 0, st, N, nnodes, tstart, d_nodes);
-  if (leaf_total > 0)
-    hipLaunchKernelGGL(k_write_tris, dim3(blocks(leaf_total)), dim3(BLK), 0, st, N, leaf_total, leaf_tri, leaf_node,
-                       tstart, d_v9, d_n9, d_mtl, d_tris);
-  KD_TRY(hipGetLastError());
-  nodes_out.resize(nnodes);
-  tris_out.resize((size_t)leaf_total);
-  KD_TRY(hipMemcpyAsync(nodes_out.data(), d_nodes, sizeof(kdpt_node_bare) * (size_t)nnodes, hipMemcpyDeviceToHost, st));
-  if (leaf_total > 0)
-    KD_TRY(hipMemcpyAsync(tris_out.data(), d_tris, sizeof(kdpt_tri_bare) * (size_t)leaf_total, hipMemcpyDeviceToHost,
-                          st));
-  KD_TRY(hipStreamSynchronize(st));
+  Build B(v9, n9, mtl, ntri, maxdepth, st, A);
+  int rc;
+  if ((rc = upload_stage(B)) || (rc = root_box_stage(B)) || (rc = levels_stage(B)) || (rc = preorder_stage(B)) ||
+      (rc = emit_stage(B, nodes_out, tris_out)))
+    return rc;
   if (ms) *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return KDPT_OK;
 }

@@ -40,6 +40,7 @@
 #include <rccl/rccl.h>
 
 #include "../../include/kdpt.h"
+#include "kdpt_error.h"
 #include "kdpt_device.h"
 #include "kdpt_clusters.h"
 #include "kdpt_scene_prep.h"
@@ -48,22 +49,9 @@ using namespace kdpt;
 
 namespace {
 
-thread_local std::string g_last_error;
 double g_reduce_spin_us = 0;  // kdpt_set_tuning(NULL, "reduce_spin_us", v): the default of new contexts
 double g_cluster_chord = -1;   // kdpt_set_tuning(NULL, "cluster_chord", v): big-leaf grouping of new contexts
 bool g_cu_mask_streams = true;  // kdpt_set_tuning(NULL, "cu_mask_streams", v): ... and their stream kind
-
-int fail(int code, const std::string& msg) {
-  g_last_error = msg;
-  return code;
-}
-
-#define HIP_TRY(expr)                                                                      \
-  do {                                                                                     \
-    hipError_t e_ = (expr);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      return fail(KDPT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));        \
-  } while (0)
 
 }  // namespace
 
@@ -379,8 +367,7 @@ int alloc_iter(kdpt_ctx* c, IterState* it, hipStream_t st, bool partial) {
       (rc = dalloc(it, &it->cray, 2 * npix)) || (rc = dalloc(it, &it->tile_counts, (size_t)MAX_KEYS * ntiles)) ||
       (rc = dalloc(it, &it->tile_off, (size_t)MAX_KEYS * ntiles)))
     return rc;
-  if (hipHostMalloc((void**)&it->h_counts, sizeof(int) * (cap + 3), hipHostMallocDefault) != hipSuccess)
-    return fail(KDPT_ERR_HIP, "hipHostMalloc");
+  HIP_TRY(hipHostMalloc((void**)&it->h_counts, sizeof(int) * (cap + 3), hipHostMallocDefault));
   HIP_TRY(hipMemsetAsync(it->counts, 0, sizeof(int) * (4 * cap + 5), st));
   HIP_TRY(hipMemsetAsync(it->lb, 0, sizeof(unsigned long long) * cap * ntiles, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -419,7 +406,7 @@ void drop_groups(kdpt_ctx* c) {
 int make_group(kdpt_ctx* c, int B) {
   c->groups.emplace_back();
   IterGroup& grp = c->groups.back();
-  if (create_stream(c, &grp.stream) != KDPT_OK) return fail(KDPT_ERR_HIP, "hipStreamCreate failed");
+  if (int rc = create_stream(c, &grp.stream)) return rc;
   for (int b = 0; b < B; b++) {
     grp.its.emplace_back(new IterState());
     int rc = alloc_iter(c, grp.its.back().get(), grp.stream, true);
@@ -550,24 +537,26 @@ int build_masks(kdpt_ctx* c, int n) {
   };
   // (the uploads on the context's stream, ahead of the kernel; pageable sources are staged before each call
   // returns, and the stream is drained before the temporaries go)
-  if (hipMalloc((void**)&dm, std::max<size_t>((size_t)nb * ncl, 1) * sizeof(unsigned long long)) != hipSuccess ||
-      hipMalloc(&d_ent, ent.size() * sizeof(double)) != hipSuccess ||
-      hipMalloc(&d_krig, me.krig.size() * sizeof(float)) != hipSuccess ||
-      hipMalloc(&d_bd, bd.size() * sizeof(double)) != hipSuccess ||
-      hipMemcpyAsync(d_ent, ent.data(), ent.size() * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      hipMemcpyAsync(d_krig, me.krig.data(), me.krig.size() * sizeof(float), hipMemcpyHostToDevice, c->stream) !=
+  hipError_t e;
+  if ((e = hipMalloc((void**)&dm, std::max<size_t>((size_t)nb * ncl, 1) * sizeof(unsigned long long))) != hipSuccess ||
+      (e = hipMalloc(&d_ent, ent.size() * sizeof(double))) != hipSuccess ||
+      (e = hipMalloc(&d_krig, me.krig.size() * sizeof(float))) != hipSuccess ||
+      (e = hipMalloc(&d_bd, bd.size() * sizeof(double))) != hipSuccess ||
+      (e = hipMemcpyAsync(d_ent, ent.data(), ent.size() * sizeof(double), hipMemcpyHostToDevice, c->stream)) !=
           hipSuccess ||
-      hipMemcpyAsync(d_bd, bd.data(), bd.size() * sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+      (e = hipMemcpyAsync(d_krig, me.krig.data(), me.krig.size() * sizeof(float), hipMemcpyHostToDevice, c->stream)) !=
+          hipSuccess ||
+      (e = hipMemcpyAsync(d_bd, bd.data(), bd.size() * sizeof(double), hipMemcpyHostToDevice, c->stream)) != hipSuccess) {
     (void)hipStreamSynchronize(c->stream);
     release();
     (void)hipFree(dm);
-    return fail(KDPT_ERR_HIP, "mask build: device buffers");
+    return hip_fail("mask build: device buffers", e);
   }
   hipLaunchKernelGGL(k_build_masks, dim3(ncl, (nb + 255) / 256), dim3(256), 0, c->stream, d_ent, d_krig, d_bd, ncl,
                      nb, Kf, dm);
   const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(c->stream);
   release();
-  int rc = (e1 != hipSuccess || e2 != hipSuccess) ? fail(KDPT_ERR_HIP, "k_build_masks failed") : KDPT_OK;
+  int rc = (e1 != hipSuccess || e2 != hipSuccess) ? hip_fail("k_build_masks", e1 != hipSuccess ? e1 : e2) : KDPT_OK;
   if (!rc && !c->tn_dev) {
     std::vector<float4> tn;
     build_entry_normals(cs, tn);
@@ -800,24 +789,29 @@ struct DeviceFree {
 #ifdef KDPT_TAIL_PROF
 extern "C" int kdpt_debug_tail_prof(unsigned long long* out) {  // sums, then zeroes, the counters
   const unsigned long long zero[4] = {0, 0, 0, 0};
-  if (hipDeviceSynchronize() != hipSuccess) return -1;
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tail_prof), sizeof(zero)) != hipSuccess) return -1;
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_tail_prof), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
+  hipError_t e;
+  if ((e = hipDeviceSynchronize()) != hipSuccess ||
+      (e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tail_prof), sizeof(zero))) != hipSuccess ||
+      (e = hipMemcpyToSymbol(HIP_SYMBOL(g_tail_prof), zero, sizeof(zero))) != hipSuccess)
+    return fail(-1, std::string("kdpt_debug_tail_prof: ") + hipGetErrorString(e));
+  return 0;
 }
 #endif
 #ifdef KDPT_SHADE_PROF
 extern "C" int kdpt_debug_shade_prof(unsigned long long* out) {  // sums, then zeroes, the counters
   const unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (hipDeviceSynchronize() != hipSuccess) return -1;
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_shade_prof), sizeof(zero)) != hipSuccess) return -1;
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_shade_prof), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
+  hipError_t e;
+  if ((e = hipDeviceSynchronize()) != hipSuccess ||
+      (e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_shade_prof), sizeof(zero))) != hipSuccess ||
+      (e = hipMemcpyToSymbol(HIP_SYMBOL(g_shade_prof), zero, sizeof(zero))) != hipSuccess)
+    return fail(-1, std::string("kdpt_debug_shade_prof: ") + hipGetErrorString(e));
+  return 0;
 }
 #endif
 extern "C" {
 
 void kdpt_default_options(kdpt_options* o) { default_options(o); }
 
-const char* kdpt_last_error(void) { return g_last_error.c_str(); }
 
 int kdpt_create(const kdpt_scene* sc, const kdpt_options* opt, int device, kdpt_ctx** out) {
   const auto t_create = std::chrono::steady_clock::now();
@@ -847,12 +841,13 @@ int kdpt_create(const kdpt_scene* sc, const kdpt_options* opt, int device, kdpt_
     kdpt_destroy(c);
     return rc;
   };
-  if (hipSetDevice(device) != hipSuccess) return bail(fail(KDPT_ERR_HIP, "hipSetDevice failed"));
-  c->cu_mask_streams = g_cu_mask_streams;
-  if (create_stream(c, &c->stream) != KDPT_OK) return bail(fail(KDPT_ERR_HIP, "hipStreamCreate failed"));
-  if (hipEventCreateWithFlags(&c->entry_ev, hipEventDisableTiming) != hipSuccess)
-    return bail(fail(KDPT_ERR_HIP, "hipEventCreate failed"));
   int rc;
+  hipError_t e;
+  if ((e = hipSetDevice(device)) != hipSuccess) return bail(hip_fail("hipSetDevice", e));
+  c->cu_mask_streams = g_cu_mask_streams;
+  if ((rc = create_stream(c, &c->stream))) return bail(rc);
+  if ((e = hipEventCreateWithFlags(&c->entry_ev, hipEventDisableTiming)) != hipSuccess)
+    return bail(hip_fail("hipEventCreateWithFlags", e));
   // the prepared arrays onto the device, DevScene pointed at them
   auto up = [&](auto** d, const auto& v) { return dupload(c, d, v.data(), v.size()); };
   DevScene& S = c->S;
@@ -974,7 +969,7 @@ int kdpt_create(const kdpt_scene* sc, const kdpt_options* opt, int device, kdpt_
   if ((rc = setup_trace(c))) return bail(rc);
   c->S.trip_limit = 8 * std::max(c->S.num_nodes, 1) + 64;
   // the scene's uploads (hipMemcpy) complete before any kernel of the context's non-blocking streams
-  if (hipDeviceSynchronize() != hipSuccess) return bail(fail(KDPT_ERR_HIP, "hipDeviceSynchronize failed"));
+  if ((e = hipDeviceSynchronize()) != hipSuccess) return bail(hip_fail("hipDeviceSynchronize", e));
   if ((rc = kdpt_reset(c))) return bail(rc);
   c->reduce_spin_us = g_reduce_spin_us;
   c->create_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_create).count();
@@ -1021,7 +1016,8 @@ int kdpt_set_tuning(kdpt_ctx* c, const char* name, double value) {
     g_cluster_chord = value;
     return KDPT_OK;
   }
-  if (!c || !name) return fail(KDPT_ERR_ARG, "null arg");
+  if (!name) return fail(KDPT_ERR_ARG, "kdpt_set_tuning: null name");
+  if (!c) return fail(KDPT_ERR_ARG, "kdpt_set_tuning: null ctx, and no process-wide tuning knob is called " + k);
   if (k == "cast_chunk") {  // kdpt_cast_rays' chunk; its buffers are remade by the next call
     if (!(value >= 64.0 && value <= (double)(1 << 26))) return fail(KDPT_ERR_ARG, "cast_chunk must be in 64 .. 2^26");
     c->cast_chunk = (int)value;
@@ -1380,20 +1376,20 @@ static int save_image_pass(kdpt_ctx* c, float samples, uint8_t* rgb, float* lin)
   uint8_t* d_rgb = nullptr;
   float* d_lin = nullptr;
   HIP_TRY(hipMalloc((void**)&d_rgb, n3));
-  if (lin && hipMalloc((void**)&d_lin, n3 * sizeof(float)) != hipSuccess) {
+  hipError_t e = lin ? hipMalloc((void**)&d_lin, n3 * sizeof(float)) : hipSuccess;
+  if (e != hipSuccess) {
     (void)hipFree(d_rgb);
-    return fail(KDPT_ERR_HIP, "hipMalloc");
+    return hip_fail("save image: hipMalloc", e);
   }
   hipLaunchKernelGGL(k_save_image, dim3((c->npix + 255) / 256), dim3(256), 0, c->stream, c->image, c->W, c->H,
                      samples, d_rgb, d_lin);
-  hipError_t e = hipGetLastError();
+  e = hipGetLastError();
   if (e == hipSuccess && rgb) e = hipMemcpyAsync(rgb, d_rgb, n3, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess && lin) e = hipMemcpyAsync(lin, d_lin, n3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   (void)hipFree(d_rgb);
   if (d_lin) (void)hipFree(d_lin);
-  if (e != hipSuccess) return fail(KDPT_ERR_HIP, std::string("save image: ") + hipGetErrorString(e));
-  return KDPT_OK;
+  return e == hipSuccess ? KDPT_OK : hip_fail("save image", e);
 }
 
 int kdpt_save_rgb8(kdpt_ctx* c, float samples, uint8_t* rgb) {
@@ -1406,8 +1402,7 @@ int kdpt_save_png(kdpt_ctx* c, const char* path, float samples) {
   std::vector<uint8_t> rgb(3 * (size_t)c->npix);
   int rc = save_image_pass(c, samples, rgb.data(), nullptr);
   if (rc) return rc;
-  rc = kdpt_write_png(path, rgb.data(), c->W, c->H);
-  return rc ? fail(rc, std::string("cannot write ") + path) : KDPT_OK;
+  return kdpt_write_png(path, rgb.data(), c->W, c->H);  // (its failure names the path and the reason)
 }
 
 int kdpt_save_hdr(kdpt_ctx* c, const char* path, float samples) {
@@ -1415,8 +1410,7 @@ int kdpt_save_hdr(kdpt_ctx* c, const char* path, float samples) {
   std::vector<float> lin(3 * (size_t)c->npix);
   int rc = save_image_pass(c, samples, nullptr, lin.data());
   if (rc) return rc;
-  rc = kdpt_write_hdr(path, lin.data(), c->W, c->H);
-  return rc ? fail(rc, std::string("cannot write ") + path) : KDPT_OK;
+  return kdpt_write_hdr(path, lin.data(), c->W, c->H);
 }
 
 int kdpt_cull_masks(kdpt_ctx* c, int* mask_n, int* num_clusters, unsigned long long* masks) {
@@ -1621,21 +1615,18 @@ int kdpt_selftest_rng_draws(int mode, const uint32_t* in, int n, int k, float* o
   uint32_t* di;
   float* dout;
   HIP_TRY(hipMalloc((void**)&di, sizeof(uint32_t) * nin));
-  if (hipMalloc((void**)&dout, sizeof(float) * nout) != hipSuccess) {
+  if (const hipError_t e = hipMalloc((void**)&dout, sizeof(float) * nout)) {
     (void)hipFree(di);
-    return fail(KDPT_ERR_HIP, "hipMalloc failed");
+    return hip_fail("rng selftest: hipMalloc", e);
   }
-  int rc = KDPT_OK;
-  if (hipMemcpy(di, in, sizeof(uint32_t) * nin, hipMemcpyHostToDevice) != hipSuccess) rc = KDPT_ERR_HIP;
-  if (rc == KDPT_OK) {
+  hipError_t e = hipMemcpy(di, in, sizeof(uint32_t) * nin, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
     hipLaunchKernelGGL(k_selftest_rng_draws, dim3((n + 255) / 256), dim3(256), 0, 0, mode, di, n, k, dout);
-    if (hipGetLastError() != hipSuccess ||
-        hipMemcpy(out, dout, sizeof(float) * nout, hipMemcpyDeviceToHost) != hipSuccess)
-      rc = KDPT_ERR_HIP;
+    if ((e = hipGetLastError()) == hipSuccess) e = hipMemcpy(out, dout, sizeof(float) * nout, hipMemcpyDeviceToHost);
   }
   (void)hipFree(di);
   (void)hipFree(dout);
-  return rc == KDPT_OK ? KDPT_OK : fail(rc, "rng selftest failed");
+  return e == hipSuccess ? KDPT_OK : hip_fail("rng selftest", e);
 }
 
 int kdpt_selftest_glm(int fn, const float* in, int n, float* out) {
@@ -2248,9 +2239,10 @@ int kdpt_render_sharded(const kdpt_scene* scene, const kdpt_options* opt, int nd
       if ((rc = dalloc(c0, &staged[i], (size_t)n3))) return cleanup(rc);
   // a pageable host `out` pinned for the call (released by the final kdpt_synchronize of c0)
   pin_host_out(c0, out, sizeof(float) * (size_t)n3 * (size_t)frames);
+  hipError_t he;  // the HIP status behind a failing step
   auto xevent = [&](int dev, hipStream_t st, hipEvent_t* e) {
-    if (hipSetDevice(dev) != hipSuccess || hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess ||
-        hipEventRecord(*e, st) != hipSuccess)
+    if ((he = hipSetDevice(dev)) != hipSuccess || (he = hipEventCreateWithFlags(e, hipEventDisableTiming)) != hipSuccess ||
+        (he = hipEventRecord(*e, st)) != hipSuccess)
       return false;
     xev.push_back({dev, *e});
     return true;
@@ -2262,13 +2254,13 @@ int kdpt_render_sharded(const kdpt_scene* scene, const kdpt_options* opt, int nd
     std::vector<hipEvent_t> share_done(ndev, nullptr);  // each rank's last add of the frame (copy reduce)
     for (int i = 0; i < ndev; i++) {
       kdpt_ctx* ci = cs[i];
-      if (hipSetDevice(ci->device) != hipSuccess) return cleanup(fail(KDPT_ERR_HIP, "hipSetDevice"));
+      if ((he = hipSetDevice(ci->device)) != hipSuccess) return cleanup(hip_fail("hipSetDevice", he));
       if ((rc = enqueue_frame(ci, f, spp, pipeline, batch))) return cleanup(rc);
       if ((rc = reduce_spin(ci, ci->reduce_stream))) return cleanup(rc);
       // (recorded on the rank's reduce stream, which already waits for the share)
-      if (!xevent(ci->device, ci->reduce_stream, &share_done[i])) return cleanup(fail(KDPT_ERR_HIP, "frame events"));
+      if (!xevent(ci->device, ci->reduce_stream, &share_done[i])) return cleanup(hip_fail("frame events", he));
     }
-    if (hipSetDevice(c0->device) != hipSuccess) return cleanup(fail(KDPT_ERR_HIP, "hipSetDevice"));
+    if ((he = hipSetDevice(c0->device)) != hipSuccess) return cleanup(hip_fail("hipSetDevice", he));
     if ((rc = frame_buffers(c0))) return cleanup(rc);
     if (reduce == KDPT_REDUCE_RCCL) {
       R->groupStart();
@@ -2287,28 +2279,29 @@ int kdpt_render_sharded(const kdpt_scene* scene, const kdpt_options* opt, int nd
       parts.p[0] = c0->frame_buf[f & 1];
       for (int i = 1; i < ndev; i++) {
         kdpt_ctx* ci = cs[i];
-        if (hipSetDevice(c0->device) != hipSuccess ||
-            hipStreamWaitEvent(c0->reduce_stream, share_done[i], 0) != hipSuccess ||
-            hipMemcpyPeerAsync(staged[i], c0->device, ci->frame_buf[f & 1], ci->device, sizeof(float) * (size_t)n3,
-                               c0->reduce_stream) != hipSuccess)
-          return cleanup(fail(KDPT_ERR_HIP, "copy reduce"));
+        if ((he = hipSetDevice(c0->device)) != hipSuccess ||
+            (he = hipStreamWaitEvent(c0->reduce_stream, share_done[i], 0)) != hipSuccess ||
+            (he = hipMemcpyPeerAsync(staged[i], c0->device, ci->frame_buf[f & 1], ci->device, sizeof(float) * (size_t)n3,
+                                     c0->reduce_stream)) != hipSuccess)
+          return cleanup(hip_fail("copy reduce: peer copy", he));
         parts.p[i] = staged[i];
       }
       hipLaunchKernelGGL(k_sum_frames, dim3((n3 + 255) / 256), dim3(256), 0, c0->reduce_stream, c0->frame_sum, parts, n3);
-      if (hipGetLastError() != hipSuccess) return cleanup(fail(KDPT_ERR_HIP, "k_sum_frames"));
+      if ((he = hipGetLastError()) != hipSuccess) return cleanup(hip_fail("k_sum_frames", he));
       // the other ranks' frame_buf[f & 1] may be reused (frame f + 2) once these copies are done
       hipEvent_t done;
-      if (!xevent(c0->device, c0->reduce_stream, &done)) return cleanup(fail(KDPT_ERR_HIP, "copy reduce"));
+      if (!xevent(c0->device, c0->reduce_stream, &done)) return cleanup(hip_fail("copy reduce: done event", he));
       for (int i = 1; i < ndev; i++)
-        if (hipSetDevice(cs[i]->device) != hipSuccess || hipStreamWaitEvent(cs[i]->reduce_stream, done, 0) != hipSuccess)
-          return cleanup(fail(KDPT_ERR_HIP, "copy reduce"));
+        if ((he = hipSetDevice(cs[i]->device)) != hipSuccess ||
+            (he = hipStreamWaitEvent(cs[i]->reduce_stream, done, 0)) != hipSuccess)
+          return cleanup(hip_fail("copy reduce: wait for the done event", he));
     }
-    if (hipSetDevice(c0->device) != hipSuccess) return cleanup(fail(KDPT_ERR_HIP, "hipSetDevice"));
+    if ((he = hipSetDevice(c0->device)) != hipSuccess) return cleanup(hip_fail("hipSetDevice", he));
     if ((rc = finish_frame(c0, c0->frame_sum, out, k, c0->reduce_stream))) return cleanup(rc);
     for (int i = 0; i < ndev; i++) {
-      if (hipSetDevice(cs[i]->device) != hipSuccess ||
-          hipEventRecord(cs[i]->frame_ev[f & 1], cs[i]->reduce_stream) != hipSuccess)
-        return cleanup(fail(KDPT_ERR_HIP, "hipEventRecord"));
+      if ((he = hipSetDevice(cs[i]->device)) != hipSuccess ||
+          (he = hipEventRecord(cs[i]->frame_ev[f & 1], cs[i]->reduce_stream)) != hipSuccess)
+        return cleanup(hip_fail("hipEventRecord", he));
     }
   }
   for (int i = 0; i < ndev; i++)

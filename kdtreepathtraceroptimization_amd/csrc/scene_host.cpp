@@ -19,6 +19,7 @@
 // The OBJ/MTL parsing restates tinyobjloader (MIT, Copyright (c) 2012-2016 Syoyo Fujita and many
 // contributors); its notice is in THIRD_PARTY_NOTICES.md at the repository root.
 #include <algorithm>
+#include <cerrno>
 #include <cfloat>
 #include <cmath>
 #include <cstdio>
@@ -34,9 +35,23 @@
 #include <vector>
 
 #include "../../include/kdpt.h"
+#include "kdpt_error.h"
 #include "kdpt_math.h"
 
 using namespace kdpt;
+
+// The library's error slot (csrc/kdpt_error.h): one message per thread, written only by fail().
+namespace {
+std::string& error_slot() {
+  thread_local std::string slot;
+  return slot;
+}
+}  // namespace
+int kdpt::fail(int code, const std::string& msg) {
+  error_slot() = msg;
+  return code;
+}
+extern "C" const char* kdpt_last_error(void) { return error_slot().c_str(); }
 
 struct kdpt_scene_data {
   kdpt_camera camera{};
@@ -55,8 +70,6 @@ struct kdpt_scene_data {
 };
 
 namespace {
-
-thread_local std::string g_err;
 
 // ------------------------------------------------------------------ mat4
 struct Mat {
@@ -390,6 +403,7 @@ struct LineReader {
   size_t pos = 0;
   bool eof = false;
   bool open(const char* path) {
+    errno = 0;
     std::ifstream f(path, std::ios::binary);
     if (!f) return false;
     std::stringstream ss;
@@ -564,9 +578,13 @@ struct ObjSoup {
   std::vector<kdpt_material> shape_mats;
 };
 
+int cannot_open(const char* what, const char* path) {  // after a failed LineReader::open
+  return fail(KDPT_ERR_IO, std::string("cannot open ") + what + " " + path + ": " + strerror(errno ? errno : EIO));
+}
+
 int load_obj(const char* path, ObjSoup& out) {
   LineReader r;
-  if (!r.open(path)) return KDPT_ERR_IO;
+  if (!r.open(path)) return cannot_open("OBJ file", path);
   std::string p(path);
   const std::string base = p.substr(0, p.find_last_of("/\\") + 1);
   std::vector<float> v, vn;
@@ -724,7 +742,7 @@ struct ParsedScene {
 
 int parse_scene_text(const char* path, ParsedScene& ps) {
   LineReader r;
-  if (!r.open(path)) return KDPT_ERR_IO;
+  if (!r.open(path)) return cannot_open("scene file", path);
   while (!r.eof) {
     std::string line = r.getline();
     if (line.empty()) continue;
@@ -902,9 +920,12 @@ extern "C" {
 namespace {
 // Scene::Scene + Scene::loadObj from parsed values; the KD tree on the host (device < 0) or on the GPU
 int scene_build(const kdpt_scene_desc* d, int device, kdpt_scene_data** out) {
-  if (!d || !out) return KDPT_ERR_ARG;
+  if (!d) return fail(KDPT_ERR_ARG, "scene build: null desc");
+  if (!out) return fail(KDPT_ERR_ARG, "scene build: null out");
   *out = nullptr;
-  if (d->res[0] <= 0 || d->res[1] <= 0) return KDPT_ERR_ARG;
+  if (d->res[0] <= 0 || d->res[1] <= 0)
+    return fail(KDPT_ERR_ARG, "scene build: res must be positive, got " + std::to_string(d->res[0]) + " x " +
+                                  std::to_string(d->res[1]));
   std::unique_ptr<kdpt_scene_data> sd(new kdpt_scene_data());
   sd->traceDepth = d->traceDepth;
   sd->iterations = d->iterations;
@@ -937,7 +958,7 @@ int scene_build(const kdpt_scene_desc* d, int device, kdpt_scene_data** out) {
     } else {
       const int rc = kdpt_host::build_kd_device(d->verts9, d->norms9, d->shape_of_tri, d->ntri, maxdepth, device,
                                                 sd->nodes, sd->tris, &sd->kd_build_ms);
-      if (rc) return rc;
+      if (rc) return rc;  // (the build has said why)
     }
     sd->has_obj = true;
     obj_arrays(*d, *sd);
@@ -950,19 +971,23 @@ int scene_build(const kdpt_scene_desc* d, int device, kdpt_scene_data** out) {
 int kdpt_scene_build(const kdpt_scene_desc* d, kdpt_scene_data** out) { return scene_build(d, -1, out); }
 
 int kdpt_scene_build_device(const kdpt_scene_desc* d, int device, kdpt_scene_data** out) {
-  if (device < 0) return KDPT_ERR_ARG;
+  if (device < 0) return fail(KDPT_ERR_ARG, "kdpt_scene_build_device: device must be >= 0, got " + std::to_string(device));
   return scene_build(d, device, out);
 }
 
 int kdpt_scene_kd_build_ms(const kdpt_scene_data* sd, double* ms) {
-  if (!sd || !ms) return KDPT_ERR_ARG;
+  if (!sd) return fail(KDPT_ERR_ARG, "kdpt_scene_kd_build_ms: null sd");
+  if (!ms) return fail(KDPT_ERR_ARG, "kdpt_scene_kd_build_ms: null ms");
   *ms = sd->kd_build_ms;
   return KDPT_OK;
 }
 
 int kdpt_build_kd_device(const float* verts9, const float* norms9, const int* mtl, int ntri, int maxdepth, int device,
                          kdpt_node_bare** nodes, int* nnodes, kdpt_tri_bare** tris, int* ntris, double* ms) {
-  if (!verts9 || !norms9 || !mtl || ntri < 0 || !nodes || !nnodes || !tris || !ntris) return KDPT_ERR_ARG;
+  if (!verts9 || !norms9 || !mtl) return fail(KDPT_ERR_ARG, "kdpt_build_kd_device: null verts9, norms9 or mtl");
+  if (ntri < 0) return fail(KDPT_ERR_ARG, "kdpt_build_kd_device: ntri must be >= 0, got " + std::to_string(ntri));
+  if (!nodes || !nnodes || !tris || !ntris)
+    return fail(KDPT_ERR_ARG, "kdpt_build_kd_device: null nodes, nnodes, tris or ntris");
   std::vector<kdpt_node_bare> nv;
   std::vector<kdpt_tri_bare> tv;
   const int rc = kdpt_host::build_kd_device(verts9, norms9, mtl, ntri, maxdepth > 0 ? maxdepth : 13, device, nv, tv, ms);
@@ -972,7 +997,8 @@ int kdpt_build_kd_device(const float* verts9, const float* norms9, const int* mt
   if (!*nodes || !*tris) {
     free(*nodes);
     free(*tris);
-    return KDPT_ERR_ARG;
+    return fail(KDPT_ERR_ARG, "kdpt_build_kd_device: cannot allocate the result arrays (" + std::to_string(nv.size()) +
+                                  " nodes, " + std::to_string(tv.size()) + " triangles)");
   }
   if (!nv.empty()) memcpy(*nodes, nv.data(), nv.size() * sizeof(kdpt_node_bare));
   if (!tv.empty()) memcpy(*tris, tv.data(), tv.size() * sizeof(kdpt_tri_bare));
@@ -985,7 +1011,8 @@ int kdpt_build_kd_device(const float* verts9, const float* norms9, const int* mt
 namespace {
 int scene_load(const char* scene_path, const char* obj_path, int res_w, int res_h, int depth, int device,
                kdpt_scene_data** out) {
-  if (!scene_path || !out) return KDPT_ERR_ARG;
+  if (!scene_path) return fail(KDPT_ERR_ARG, "scene load: null scene_path");
+  if (!out) return fail(KDPT_ERR_ARG, "scene load: null out");
   ParsedScene ps;
   int rc = parse_scene_text(scene_path, ps);
   if (rc) return rc;
@@ -1026,12 +1053,13 @@ int kdpt_scene_load(const char* scene_path, const char* obj_path, int res_w, int
 
 int kdpt_scene_load_device(const char* scene_path, const char* obj_path, int res_w, int res_h, int depth, int device,
                            kdpt_scene_data** out) {
-  if (device < 0) return KDPT_ERR_ARG;
+  if (device < 0) return fail(KDPT_ERR_ARG, "kdpt_scene_load_device: device must be >= 0, got " + std::to_string(device));
   return scene_load(scene_path, obj_path, res_w, res_h, depth, device, out);
 }
 
 int kdpt_scene_view(const kdpt_scene_data* sd, kdpt_scene* o) {
-  if (!sd || !o) return KDPT_ERR_ARG;
+  if (!sd) return fail(KDPT_ERR_ARG, "kdpt_scene_view: null sd");
+  if (!o) return fail(KDPT_ERR_ARG, "kdpt_scene_view: null out");
   memset(o, 0, sizeof *o);
   o->camera = sd->camera;
   o->traceDepth = sd->traceDepth;

@@ -3,7 +3,8 @@
 // Parses the scene and OBJ with the product's C++ parsers and builds the KD tree (csrc/scene_host.cpp),
 // encodes a PNG and an HDR of a small image (csrc/image_io.cpp), and walks NRAYS random rays through the
 // compact-state traversal (csrc/kdpt_device.h compiled for the host).  Exits non-zero on a parse error
-// code; the sanitizers abort on any memory or UB finding.  Prints a JSON summary.
+// code; the sanitizers abort on any memory or UB finding.  Prints a JSON summary; for a refused input it holds
+// the code and kdpt_last_error()'s message.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,7 +22,13 @@ int main(int argc, char** argv) {
   const char* obj = strcmp(argv[2], "-") ? argv[2] : nullptr;
   int rc = kdpt_scene_load(argv[1], obj, 0, 0, 0, &sd);
   if (rc) {
-    printf("{\"load_rc\": %d}\n", rc);
+    printf("{\"load_rc\": %d, \"error\": \"", rc);
+    for (const char* p = kdpt_last_error(); *p; p++) {  // as a JSON string
+      if (*p == '"' || *p == '\\') printf("\\%c", *p);
+      else if ((unsigned char)*p < 0x20) printf("\\u%04x", *p);
+      else putchar(*p);
+    }
+    printf("\"}\n");
     return 0;  // a refused input is a valid outcome; the sanitizers judge how it was refused
   }
   kdpt_scene s;

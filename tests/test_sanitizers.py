@@ -5,8 +5,8 @@ restatement under ASan/UBSan; the product's host code parses untrusted OBJ/MTL/s
   csrc/kdpt_device.h compiled for the host, all sanitized, over the edge OBJs of test_host_builder.py,
   malformed OBJ and scene files (missing/short normal lists, out-of-range, zero and negative indices,
   truncated faces, garbage, NaN/inf coordinates, a 200 kB line, a missing mtllib) and, where present,
-  the reference's own meshes: each input is either built or refused with an error code, never a
-  sanitizer report;
+  the reference's own meshes: each input is either built or refused with an error code and a message
+  (kdpt_last_error, which names the file when it cannot be read), never a sanitizer report;
 - tests/native/traverse_diff.cpp linked with a sanitized build of the oracle (oracle/kdpt_oracle.c,
   whose literal visited bitmap is where the reference itself writes nodeIDs[-1]): the differential
   traversal test runs clean and still finds no mismatch;
@@ -82,7 +82,9 @@ def _run(exe, scene, obj, nrays=300):
     p = subprocess.run([exe, scene, obj, str(nrays)], capture_output=True, text=True, timeout=300, env=ENV)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     assert "runtime error" not in p.stderr and "Sanitizer" not in p.stderr, p.stderr[-4000:]
-    return json.loads(p.stdout.strip().splitlines()[-1])
+    r = json.loads(p.stdout.strip().splitlines()[-1])
+    assert r["load_rc"] == 0 or r["error"], r  # a refusal says why
+    return r
 
 
 @pytest.mark.parametrize("name", sorted(EDGE_OBJS) + sorted(MALFORMED_OBJS))
@@ -97,6 +99,14 @@ def test_host_builder_clean_under_sanitizers(asan_host, files, name):
 def test_scene_parser_clean_under_sanitizers(asan_host, files, name):
     d, _ = files
     _run(asan_host, str(d / f"scene_{name}.txt"), "-")
+
+
+def test_unreadable_inputs_name_the_file(asan_host, files):
+    d, scene = files
+    r = _run(asan_host, str(d / "no_such_scene.txt"), "-")
+    assert r["load_rc"] == -4 and str(d / "no_such_scene.txt") in r["error"]
+    r = _run(asan_host, scene, str(d / "no_such.obj"))
+    assert r["load_rc"] == -4 and str(d / "no_such.obj") in r["error"] and scene not in r["error"]
 
 
 @pytest.mark.skipif(not HAS_REFERENCE, reason="/root/reference not present")
