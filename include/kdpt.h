@@ -280,9 +280,10 @@ int kdpt_trace_config(kdpt_ctx *ctx, int *tree_mode, int *block, int *grid, long
  * For meshes whose triangles are too large for a rigorous margin that still culls (dragon_5), the box levels
  * use a fast coefficient and per-cluster direction masks decide the missed pairs' near-parallel triangles
  * one by one (the masked cull): exact = 1 as well.  exact = 0 after tuning "cull_exact" = 0 or a fixed
- * "cull_margin", and for the brute-force route (enable_kd = 0) of such meshes, whose 64-triangle chunk boxes are
- * culled at the box coefficient (1e-3) without masks: the cull is then conservative except for rays nearly
- * coplanar with a triangle. */
+ * "cull_margin": the cull is then conservative except for rays nearly coplanar with a triangle.  The brute-force
+ * route (enable_kd = 0) has no masks: each of its 64-triangle chunks is culled at the rigorous coefficient of its
+ * own triangles (never, when that could cull nothing), so exact = 1 and margin is the smallest of those
+ * coefficients (+inf when no chunk is culled), unless a knob fixes one. */
 int kdpt_cull_margin(kdpt_ctx *ctx, float *margin, double *rigorous, int *exact);
 /* Report only: *staged = 1 when the fused shading kernels run with the scene's analytic geoms and materials copied
  * to LDS (at most 8 geoms, KD boxes of viz_kd included, and at most 32 materials), 0 when they read them from

@@ -603,15 +603,24 @@ inline int dir_mask_resolution(int ncl, size_t budget = (size_t)640 << 20) {
 }
 
 // The brute-force route's boxes of 64 file-order triangles [64j, 64j + 64): the triangles glm tests,
-// v0, v0 + e1, v0 + e2, exact in double and rounded outward to float (BruteArgs::chunk_lo / chunk_hi).
+// v0, v0 + e1, v0 + e2, exact in double and rounded outward to float (BruteArgs::chunk_lo / chunk_hi), and in
+// chunk_lo[j].w the coefficient the chunk is culled at (kdpt_device.h brute_chunk_may_pass): the rigorous one of
+// the chunk's own triangles, 8.75 max |e1||e2| + 64 u (1 + max|coord| + max|e|) as cluster_margin (below) forms the
+// scene's, rounded up -- so the chunk cull drops no triangle that passes glm's u/v tests, for any line.  The route
+// has no direction masks, so nothing smaller is exact.  At a coefficient K >= 1 the widened box
+// (K (1 + |o - c|_1 + size_1) on every side) holds the origin of every line and the test can cull nothing:
+// CHUNK_MARGIN_CAP, stored as +inf (never culled).
+constexpr double CHUNK_MARGIN_CAP = 1.0;
 inline void build_chunk_boxes(const std::vector<float4>& tv, const std::vector<float4>& e1,
                               const std::vector<float4>& e2, int nt, std::vector<float4>& clo,
                               std::vector<float4>& chi) {
   const int nch = std::max(1, (nt + 63) / 64);
+  const double u = ULP_HALF;
   clo.assign(nch, make_float4(0, 0, 0, 0));
   chi.assign(nch, make_float4(0, 0, 0, 0));
   for (int j = 0; j < nch; j++) {
     double lo[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, hi[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
+    double emax = 0.0, pmax = 0.0, cmax = 0.0;
     for (int k = 64 * j; k < std::min(nt, 64 * j + 64); k++) {
       const double v[3] = {tv[k].x, tv[k].y, tv[k].z}, a[3] = {e1[k].x, e1[k].y, e1[k].z},
                    b[3] = {e2[k].x, e2[k].y, e2[k].z};
@@ -619,6 +628,11 @@ inline void build_chunk_boxes(const std::vector<float4>& tv, const std::vector<f
         lo[r] = std::min({lo[r], v[r], v[r] + a[r], v[r] + b[r]});
         hi[r] = std::max({hi[r], v[r], v[r] + a[r], v[r] + b[r]});
       }
+      const double la = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+      const double lb = std::sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
+      emax = std::max(emax, std::max(la, lb));
+      pmax = std::max(pmax, la * lb);
+      cmax = std::max(cmax, std::max(std::fabs(v[0]), std::max(std::fabs(v[1]), std::fabs(v[2]))) + la + lb);
     }
     float l[3], h[3];
     for (int r = 0; r < 3; r++) {
@@ -628,7 +642,9 @@ inline void build_chunk_boxes(const std::vector<float4>& tv, const std::vector<f
       h[r] = (float)hi[r];
       if ((double)h[r] < hi[r]) h[r] = std::nextafter(h[r], FLT_MAX);
     }
-    clo[j] = make_float4(l[0], l[1], l[2], 0.0f);
+    const double K = 8.75 * pmax + 64.0 * u * (1.0 + cmax + emax);
+    const float Kf = K < CHUNK_MARGIN_CAP ? std::nextafter((float)K, FLT_MAX) : HUGE_VALF;  // (NaN: never culled)
+    clo[j] = make_float4(l[0], l[1], l[2], Kf);
     chi[j] = make_float4(h[0], h[1], h[2], 0.0f);
   }
 }
@@ -643,9 +659,11 @@ inline void build_chunk_boxes(const std::vector<float4>& tv, const std::vector<f
 // rounding).  Meshes of small triangles (the C5 icosphere: E_max = 1.07e-4, K = 9.4e-4) get it; for meshes of
 // large triangles it would cull nothing (dragon_5: E_max = 0.2), so their box levels use K = CULL_MARGIN_MASKED
 // (1e-3) and the masked cull (build_dir_masks, mask_bound_code) decides a missed pair's near-parallel triangles:
-// exact as well.  The box coefficient alone (knob "cull_exact" = 0, and the brute-force route's chunk cull) is
+// exact as well.  The box coefficient alone (knob "cull_exact" = 0) is
 // conservative except for lines lying within ~17 u |o - v0| of a triangle's plane and within ~17 u rho / K of
 // parallel to it (tests/native/cull_diff.cpp constructs such lines); the "cluster_cull" knob = 0 removes the cull.
+// The brute-force route has no masks and does not use this coefficient: each of its chunks is culled at its own
+// rigorous one (build_chunk_boxes, above; tests/native/brute_diff.cpp).
 struct CullMargin {
   float K;          // the box-only tests' coefficient (DevScene::cl_margin)
   float K_lo;       // the slab level's floor (cl_margin_lo)

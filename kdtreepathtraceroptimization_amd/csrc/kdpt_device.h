@@ -580,6 +580,18 @@ KDPT_HD int tri_test_v(const TriData& T, f3 o, f3 d, float& bx, float& by, float
   return (bz >= 0.0f) ? 2 : 1;
 }
 
+// The hit point of an intersected triangle (barycentrics bx, by, parameter bz; vertex normals n1v .. n3v), moved
+// along the interpolated normal as the reference moves it, and its distance from the origin: the t it compares.
+template <bool HYBRID>
+KDPT_HD float tri_hit_t_n(float4 n1v, float4 n2v, float4 n3v, f3 o, f3 d, float bx, float by, float bz, f3& hit,
+                          f3& norm) {
+  const float w0 = 1 - bx - by;
+  norm = normalize(add(add(scl(mk3(n1v.x, n1v.y, n1v.z), w0), scl(mk3(n2v.x, n2v.y, n2v.z), bx)),
+                       scl(mk3(n3v.x, n3v.y, n3v.z), by)));
+  hit = add(add(o, scl(d, bz)), scl(norm, HYBRID ? 0.0001f : 0.00001f));
+  return distance(o, hit);
+}
+
 // ---------------------------------------------------------------------------
 // Big leaves (>= BIG_LEAF triangles) are swept in clusters of 64; the C5 route groups SUPER clusters under
 // one half-precision box.  The cluster cull below is host-compilable so that tests/native/cull_diff.cpp
@@ -634,6 +646,43 @@ KDPT_HD bool cluster_may_pass(float4 lo, float4 hi, f3 o, f3 inv, float K) {
   const float tmin = fmaxf(fmaxf(fminf(t1x, t2x), fminf(t1y, t2y)), fminf(t1z, t2z));
   const float tmax = fminf(fminf(fmaxf(t1x, t2x), fmaxf(t1y, t2y)), fmaxf(t1z, t2z));
   return tmin <= tmax;
+}
+
+// The brute-force route's chunk decision (kernels_brute.h k_brute; tests/native/brute_diff.cpp runs the same):
+// may the line through o cross a triangle of file-order chunk j?  The box is chunk_lo[j] / chunk_hi[j], the
+// coefficient the chunk's own rigorous one, chunk_lo[j].w (kdpt_clusters.h build_chunk_boxes: no triangle of a
+// culled chunk passes glm's u/v tests, for any line; +inf, never culled, for a chunk whose coefficient could cull
+// nothing) -- or `fixed` when that is > 0: the one coefficient of the tuning knobs "cull_margin" (not exact) and
+// "cluster_cull" = 0 (+inf).
+KDPT_HD bool brute_chunk_may_pass(const float4* chunk_lo, const float4* chunk_hi, int j, f3 o, f3 inv, float fixed) {
+  const float4 lo = chunk_lo[j];
+  return cluster_may_pass(lo, chunk_hi[j], o, inv, fixed > 0.0f ? fixed : lo.w);
+}
+
+// The brute-force route's per-shape bbox test: intersectBbox (src/interactions.h:136-165), std::min/max as in
+// intersectAABBarrays
+KDPT_HD float intersectBbox(f3 o, f3 d, float4 lo, float4 hi) {
+  const f3 invdir = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+  const float v1 = (lo.x - o.x) * invdir.x, v2 = (hi.x - o.x) * invdir.x;
+  const float v3 = (lo.y - o.y) * invdir.y, v4 = (hi.y - o.y) * invdir.y;
+  const float v5 = (lo.z - o.z) * invdir.z, v6 = (hi.z - o.z) * invdir.z;
+  const float dmin = std_max(std_max(std_min(v1, v2), std_min(v3, v4)), std_min(v5, v6));
+  const float dmax = std_min(std_min(std_max(v1, v2), std_max(v3, v4)), std_max(v5, v6));
+  if (dmax < 0) return dmax;
+  if (dmin > dmax) return dmax;
+  return dmin;
+}
+
+// Is glm::intersectRayTriangle certain to return false?  a, u, v, w are the reference's exact values;
+// f = RN(1/a) > 0 (a >= eps).  bx = RN(f*u) < 0 for u < -a*2^-100 (|f*u| >= 2^-101, far from rounding
+// to -0); bx > 1 for u > RN(a*(1+2^-20)) (then u/a > 1 + 2^-21 and two roundings cannot bring it to 1);
+// likewise by, the sum (u + v > a*(1+2^-18) with u, v >= 0) and bz = RN(f*w) < 0.
+KDPT_HD bool tri_certain_miss(float a, float u, float v, float w) {
+  const float tiny = a * 0x1p-100f;
+  const float one_u = a * 1.00000095367431640625f;  // a * (1 + 2^-20)
+  const float one_s = a * 1.000003814697265625f;    // a * (1 + 2^-18)
+  return !(a >= FLT_EPS) || u < -tiny || u > one_u || v < -tiny || w < -tiny ||
+         (u >= 0.0f && v >= 0.0f && u + v > one_s);
 }
 
 // The margin coefficient of the slab level for a line of direction d and a cluster of normal n (n.w = the
@@ -1174,16 +1223,6 @@ __device__ inline int tri_test(const DevScene& S, int i, f3 o, f3 d, float& bx, 
   return tri_test_v(tri_load(S, i), o, d, bx, by, bz);
 }
 
-
-template <bool HYBRID>
-__device__ inline float tri_hit_t_n(float4 n1v, float4 n2v, float4 n3v, f3 o, f3 d, float bx, float by, float bz,
-                                    f3& hit, f3& norm) {
-  const float w0 = 1 - bx - by;
-  norm = normalize(add(add(scl(mk3(n1v.x, n1v.y, n1v.z), w0), scl(mk3(n2v.x, n2v.y, n2v.z), bx)),
-                       scl(mk3(n3v.x, n3v.y, n3v.z), by)));
-  hit = add(add(o, scl(d, bz)), scl(norm, HYBRID ? 0.0001f : 0.00001f));
-  return distance(o, hit);
-}
 
 template <bool HYBRID>
 __device__ inline float tri_hit_t(const DevScene& S, int i, f3 o, f3 d, float bx, float by, float bz, f3& hit,

@@ -200,6 +200,7 @@ struct kdpt_ctx {
   int num_shapes = 0;
   float4* chunk_lo = nullptr;  // brute force: boxes of 64 file-order triangles
   float4* chunk_hi = nullptr;
+  float chunk_k_min = 0.0f;    // brute force: the smallest of the chunks' own cull coefficients (chunk_lo[j].w)
   // spp-sharded frames (kdpt_comm_init / kdpt_render_frames / kdpt_render_sharded): this context's rank, the
   // RCCL communicator (null: one rank, or the in-process copy reduce of kdpt_render_sharded), two frame
   // buffers (frame f accumulates into frame_buf[f & 1] while f - 1 is reduced) and rank 0's reduced frame
@@ -935,6 +936,8 @@ int kdpt_create(const kdpt_scene* sc, const kdpt_options* opt, int device, kdpt_
       return bail(rc);
     c->num_shapes = (int)p.shapes.size();
     c->brute = true;
+    c->chunk_k_min = HUGE_VALF;
+    for (const float4& q : p.chunk_lo) c->chunk_k_min = std::min(c->chunk_k_min, q.w);
   }
   if (o.external_image) {
     c->image = o.external_image;
@@ -1334,6 +1337,13 @@ int kdpt_shade_staged(kdpt_ctx* c, int* staged) {
 
 int kdpt_cull_margin(kdpt_ctx* c, float* margin, double* rigorous, int* exact) {
   if (!c) return fail(KDPT_ERR_ARG, "null ctx");
+  if (c->brute && c->cull_scene) {
+    // the chunk cull: every chunk at its own rigorous coefficient (the smallest is reported; +inf: no chunk culls)
+    if (margin) *margin = c->chunk_k_min;
+    if (rigorous) *rigorous = c->cull.rigorous;
+    if (exact) *exact = 1;
+    return KDPT_OK;
+  }
   if (margin) *margin = c->S.cl_margin;
   if (rigorous) *rigorous = c->cull.rigorous;
   // the box-only levels use cl_margin; the slab level's margin is rigorous by construction whenever that is;
@@ -1748,7 +1758,8 @@ int brute_stage(const Batch& B, int depth) {
   for (int b = 0; b < B.nb; b++) {
     IterState* it = B.its[b];
     const BruteArgs ba{scene_of(c, it), it->buf[it->cur], it->counts, depth, it->hits, c->shapes, c->num_shapes,
-                       c->chunk_lo, c->chunk_hi, c->counters, B.its[0]->trace_t};
+                       c->chunk_lo, c->chunk_hi, c->cull_scene ? 0.0f : c->S.cl_margin, c->counters,
+                       B.its[0]->trace_t};
     hipLaunchKernelGGL(kernel, dim3(c->ntiles), dim3(TILE), 0, B.st, ba);
     HIP_TRY(hipGetLastError());
     if (c->sync_debug) {

@@ -29,35 +29,11 @@ struct BruteArgs {
   const BruteShape* shapes;  // kdpt_scene_prep.h
   int num_shapes;
   const float4* chunk_lo;  // boxes of the file-order triangles [64j, 64j + 64) (the tested triangles
-  const float4* chunk_hi;  // v0, v0 + e1, v0 + e2, rounded outward)
+  const float4* chunk_hi;  // v0, v0 + e1, v0 + e2, rounded outward); chunk_lo[j].w: the chunk's cull coefficient
+  float chunk_k;           // 0: the chunks' own coefficients; > 0: one for all ("cull_margin", "cluster_cull" = 0)
   Counters* counters;
   unsigned long long* trace_t;
 };
-
-// intersectBbox (src/interactions.h:136-165), std::min/max as in intersectAABBarrays
-__device__ inline float intersectBbox(f3 o, f3 d, float4 lo, float4 hi) {
-  const f3 invdir = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-  const float v1 = (lo.x - o.x) * invdir.x, v2 = (hi.x - o.x) * invdir.x;
-  const float v3 = (lo.y - o.y) * invdir.y, v4 = (hi.y - o.y) * invdir.y;
-  const float v5 = (lo.z - o.z) * invdir.z, v6 = (hi.z - o.z) * invdir.z;
-  const float dmin = std_max(std_max(std_min(v1, v2), std_min(v3, v4)), std_min(v5, v6));
-  const float dmax = std_min(std_min(std_max(v1, v2), std_max(v3, v4)), std_max(v5, v6));
-  if (dmax < 0) return dmax;
-  if (dmin > dmax) return dmax;
-  return dmin;
-}
-
-// Is glm::intersectRayTriangle certain to return false?  a, u, v, w are the reference's exact values;
-// f = RN(1/a) > 0 (a >= eps).  bx = RN(f*u) < 0 for u < -a*2^-100 (|f*u| >= 2^-101, far from rounding
-// to -0); bx > 1 for u > RN(a*(1+2^-20)) (then u/a > 1 + 2^-21 and two roundings cannot bring it to 1);
-// likewise by, the sum (u + v > a*(1+2^-18) with u, v >= 0) and bz = RN(f*w) < 0.
-__device__ inline bool tri_certain_miss(float a, float u, float v, float w) {
-  const float tiny = a * 0x1p-100f;
-  const float one_u = a * 1.00000095367431640625f;  // a * (1 + 2^-20)
-  const float one_s = a * 1.000003814697265625f;    // a * (1 + 2^-18)
-  return !(a >= FLT_EPS) || u < -tiny || u > one_u || v < -tiny || w < -tiny ||
-         (u >= 0.0f && v >= 0.0f && u + v > one_s);
-}
 
 template <bool COUNT>
 __device__ inline void brute_triangle(const DevScene& S, int k, const TriData& T, f3 o, f3 d, float& t_min, int& best,
@@ -144,12 +120,13 @@ __global__ __launch_bounds__(TILE) void k_brute(BruteArgs A) {
           // every lane that tests this shape starts at the same triangle: scalar triangle fetches
           const int k0 = __builtin_amdgcn_readfirstlane(it0 / 3);
           const int nt = nidx / 3;
-          // 64-triangle chunks: no triangle of a chunk whose box the lane's line misses (box widened as in
-          // cluster_may_pass) passes the u/v tests, so those lanes skip it, and the wave skips a chunk no lane
-          // can hit; the others test its triangles in file order as before
+          // 64-triangle chunks: no triangle of a chunk whose box the lane's line misses passes glm's u/v tests --
+          // the box is widened by the chunk's own rigorous coefficient (brute_chunk_may_pass; a chunk of
+          // triangles too large for one that culls is never skipped) -- so those lanes skip it, and the wave
+          // skips a chunk no lane can hit; the others test its triangles in file order as before
           for (int k = k0; k < k0 + nt;) {
             const int j = k >> 6, kend = min(k0 + nt, (j + 1) << 6);
-            const bool may = take && (!cull || cluster_may_pass(A.chunk_lo[j], A.chunk_hi[j], o, inv, S.cl_margin));
+            const bool may = take && (!cull || brute_chunk_may_pass(A.chunk_lo, A.chunk_hi, j, o, inv, A.chunk_k));
             if (__any(may)) {
               for (; k < kend; k++) {
                 const TriData T = tri_load(S, k);

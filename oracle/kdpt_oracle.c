@@ -983,16 +983,11 @@ static void shadeMaterial(const orc_scene *s, const orc_opts *o, int num_paths, 
 
 static int cmp_paths_stable_key(const void *a, const void *b) { (void)a; (void)b; return 0; }
 
-/* One pathtrace() iteration.  stop_depth >= 0: return after that bounce. */
-static int run_iteration(const orc_scene *s, const orc_opts *o, int iter, orc_path *paths, orc_path *tmp,
-                         orc_isect *isects, float *image, orc_stats *st, int stop_depth, int *npaths_out) {
-    const orc_camera *cam = &s->camera;
-    int W = cam->resolution[0], H = cam->resolution[1];
-    int pixelcount = W * H;
-    /* cacherays (src/pathtrace.cu:2448-2456): camera rays of iteration 1 are reused; the
-       bounce RNG still uses the real iter */
-    generateRayFromCamera(cam, o->cacherays ? 1 : iter, s->traceDepth, paths, o->focalLength, o->dofAngle,
-                          o->antialias);
+/* pathtrace()'s bounce loop and gathers over the first `pixelcount` paths, as the camera stage (or a caller's
+ * rays, orc_render_rays) left them.  stop_depth >= 0: return after that bounce. */
+static int run_bounces(const orc_scene *s, const orc_opts *o, int iter, int pixelcount, orc_path *paths,
+                       orc_path *tmp, orc_isect *isects, float *image, orc_stats *st, int stop_depth,
+                       int *npaths_out) {
     int depth = 0;
     int num_paths = pixelcount;
     counters_t cnt = {0, 0, 0, 0};
@@ -1062,6 +1057,18 @@ static int run_iteration(const orc_scene *s, const orc_opts *o, int iter, orc_pa
     return 0;
 }
 
+/* One pathtrace() iteration.  stop_depth >= 0: return after that bounce. */
+static int run_iteration(const orc_scene *s, const orc_opts *o, int iter, orc_path *paths, orc_path *tmp,
+                         orc_isect *isects, float *image, orc_stats *st, int stop_depth, int *npaths_out) {
+    const orc_camera *cam = &s->camera;
+    /* cacherays (src/pathtrace.cu:2448-2456): camera rays of iteration 1 are reused; the
+       bounce RNG still uses the real iter */
+    generateRayFromCamera(cam, o->cacherays ? 1 : iter, s->traceDepth, paths, o->focalLength, o->dofAngle,
+                          o->antialias);
+    return run_bounces(s, o, iter, cam->resolution[0] * cam->resolution[1], paths, tmp, isects, image, st,
+                       stop_depth, npaths_out);
+}
+
 void orc_default_opts(orc_opts *o) {
     o->focalLength = 6.0f;
     o->dofAngle = 0.0f;
@@ -1104,6 +1111,55 @@ int orc_render(const orc_scene *s, const orc_opts *o, int iter_first, int iter_c
     memset(&local, 0, sizeof local);
     for (int it = iter_first; it < iter_first + iter_count; it++)
         run_iteration(s, o, it, paths, tmp, isects, image, &local, -1, NULL);
+    if (stats) *stats = local;
+    free(paths); free(tmp); free(isects);
+    return 0;
+}
+
+int orc_camera_rays(const orc_scene *s, const orc_opts *o, int iter, float *origins, float *directions) {
+    int pixelcount = s->camera.resolution[0] * s->camera.resolution[1];
+    orc_path *paths = (orc_path *)calloc((size_t)pixelcount, sizeof(orc_path));
+    if (!paths) return -1;
+    generateRayFromCamera(&s->camera, o->cacherays ? 1 : iter, s->traceDepth, paths, o->focalLength, o->dofAngle,
+                          o->antialias);
+    for (int i = 0; i < pixelcount; i++) {
+        memcpy(origins + 3 * (size_t)i, paths[i].origin, 12);
+        memcpy(directions + 3 * (size_t)i, paths[i].direction, 12);
+    }
+    free(paths);
+    return 0;
+}
+
+int orc_render_rays(const orc_scene *s, const orc_opts *o, const float *origins, const float *directions, int n,
+                    int iter_first, int iter_count, float *radiance, orc_stats *stats, int nthreads) {
+    if (shades_past_materials(s, o)) return -2;
+    if (n < 0) return -1;
+#ifdef _OPENMP
+    if (nthreads > 0) omp_set_num_threads(nthreads);
+#else
+    (void)nthreads;
+#endif
+    size_t cap = n > 0 ? (size_t)n : 1;
+    orc_path *paths = (orc_path *)calloc(cap, sizeof(orc_path));
+    orc_path *tmp = (orc_path *)calloc(cap, sizeof(orc_path));
+    orc_isect *isects = (orc_isect *)calloc(cap, sizeof(orc_isect));
+    if (!paths || !tmp || !isects) { free(paths); free(tmp); free(isects); return -1; }
+    orc_stats local;
+    memset(&local, 0, sizeof local);
+    for (int it = iter_first; it < iter_first + iter_count; it++) {
+        /* the camera stage's writes (generateRayFromCamera), with the caller's ray: sdepth and materialIdHit
+           stay what the slot last held */
+        for (int i = 0; i < n; i++) {
+            orc_path *seg = &paths[i];
+            memcpy(seg->origin, origins + 3 * (size_t)i, 12);
+            memcpy(seg->direction, directions + 3 * (size_t)i, 12);
+            seg->isinside = 0;
+            seg->color[0] = 1.0f; seg->color[1] = 1.0f; seg->color[2] = 1.0f;
+            seg->pixelIndex = i;
+            seg->remainingBounces = s->traceDepth;
+        }
+        run_bounces(s, o, it, n, paths, tmp, isects, radiance, &local, -1, NULL);
+    }
     if (stats) *stats = local;
     free(paths); free(tmp); free(isects);
     return 0;

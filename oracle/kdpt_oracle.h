@@ -211,6 +211,17 @@ int orc_load_obj(const char *obj_path, float **verts9, float **norms9, int **sha
 int orc_render(const orc_scene *s, const orc_opts *o, int iter_first, int iter_count,
                float *image, orc_stats *stats, int nthreads);
 
+/* The W*H rays generateRayFromCamera produces for iteration `iter` (cacherays: iteration 1's), 3 floats each,
+ * ray y*W + x at [3 (y*W + x)]. */
+int orc_camera_rays(const orc_scene *s, const orc_opts *o, int iter, float *origins, float *directions);
+
+/* orc_render with the camera stage replaced (include/kdpt.h kdpt_trace_rays): path i starts as {origins[i],
+ * directions[i], colour 1, pixelIndex i, remainingBounces traceDepth}, n paths instead of W*H, and everything after
+ * that is orc_render's own bounce loop -- compaction, iteration 2's sort, both gathers, the RNG seeds by slot,
+ * enable_kd, usebbox, vizkd, the -2 refusal.  radiance: 3*n floats, caller-zeroed, accumulated like an image. */
+int orc_render_rays(const orc_scene *s, const orc_opts *o, const float *origins, const float *directions, int n,
+                    int iter_first, int iter_count, float *radiance, orc_stats *stats, int nthreads);
+
 /* Debug: run iteration `iter` through bounce `stop_depth` (0-based) and copy the
  * path array (after compaction/sort of that bounce) to out (>= W*H entries). */
 int orc_paths_after(const orc_scene *s, const orc_opts *o, int iter, int stop_depth,

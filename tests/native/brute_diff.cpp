@@ -1,0 +1,652 @@
+// TEST INFRASTRUCTURE: host differential of the brute-force intersect route (kernels_brute.h k_brute, enable_kd = 0).
+//
+// k_brute is the reference's loop over every OBJ triangle in file order with two shortcuts: a lane skips a
+// 64-triangle chunk whose box its line misses (kdpt_device.h brute_chunk_may_pass), and it rejects a triangle
+// without the division when glm's answer is certain (tri_certain_miss).  Both are compiled here for the host, with
+// the arrays kdpt_scene_prep.h prepare_brute builds from the scene's OBJ arrays (the kernel's triangles, chunk boxes
+// and coefficients, shapes -- in file order), and checked on adversarial lines:
+//   (a) chunk-local, every line: the chunk of the triangle the line was aimed at must not be culled while one of its
+//       triangles returns tri_test_v == 2 with tri_hit_t_n > 0 ("dropped"); tri_certain_miss must not hold for a
+//       triangle with tri_test_v == 2 ("cm_viol");
+//   (b) whole route, on every line with a chunk-local event (a hit in its chunk, or its chunk culled) and every 256th
+//       other: one lane of k_brute (shape loop, `iterator`, bbox, chunk cull, tri_certain_miss, exact test,
+//       first-minimum rule) against the reference's plain loop over the raw OBJ arrays (src/pathtrace.cu:485-576):
+//       winner, t bits and hit count must be equal ("route_viol").
+// A third part checks tri_certain_miss alone: triangles scaled by 2^+-40, 2^+-60 and to a determinant near
+// FLT_EPSILON, and the rule's arithmetic on (a, u, v, w) within 4 ulps of each threshold over the whole float range.
+//
+//   brute_diff SCENE.bin NLINES SEED [--bbox] [--margin K] [--only GEN] [--no-route] [--inside lx ly lz hx hy hz]
+//              [--emit FILE N]
+// SCENE.bin: int32 num_shapes, polyidxcount, num_obj_verts, num_obj_norms, num_bbox_floats; obj_verts, obj_norms
+// (float32), obj_polysidxflat, obj_polyoffsets (int32), obj_bboxes (float32), obj_materialOffsets (int32).
+// --margin K: one coefficient for every chunk (the "cull_margin" knob) instead of the chunks' own.
+// --only GEN: every line from that generator (with --emit: every line after the first 4 N, which keep the mix).
+// --no-route: part (a) only.
+// --emit FILE N: N rays (float32 origin.xyz, direction.xyz, directions normalised in float, every reciprocal finite)
+// of the generated lines, those that need exactness first: the reference loop's winner is a triangle whose chunk
+// cluster_may_pass misses at K = 1e-3.  --inside keeps only origins inside that box.  Prints one JSON line.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <random>
+#include <vector>
+
+#include "../../kdtreepathtraceroptimization_amd/csrc/kdpt_scene_prep.h"
+
+using namespace kdpt;
+
+namespace {
+
+enum Gen { G_RANDOM, G_GRAZE, G_GRAZE_EDGE, G_FACE, G_AXIS, G_SHAPE_EDGE, G_ROUND, G_SHARED, G_BARY, NGEN };
+const char* kGenName[NGEN] = {"random", "graze", "graze_edge", "face", "axis", "shape_edge", "round", "shared", "bary"};
+
+struct Counts {
+  long long lines = 0, culled = 0, hit_own = 0, dropped = 0, cm_viol = 0, route_runs = 0, route_viol = 0, nofast = 0;
+  void add(const Counts& o) {
+    lines += o.lines; culled += o.culled; hit_own += o.hit_own; dropped += o.dropped; cm_viol += o.cm_viol;
+    route_runs += o.route_runs; route_viol += o.route_viol; nofast += o.nofast;
+  }
+};
+
+struct V3 { double x, y, z; };
+V3 v3(double x, double y, double z) { return V3{x, y, z}; }
+V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
+V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
+V3 operator*(V3 a, double s) { return v3(a.x * s, a.y * s, a.z * s); }
+double dotd(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+V3 crossd(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+V3 unitd(V3 a) { return a * (1.0 / std::sqrt(dotd(a, a))); }
+double comp(V3 a, int i) { return i == 0 ? a.x : (i == 1 ? a.y : a.z); }
+void setc(V3& a, int i, double v) { (i == 0 ? a.x : (i == 1 ? a.y : a.z)) = v; }
+V3 of4(float4 q) { return v3(q.x, q.y, q.z); }
+
+struct Scene {
+  std::vector<float> verts, norms, bboxes;
+  std::vector<int> idx, offs, mats;
+  kdpt_scene sc{};
+  PreparedScene p;
+  int nt = 0;
+  bool use_bbox = false;
+  float fixed = 0.0f;  // --margin: the chunk decision's fixed coefficient (0: the chunks' own)
+};
+
+struct Result {
+  int winner = -1;
+  float t = FLT_MAXV;
+  long long hits = 0;
+};
+
+// brute_triangle's per-lane work (kernels_brute.h): true when the exact test ran and returned "intersected"
+inline bool lane_triangle(const Scene& S, int k, f3 o, f3 d, float& t, bool& certain) {
+  const TriArrays& T = S.p.tri;
+  const TriData td{T.tv0[k], T.te1[k], T.te2[k]};
+  const f3 v0 = mk3(td.v0.x, td.v0.y, td.v0.z), e1 = mk3(td.e1.x, td.e1.y, td.e1.z), e2 = mk3(td.e2.x, td.e2.y, td.e2.z);
+  const f3 p = cross(d, e2);
+  const float a = dot(e1, p);
+  const f3 s = sub(o, v0);
+  const float u = dot(s, p);
+  const f3 q = cross(s, e1);
+  const float v = dot(d, q);
+  const float w = dot(e2, q);
+  certain = tri_certain_miss(a, u, v, w);
+  if (certain) return false;
+  float bx, by, bz;
+  if (tri_test_v(td, o, d, bx, by, bz) != 2) return false;
+  f3 hp, nn;
+  t = tri_hit_t_n<true>(T.tn0[k], T.tn1[k], T.tn2[k], o, d, bx, by, bz, hp, nn);
+  return true;
+}
+
+// One lane of k_brute whose wave starts every shape at the same triangle (the branch with the chunk cull).
+Result lane(const Scene& S, f3 o, f3 d) {
+  Result r;
+  const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+  const bool cull = fabsf(inv.x) < FLT_INFV && fabsf(inv.y) < FLT_INFV && fabsf(inv.z) < FLT_INFV;
+  int iterator = 0;
+  for (size_t sh = 0; sh < S.p.shapes.size(); sh++) {
+    const BruteShape B = S.p.shapes[sh];
+    const int nidx = fbits(B.lo.w);
+    bool take = true;
+    if (S.use_bbox) take = intersectBbox(o, d, B.lo, B.hi) > -1.0f;
+    if (!take) continue;
+    const int k0 = iterator / 3, nt = nidx / 3;
+    for (int k = k0; k < k0 + nt;) {
+      const int j = k >> 6, kend = std::min(k0 + nt, (j + 1) << 6);
+      const bool may = !cull || brute_chunk_may_pass(S.p.chunk_lo.data(), S.p.chunk_hi.data(), j, o, inv, S.fixed);
+      if (may)
+        for (; k < kend; k++) {
+          float t;
+          bool certain;
+          if (lane_triangle(S, k, o, d, t, certain)) {
+            r.hits++;
+            if (t > 0.0f && r.t > t) {
+              r.t = t;
+              r.winner = k;
+            }
+          }
+        }
+      k = kend;
+    }
+    iterator += nidx;
+  }
+  return r;
+}
+
+// The reference's loop (src/pathtrace.cu:485-576) over the raw OBJ arrays: every triangle of every shape whose bbox
+// test passed, `iterator` advancing only past those, glm's test, first minimum.
+Result reference(const Scene& S, f3 o, f3 d) {
+  Result r;
+  int iterator = 0;
+  const float* bb = S.bboxes.data();
+  const float *V = S.verts.data(), *N = S.norms.data();
+  for (int i = 0; i < S.sc.num_shapes; i++) {
+    float T = 0.0f;
+    if (S.use_bbox) {
+      const float4 mn = make_float4((float)((double)bb[i] - 0.01), (float)((double)bb[i + 1] - 0.01),
+                                    (float)((double)bb[i + 2] - 0.01), 0.0f);
+      const float4 mx = make_float4((float)((double)bb[i + 3] + 0.01), (float)((double)bb[i + 4] + 0.01),
+                                    (float)((double)bb[i + 5] + 0.01), 0.0f);
+      T = intersectBbox(o, d, mn, mx);
+    }
+    if (!(T > -1.0f)) continue;
+    for (int j = iterator; j < iterator + S.offs[i]; j += 3) {
+      const int p1 = 3 * S.idx[j], p2 = 3 * S.idx[j + 1], p3 = 3 * S.idx[j + 2];
+      const TriData td{make_float4(V[p1], V[p1 + 1], V[p1 + 2], 0.0f),
+                       make_float4(V[p2] - V[p1], V[p2 + 1] - V[p1 + 1], V[p2 + 2] - V[p1 + 2], 0.0f),
+                       make_float4(V[p3] - V[p1], V[p3 + 1] - V[p1 + 1], V[p3 + 2] - V[p1 + 2], 0.0f)};
+      float bx, by, bz;
+      if (tri_test_v(td, o, d, bx, by, bz) != 2) continue;
+      r.hits++;
+      f3 hp, nn;
+      const float t = tri_hit_t_n<true>(make_float4(N[p1], N[p1 + 1], N[p1 + 2], 0.0f),
+                                        make_float4(N[p2], N[p2 + 1], N[p2 + 2], 0.0f),
+                                        make_float4(N[p3], N[p3 + 1], N[p3 + 2], 0.0f), o, d, bx, by, bz, hp, nn);
+      if (t > 0.0f && r.t > t) {
+        r.t = t;
+        r.winner = j / 3;
+      }
+    }
+    iterator += S.offs[i];
+  }
+  return r;
+}
+
+bool read_scene(const char* path, Scene& S) {
+  FILE* f = fopen(path, "rb");
+  if (!f) return false;
+  int h[5];
+  if (fread(h, 4, 5, f) != 5 || h[0] < 1 || h[1] < 3 || h[2] < 0 || h[3] < 0 || h[4] < 0) return false;
+  S.verts.resize(h[2]); S.norms.resize(h[3]); S.idx.resize(h[1]); S.offs.resize(h[0]); S.bboxes.resize(h[4]);
+  S.mats.resize(h[0]);
+  bool ok = fread(S.verts.data(), 4, h[2], f) == (size_t)h[2] && fread(S.norms.data(), 4, h[3], f) == (size_t)h[3] &&
+            fread(S.idx.data(), 4, h[1], f) == (size_t)h[1] && fread(S.offs.data(), 4, h[0], f) == (size_t)h[0] &&
+            fread(S.bboxes.data(), 4, h[4], f) == (size_t)h[4] && fread(S.mats.data(), 4, h[0], f) == (size_t)h[0];
+  fclose(f);
+  if (!ok) return false;
+  long long total = 0;
+  for (int i = 0; i < h[0]; i++) {
+    if (S.offs[i] < 0 || S.offs[i] % 3) return false;
+    total += S.offs[i];
+  }
+  if (total != h[1] || h[4] < h[0] + 5) return false;
+  for (int v : S.idx)
+    if (v < 0 || 3 * (long long)v + 2 >= h[2] || 3 * (long long)v + 2 >= h[3]) return false;
+  S.sc.num_shapes = h[0];
+  S.sc.polyidxcount = h[1];
+  S.sc.num_obj_verts = h[2];
+  S.sc.num_obj_norms = h[3];
+  S.sc.num_bbox_floats = h[4];
+  S.sc.has_obj = 1;
+  S.sc.obj_verts = S.verts.data();
+  S.sc.obj_norms = S.norms.data();
+  S.sc.obj_polysidxflat = S.idx.data();
+  S.sc.obj_polyoffsets = S.offs.data();
+  S.sc.obj_bboxes = S.bboxes.data();
+  S.sc.obj_materialOffsets = S.mats.data();
+  S.nt = h[1] / 3;
+  return true;
+}
+
+float step_ulps(float x, int n) {
+  for (; n > 0; n--) x = std::nextafter(x, FLT_MAX);
+  for (; n < 0; n++) x = std::nextafter(x, -FLT_MAX);
+  return x;
+}
+
+// tri_certain_miss alone.  (1) its arithmetic: for determinants a over the whole float range at and above FLT_EPSILON,
+// every (u, v, w) within 4 ulps of each threshold (0, -a 2^-100, a, a (1 + 2^-20), u + v = a, a (1 + 2^-18)), and
+// glm's own decision on f u, f v, f w (f = 1 / a): the rule must not hold when glm accepts.  (2) the scene's
+// triangles scaled by 2^+-40, 2^+-60 and so that a lands within [1/2, 8] FLT_EPSILON, rays aimed at their edges and
+// vertices from scaled origins.
+void certain_miss_check(const Scene& S, long long n, unsigned seed, long long& cases, long long& accepted,
+                        long long& viol) {
+  long long c1 = 0, a1 = 0, v1 = 0;
+#pragma omp parallel for schedule(dynamic, 1024) reduction(+ : c1, a1, v1)
+  for (long long r = 0; r < n; r++) {
+    std::mt19937_64 rng(seed * 0xD1B54A32D192ED03ull + (unsigned long long)r);
+    std::uniform_real_distribution<double> U(0.0, 1.0);
+    auto glm_accepts = [](float a, float u, float v, float w) {
+      if (a < FLT_EPS) return false;
+      const float f = 1.0f / a;
+      const float bx = f * u;
+      if (bx < 0.0f || bx > 1.0f) return false;
+      const float by = f * v;
+      if (by < 0.0f || by + bx > 1.0f) return false;
+      return f * w >= 0.0f;
+    };
+    if (r % 2 == 0) {
+      // a = m 2^e: e from FLT_EPSILON's exponent up to 2^127 (a (1 + 2^-20) near overflow), half of them within 4
+      // ulps of FLT_EPSILON
+      float a = (float)std::ldexp(1.0 + U(rng), -23 + (int)(U(rng) * 150.0));
+      if (U(rng) < 0.25) a = step_ulps(FLT_EPS, (int)(U(rng) * 9.0) - 4);
+      if (!(a < FLT_INFV)) a = FLT_MAXV;
+      const float thr[6] = {0.0f, -(a * 0x1p-100f), a, a * 1.00000095367431640625f, a * 1.000003814697265625f,
+                            (float)(0.5 * (double)a)};
+      float uvw[3];
+      for (int q = 0; q < 3; q++) {
+        const float base = thr[(int)(U(rng) * 6.0) % 6];
+        uvw[q] = base < FLT_INFV ? step_ulps(base, (int)(U(rng) * 9.0) - 4) : FLT_MAXV;
+        if (U(rng) < 0.1) uvw[q] = (U(rng) < 0.5 ? -1.0f : 1.0f) * (float)std::ldexp(1.0, -149 + (int)(U(rng) * 30.0));
+      }
+      if (U(rng) < 0.3) uvw[1] = step_ulps(a - uvw[0], (int)(U(rng) * 9.0) - 4);  // u + v near a
+      c1++;
+      const bool acc = glm_accepts(a, uvw[0], uvw[1], uvw[2]);
+      a1 += acc;
+      v1 += acc && tri_certain_miss(a, uvw[0], uvw[1], uvw[2]);
+    } else {
+      const int k = (int)(U(rng) * S.nt) % S.nt;
+      const TriArrays& T = S.p.tri;
+      const V3 p0 = of4(T.tv0[k]), a1v = of4(T.te1[k]), a2v = of4(T.te2[k]);
+      const V3 nrm = crossd(a1v, a2v);
+      const double nl = std::sqrt(dotd(nrm, nrm));
+      if (nl == 0.0) continue;
+      const int exps[4] = {40, -40, 60, -60};
+      double sc;
+      const int mode = (int)(U(rng) * 5.0) % 5;
+      V3 dir = unitd(v3(U(rng) - 0.5, U(rng) - 0.5, U(rng) - 0.5));
+      if (mode < 4) sc = std::ldexp(1.0, exps[mode]);
+      else sc = std::sqrt((double)FLT_EPS * (0.5 + 7.5 * U(rng)) / std::max(1e-300, std::fabs(dotd(nrm, dir))));
+      // a point on an edge or at a vertex (barycentrics 0 / 1), or inside
+      double bu = U(rng), bv = U(rng) * (1.0 - bu);
+      const int e = (int)(U(rng) * 5.0) % 5;
+      if (e == 0) bu = 0.0;
+      else if (e == 1) bv = 0.0;
+      else if (e == 2) bv = 1.0 - bu;
+      else if (e == 3) { bu = U(rng) < 0.5 ? 0.0 : 1.0; bv = 0.0; }
+      const V3 P = (p0 + a1v * bu + a2v * bv) * sc;
+      if (dotd(nrm, dir) > 0) dir = dir * -1.0;  // front-facing: a > 0
+      const double dist = sc * nl / std::sqrt(dotd(a1v, a1v)) * std::pow(10.0, -1.0 + 2.0 * U(rng));
+      const V3 O = P - dir * dist;
+      f3 of = mk3((float)O.x, (float)O.y, (float)O.z);
+      const int nud = (int)(U(rng) * 9.0) - 4, ax = (int)(U(rng) * 3.0) % 3;
+      if (ax == 0) of.x = step_ulps(of.x, nud); else if (ax == 1) of.y = step_ulps(of.y, nud); else of.z = step_ulps(of.z, nud);
+      const f3 df = normalize(mk3((float)(P.x - (double)of.x), (float)(P.y - (double)of.y), (float)(P.z - (double)of.z)));
+      const float fs = (float)sc;  // a power of two, or the float the triangle is scaled by
+      const TriData td{make_float4(T.tv0[k].x * fs, T.tv0[k].y * fs, T.tv0[k].z * fs, 0.0f),
+                       make_float4(T.te1[k].x * fs, T.te1[k].y * fs, T.te1[k].z * fs, 0.0f),
+                       make_float4(T.te2[k].x * fs, T.te2[k].y * fs, T.te2[k].z * fs, 0.0f)};
+      const f3 v0 = mk3(td.v0.x, td.v0.y, td.v0.z), e1 = mk3(td.e1.x, td.e1.y, td.e1.z), e2 = mk3(td.e2.x, td.e2.y, td.e2.z);
+      const f3 p = cross(df, e2);
+      const float a = dot(e1, p);
+      const f3 s = sub(of, v0);
+      const float u = dot(s, p);
+      const f3 q = cross(s, e1);
+      const float v = dot(df, q), w = dot(e2, q);
+      float bx, by, bz;
+      const bool acc = tri_test_v(td, of, df, bx, by, bz) == 2;
+      c1++;
+      a1 += acc;
+      v1 += acc && tri_certain_miss(a, u, v, w);
+    }
+  }
+  cases = c1;
+  accepted = a1;
+  viol = v1;
+}
+
+struct Emit {
+  long long r;
+  float ray[6];
+  bool exact;
+};
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  if (argc < 4) {
+    fprintf(stderr, "usage: brute_diff SCENE.bin NLINES SEED [--bbox] [--margin K] [--inside 6 floats] [--emit FILE N]\n");
+    return 2;
+  }
+  Scene S;
+  if (!read_scene(argv[1], S)) {
+    fprintf(stderr, "brute_diff: cannot read %s\n", argv[1]);
+    return 3;
+  }
+  const long long nlines = atoll(argv[2]);
+  const unsigned seed = (unsigned)atoi(argv[3]);
+  const char* emit_path = nullptr;
+  long long emit_n = 0;
+  bool inside = false, route = true;
+  int only = -1;
+  double in_lo[3] = {0, 0, 0}, in_hi[3] = {0, 0, 0};
+  for (int i = 4; i < argc; i++) {
+    if (!strcmp(argv[i], "--bbox")) S.use_bbox = true;
+    else if (!strcmp(argv[i], "--margin") && i + 1 < argc) S.fixed = (float)atof(argv[++i]);
+    else if (!strcmp(argv[i], "--no-route")) route = false;
+    else if (!strcmp(argv[i], "--only") && i + 1 < argc) {
+      i++;
+      for (int g = 0; g < NGEN; g++)
+        if (!strcmp(argv[i], kGenName[g])) only = g;
+      if (only < 0) {
+        fprintf(stderr, "brute_diff: unknown generator %s\n", argv[i]);
+        return 2;
+      }
+    }
+    else if (!strcmp(argv[i], "--emit") && i + 2 < argc) { emit_path = argv[i + 1]; emit_n = atoll(argv[i + 2]); i += 2; }
+    else if (!strcmp(argv[i], "--inside") && i + 6 < argc) {
+      inside = true;
+      for (int a = 0; a < 3; a++) { in_lo[a] = atof(argv[i + 1 + a]); in_hi[a] = atof(argv[i + 4 + a]); }
+      i += 6;
+    } else {
+      fprintf(stderr, "brute_diff: bad argument %s\n", argv[i]);
+      return 2;
+    }
+  }
+  prepare_brute(&S.sc, S.use_bbox, S.p);
+  const TriArrays& T = S.p.tri;
+  const std::vector<float4>&clo = S.p.chunk_lo, &chi = S.p.chunk_hi;
+  const int nt = S.nt, nch = (int)clo.size();
+  // the mesh's extent, and the triangles that meet at each vertex position (G_SHARED)
+  V3 slo = v3(1e300, 1e300, 1e300), shi = v3(-1e300, -1e300, -1e300);
+  std::map<std::array<uint32_t, 3>, std::vector<int>> at_vertex;
+  for (int k = 0; k < nt; k++)
+    for (int q = 0; q < 3; q++) {
+      const float x = T.tv0[k].x + (q == 1 ? T.te1[k].x : (q == 2 ? T.te2[k].x : 0.0f));
+      const float y = T.tv0[k].y + (q == 1 ? T.te1[k].y : (q == 2 ? T.te2[k].y : 0.0f));
+      const float z = T.tv0[k].z + (q == 1 ? T.te1[k].z : (q == 2 ? T.te2[k].z : 0.0f));
+      slo = v3(std::min(slo.x, (double)x), std::min(slo.y, (double)y), std::min(slo.z, (double)z));
+      shi = v3(std::max(shi.x, (double)x), std::max(shi.y, (double)y), std::max(shi.z, (double)z));
+      const int p = 3 * S.idx[3 * k + q];
+      uint32_t key[3];
+      memcpy(key, &S.verts[p], 12);
+      std::vector<int>& l = at_vertex[{key[0], key[1], key[2]}];
+      if (l.size() < 16) l.push_back(k);
+    }
+  const V3 sext = shi - slo;
+  const double scale = std::max(1e-6, std::max(sext.x, std::max(sext.y, sext.z)));
+  std::vector<int> shape_of(nt, 0);
+  {
+    int k = 0;
+    for (int i = 0; i < S.sc.num_shapes; i++)
+      for (int q = 0; q < S.offs[i] / 3; q++) shape_of[k++] = i;
+  }
+  const float K_FAST = CULL_MARGIN_MASKED;  // the coefficient the chunk cull used to run at (need-exactness rule)
+
+  Counts tot[NGEN];
+  std::vector<Emit> emits;
+#pragma omp parallel
+  {
+    Counts loc[NGEN];
+    std::vector<Emit> lem;
+#pragma omp for schedule(dynamic, 1024)
+    for (long long r = 0; r < nlines; r++) {
+      std::mt19937_64 rng(seed * 0x9E3779B97F4A7C15ull + (unsigned long long)r);
+      std::uniform_real_distribution<double> U(0.0, 1.0);
+      auto logu = [&](double a, double b) { return std::pow(10.0, a + (b - a) * U(rng)); };
+      auto sgn = [&]() { return U(rng) < 0.5 ? -1.0 : 1.0; };
+      const int g = only >= 0 && !(emit_path && r < 4 * emit_n) ? only : (int)(r % NGEN);
+      const int ent = (int)(U(rng) * nt) % nt;  // the triangle the line is aimed at; its chunk is "the line's own"
+      const int j = ent >> 6;
+      const V3 p0 = of4(T.tv0[ent]), a1 = of4(T.te1[ent]), a2 = of4(T.te2[ent]);
+      const V3 nrm = crossd(a1, a2);
+      const double nl = std::sqrt(dotd(nrm, nrm));
+      const float4 L = clo[j], H = chi[j];
+      const V3 bl = of4(L), bh = of4(H), bs = bh - bl;
+      V3 o, d;
+      int nudge = 0, nudge_axis = 0;
+      // an origin anywhere around the mesh: its box grown to twice its size (a flat mesh's: by half the largest extent)
+      auto around = [&]() {
+        const V3 e = v3(std::max(sext.x, 0.25 * scale), std::max(sext.y, 0.25 * scale), std::max(sext.z, 0.25 * scale));
+        return (slo + shi) * 0.5 - e + v3(e.x * 2 * U(rng), e.y * 2 * U(rng), e.z * 2 * U(rng));
+      };
+      if (g == G_RANDOM || (nl == 0.0 && g != G_FACE && g != G_AXIS && g != G_SHARED)) {
+        o = around();
+        const V3 t = bl - bs * 0.25 + v3(bs.x * 1.5 * U(rng), bs.y * 1.5 * U(rng), bs.z * 1.5 * U(rng));
+        d = unitd(t - o + v3(1e-30, 0, 0));
+      } else if (g == G_GRAZE || g == G_GRAZE_EDGE || g == G_SHAPE_EDGE) {
+        // nearly in the plane of the triangle: tilted by 1e-7.5 .. 1e-2 rad (or 0), through a point of the plane
+        // near the triangle (G_GRAZE) or just outside the chunk's box (G_GRAZE_EDGE) or the shape's bbox
+        // (G_SHAPE_EDGE) near one of the triangle's vertices, offset off the plane by 0 .. 1e-3
+        const V3 n = nrm * (1.0 / nl);
+        const V3 ax = unitd(a1), ay = crossd(n, ax);
+        const double phi = 2 * M_PI * U(rng);
+        const V3 w = ax * std::cos(phi) + ay * std::sin(phi);
+        const double th = U(rng) < 0.05 ? 0.0 : logu(-7.5, -2.0);
+        d = w * std::cos(th) + n * (sgn() * std::sin(th));
+        V3 x;
+        if (g == G_GRAZE) {
+          x = p0 + a1 * (-1.0 + 3.0 * U(rng)) + a2 * (-1.0 + 3.0 * U(rng));
+        } else {
+          const int vk = (int)(U(rng) * 3) % 3;
+          x = vk == 0 ? p0 : (vk == 1 ? p0 + a1 : p0 + a2);
+          V3 blo = bl, bhi = bh;
+          if (g == G_SHAPE_EDGE) {  // the box the shape loop reads for this triangle's shape (use_bbox)
+            const float* bb = S.bboxes.data() + shape_of[ent];
+            blo = v3(bb[0] - 0.01, bb[1] - 0.01, bb[2] - 0.01);
+            bhi = v3(bb[3] + 0.01, bb[4] + 0.01, bb[5] + 0.01);
+          }
+          int best = 0;
+          double bd = 1e300, side = 1;
+          for (int a = 0; a < 3; a++) {
+            const double dl = comp(x, a) - comp(blo, a), dh = comp(bhi, a) - comp(x, a);
+            if (dl < bd) { bd = dl; best = a; side = -1; }
+            if (dh < bd) { bd = dh; best = a; side = 1; }
+          }
+          const double mb = 1e-3 * (1.0 + scale) * logu(-1.5, 1.3);
+          setc(x, best, (side < 0 ? comp(blo, best) : comp(bhi, best)) + side * mb);
+        }
+        const double h = U(rng) < 0.3 ? 0.0 : sgn() * logu(-9.0, -3.0) * scale;
+        x = x + n * h;
+        const double tau = sgn() * logu(-2.0, 1.2) * scale;
+        o = x - d * tau;
+      } else if (g == G_ROUND) {
+        // rounding-induced passes: a line in the plane of the triangle, through a point beyond one of its vertices
+        // and outside the chunk's box by 0.3 .. 30 margins (at K = 1e-3), running parallel to that box face, tilted
+        // so that glm's determinant is 1 .. 100 x FLT_EPSILON: there the float u/v values carry errors of order
+        // |s| |e| u / a
+        const V3 n = nrm * (1.0 / nl);
+        const int vk = (int)(U(rng) * 3) % 3;
+        V3 x = vk == 0 ? p0 : (vk == 1 ? p0 + a1 : p0 + a2);
+        int best = 0;
+        double bd = 1e300, side = 1;
+        for (int a = 0; a < 3; a++) {
+          const double dl = comp(x, a) - comp(bl, a), dh = comp(bh, a) - comp(x, a);
+          if (dl < bd) { bd = dl; best = a; side = -1; }
+          if (dh < bd) { bd = dh; best = a; side = 1; }
+        }
+        const double tau = sgn() * logu(-1.0, 0.7) * scale;
+        const double mloc = (double)K_FAST * (1.0 + std::fabs(tau) + bs.x + bs.y + bs.z);
+        V3 ea = v3(0, 0, 0);
+        setc(ea, best, side);
+        const V3 q = ea - n * dotd(n, ea);
+        const double qa = std::fabs(comp(q, best));
+        const double D = (side < 0 ? comp(x, best) - comp(bl, best) : comp(bh, best) - comp(x, best)) +
+                         mloc * logu(-0.5, 1.5);
+        if (qa > 1e-3) x = x + q * (D / qa);
+        V3 w = crossd(n, ea);
+        const double wl = std::sqrt(dotd(w, w));
+        if (wl < 1e-3) { w = unitd(crossd(n, v3(0.3, 0.5, 0.7))); } else { w = w * (1.0 / wl); }
+        const double sth = std::min(1.0, FLT_EPSILON * logu(0.0, 2.0) / nl);
+        d = w * std::sqrt(1.0 - sth * sth) + n * (sgn() * sth);
+        o = x - d * tau;
+      } else if (g == G_FACE) {
+        // origin on (or one float step off) a face of the chunk's box, random direction
+        o = bl + v3(bs.x * U(rng), bs.y * U(rng), bs.z * U(rng));
+        const int a = (int)(U(rng) * 3) % 3;
+        const double fv = U(rng) < 0.5 ? comp(bl, a) : comp(bh, a);
+        const int step = (int)(U(rng) * 3) - 1;
+        float ff = (float)fv;
+        if (step) ff = std::nextafter(ff, step > 0 ? FLT_MAX : -FLT_MAX);
+        setc(o, a, ff);
+        d = unitd(v3(U(rng) - 0.5, U(rng) - 0.5, U(rng) - 0.5));
+      } else if (g == G_AXIS) {
+        const int a = (int)(U(rng) * 3) % 3;
+        const double tiny[6] = {0.0, 1e-40, 1e-38, 1e-30, 1e-10, 1e-4};
+        d = v3(tiny[(int)(U(rng) * 6) % 6] * sgn(), tiny[(int)(U(rng) * 6) % 6] * sgn(),
+               tiny[(int)(U(rng) * 6) % 6] * sgn());
+        setc(d, a, sgn());
+        const V3 t = bl - bs * 0.1 + v3(bs.x * 1.2 * U(rng), bs.y * 1.2 * U(rng), bs.z * 1.2 * U(rng));
+        o = t - d * (sgn() * logu(-2.0, 1.0) * scale);
+      } else if (g == G_SHARED) {
+        // through a vertex (or the midpoint of an edge) that the triangle shares with a triangle of another chunk:
+        // both report the same t, and the first in file order must win
+        const int vk = (int)(U(rng) * 3) % 3;
+        const int pv = 3 * S.idx[3 * ent + vk];
+        uint32_t key[3];
+        memcpy(key, &S.verts[pv], 12);
+        V3 x = v3(S.verts[pv], S.verts[pv + 1], S.verts[pv + 2]);
+        const std::vector<int>& l = at_vertex[{key[0], key[1], key[2]}];
+        int other = -1;
+        for (size_t q = 0; q < l.size(); q++) {
+          const int c = l[(q + (size_t)(U(rng) * l.size())) % l.size()];
+          if ((c >> 6) != j) { other = c; break; }
+        }
+        if (other >= 0 && U(rng) < 0.5) {  // a second shared vertex: the edge's midpoint
+          for (int q = 0; q < 3; q++)
+            for (int q2 = 0; q2 < 3; q2++) {
+              const int pa = 3 * S.idx[3 * ent + q], pb = 3 * S.idx[3 * other + q2];
+              if (q != vk && !memcmp(&S.verts[pa], &S.verts[pb], 12))
+                x = (x + v3(S.verts[pa], S.verts[pa + 1], S.verts[pa + 2])) * 0.5;
+            }
+        }
+        o = around();
+        const V3 of = v3((float)o.x, (float)o.y, (float)o.z);
+        o = of;
+        d = unitd(x - of + v3(1e-30, 0, 0));
+      } else {  // G_BARY: at a point of an edge or a vertex (barycentrics 0 and 1), the origin moved by -4 .. 4 ulps
+        double bu = U(rng), bv = U(rng) * (1.0 - bu);
+        const int e = (int)(U(rng) * 4.0) % 4;
+        if (e == 0) bu = 0.0;
+        else if (e == 1) bv = 0.0;
+        else if (e == 2) bv = 1.0 - bu;
+        else { bu = U(rng) < 0.5 ? 0.0 : 1.0; bv = U(rng) < 0.5 ? 0.0 : 1.0 - bu; }
+        const V3 x = p0 + a1 * bu + a2 * bv;
+        o = around();
+        const V3 of = v3((float)o.x, (float)o.y, (float)o.z);
+        o = of;
+        d = unitd(x - of + v3(1e-30, 0, 0));
+        nudge = (int)(U(rng) * 9.0) - 4;
+        nudge_axis = (int)(U(rng) * 3.0) % 3;
+      }
+      f3 of = mk3((float)o.x, (float)o.y, (float)o.z);
+      if (nudge) {
+        if (nudge_axis == 0) of.x = step_ulps(of.x, nudge);
+        else if (nudge_axis == 1) of.y = step_ulps(of.y, nudge);
+        else of.z = step_ulps(of.z, nudge);
+      }
+      f3 df = mk3((float)d.x, (float)d.y, (float)d.z);
+      if (g != G_AXIS || emit_path) df = normalize(df);
+      const f3 inv = mk3(1.0f / df.x, 1.0f / df.y, 1.0f / df.z);
+      const bool fast = fabsf(inv.x) < FLT_INFV && fabsf(inv.y) < FLT_INFV && fabsf(inv.z) < FLT_INFV;
+      Counts& C = loc[g];
+      C.lines++;
+      if (!fast) C.nofast++;
+      // (a): the line's own chunk
+      const int kb = 64 * j, ke = std::min(nt, kb + 64);
+      bool hit_own = false;
+      for (int k = kb; k < ke; k++) {
+        float t = 0.0f;
+        bool certain = false;
+        const bool h = lane_triangle(S, k, of, df, t, certain);
+        if (certain) {
+          float bx, by, bz;
+          if (tri_test_v(TriData{T.tv0[k], T.te1[k], T.te2[k]}, of, df, bx, by, bz) == 2) C.cm_viol++;
+        }
+        if (h && t > 0.0f) hit_own = true;
+      }
+      const bool culled = fast && !brute_chunk_may_pass(clo.data(), chi.data(), j, of, inv, S.fixed);
+      C.culled += culled;
+      C.hit_own += hit_own;
+      if (culled && hit_own) C.dropped++;
+      // (b): the whole route
+      const bool event = hit_own || culled;
+      Result ref;
+      bool have_ref = false;
+      if (route && (event || (r & 255) == 0)) {
+        const Result ln = lane(S, of, df);
+        ref = reference(S, of, df);
+        have_ref = true;
+        C.route_runs++;
+        if (ln.winner != ref.winner || fbits(ln.t) != fbits(ref.t) || ln.hits != ref.hits) C.route_viol++;
+      }
+      if (emit_path && fast && fabsf(dot(df, df) - 1.0f) <= 1e-6f) {
+        bool in = true;
+        if (inside) {
+          const double oc[3] = {of.x, of.y, of.z};
+          for (int a = 0; a < 3; a++) in = in && oc[a] > in_lo[a] && oc[a] < in_hi[a];
+        }
+        if (in) {
+          // needs exactness: the reference loop's winner lies in a chunk the box misses at the fast coefficient
+          bool exact = false;
+          if (hit_own && !cluster_may_pass(L, H, of, inv, K_FAST)) {
+            if (!have_ref) ref = reference(S, of, df);
+            exact = ref.winner >= 0 && !cluster_may_pass(clo[ref.winner >> 6], chi[ref.winner >> 6], of, inv, K_FAST);
+          }
+          if (exact || r < 4 * emit_n) lem.push_back(Emit{r, {of.x, of.y, of.z, df.x, df.y, df.z}, exact});
+        }
+      }
+    }
+#pragma omp critical
+    {
+      for (int g = 0; g < NGEN; g++) tot[g].add(loc[g]);
+      emits.insert(emits.end(), lem.begin(), lem.end());
+    }
+  }
+  long long cm_cases = 0, cm_accepted = 0, cm_alone = 0;
+  certain_miss_check(S, std::min(nlines, 4000000LL), seed, cm_cases, cm_accepted, cm_alone);
+
+  long long emitted = 0, need_exact = 0;
+  if (emit_path) {
+    std::sort(emits.begin(), emits.end(), [](const Emit& a, const Emit& b) {
+      return a.exact != b.exact ? a.exact : a.r < b.r;
+    });
+    FILE* f = fopen(emit_path, "wb");
+    if (!f) return 3;
+    for (const Emit& e : emits) {
+      if (emitted == emit_n) break;
+      if (fwrite(e.ray, 4, 6, f) != 6) return 3;
+      emitted++;
+      need_exact += e.exact;
+    }
+    fclose(f);
+  }
+  int finite_k = 0;
+  double kmin = HUGE_VAL, kmax = 0.0;
+  for (int c = 0; c < nch; c++)
+    if (clo[c].w < FLT_INFV) {
+      finite_k++;
+      kmin = std::min(kmin, (double)clo[c].w);
+      kmax = std::max(kmax, (double)clo[c].w);
+    }
+  Counts all;
+  printf("{\"tris\": %d, \"chunks\": %d, \"shapes\": %d, \"use_bbox\": %d, \"fixed\": %.9g, \"chunks_culling\": %d, "
+         "\"k_min\": %.6g, \"k_max\": %.6g, \"gens\": {",
+         nt, nch, S.sc.num_shapes, (int)S.use_bbox, (double)S.fixed, finite_k, finite_k ? kmin : 0.0, kmax);
+  for (int g = 0; g < NGEN; g++) {
+    const Counts& C = tot[g];
+    all.add(C);
+    printf("%s\"%s\": {\"lines\": %lld, \"culled\": %lld, \"hit_own\": %lld, \"dropped\": %lld, \"cm_viol\": %lld, "
+           "\"route_runs\": %lld, \"route_viol\": %lld, \"nofast\": %lld}",
+           g ? ", " : "", kGenName[g], C.lines, C.culled, C.hit_own, C.dropped, C.cm_viol, C.route_runs, C.route_viol,
+           C.nofast);
+  }
+  printf("}, \"lines\": %lld, \"culled\": %lld, \"hit_own\": %lld, \"dropped\": %lld, \"cm_viol\": %lld, "
+         "\"route_runs\": %lld, \"route_viol\": %lld, \"cm_cases\": %lld, \"cm_accepted\": %lld, \"cm_alone_viol\": %lld, "
+         "\"emitted\": %lld, \"need_exact\": %lld}\n",
+         all.lines, all.culled, all.hit_own, all.dropped, all.cm_viol, all.route_runs, all.route_viol, cm_cases,
+         cm_accepted, cm_alone, emitted, need_exact);
+  return 0;
+}

@@ -286,6 +286,26 @@ void check_prepared(const char* set, const kdpt_scene& s, const kdpt_options& o,
     CHECK((int)p.shapes.size() == s.num_shapes, "%s: shapes", set);
     const size_t nch = std::max<size_t>(1, (want_t + 63) / 64);
     CHECK(p.chunk_lo.size() == nch && p.chunk_hi.size() == nch, "%s: chunk boxes", set);
+    // each chunk's box holds its triangles, and chunk_lo[j].w is the chunk's own cull coefficient: at least
+    // 8.75 max |e1||e2| of its triangles (the rigorous bound's leading term), +inf from CHUNK_MARGIN_CAP on
+    for (size_t j = 0; j < nch && p.chunk_lo.size() == nch && p.chunk_hi.size() == nch; j++) {
+      const float4 lo = p.chunk_lo[j], hi = p.chunk_hi[j];
+      double pmax = 0.0;
+      bool inside = true;
+      for (size_t k = 64 * j; k < std::min(want_t, 64 * j + 64); k++) {
+        const float4 v = p.tri.tv0[k], a = p.tri.te1[k], b = p.tri.te2[k];
+        pmax = std::max(pmax, std::sqrt((double)a.x * a.x + (double)a.y * a.y + (double)a.z * a.z) *
+                                  std::sqrt((double)b.x * b.x + (double)b.y * b.y + (double)b.z * b.z));
+        for (const float4& e : {make_float4(0, 0, 0, 0), a, b})
+          inside = inside && (double)v.x + e.x >= lo.x && (double)v.x + e.x <= hi.x && (double)v.y + e.y >= lo.y &&
+                   (double)v.y + e.y <= hi.y && (double)v.z + e.z >= lo.z && (double)v.z + e.z <= hi.z;
+      }
+      CHECK(inside, "%s: chunk %zu's box does not hold its triangles", set, j);
+      CHECK(lo.w > 0.0f && (double)lo.w > 8.75 * pmax && hi.w == 0.0f, "%s: chunk %zu coefficient %g (8.75 E = %g)", set,
+            j, (double)lo.w, 8.75 * pmax);
+      CHECK(lo.w == HUGE_VALF ? 8.75 * pmax >= CHUNK_MARGIN_CAP - 1e-3 : 8.75 * pmax < CHUNK_MARGIN_CAP,
+            "%s: chunk %zu coefficient %g against the cap (8.75 E = %g)", set, j, (double)lo.w, 8.75 * pmax);
+    }
     for (int i = 0; i < (int)p.shapes.size(); i++)
       CHECK(fbits(p.shapes[i].lo.w) == s.obj_polyoffsets[i] && fbits(p.shapes[i].hi.w) == s.obj_materialOffsets[i],
             "%s: shape %d", set, i);

@@ -89,6 +89,9 @@ def lib():
         L.orc_load_scene.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, P(OScene)]
         L.orc_free_scene.argtypes = [P(OScene)]
         L.orc_render.argtypes = [P(OScene), P(OOpts), C.c_int, C.c_int, P(C.c_float), P(OStats), C.c_int]
+        L.orc_camera_rays.argtypes = [P(OScene), P(OOpts), C.c_int, P(C.c_float), P(C.c_float)]
+        L.orc_render_rays.argtypes = [P(OScene), P(OOpts), P(C.c_float), P(C.c_float), C.c_int, C.c_int, C.c_int,
+                                      P(C.c_float), P(OStats), C.c_int]
         L.orc_paths_after.argtypes = [P(OScene), P(OOpts), C.c_int, C.c_int, C.c_void_p, P(C.c_int)]
         L.orc_kd_kat.argtypes = [C.c_char_p, C.c_int, C.c_char_p]
         L.orc_utilhash.argtypes = [C.c_uint]
@@ -203,6 +206,35 @@ class OracleScene:
         if rc:
             raise RuntimeError(f"orc_render rc={rc}")
         return img, st
+
+    def camera_rays(self, iteration, **opts):
+        """generateRayFromCamera's W*H rays of `iteration`: (origins, directions), each (W*H, 3) float32."""
+        w, h = self.resolution
+        org, drc = np.empty((w * h, 3), np.float32), np.empty((w * h, 3), np.float32)
+        o = default_opts(**opts)
+        fp = C.POINTER(C.c_float)
+        rc = lib().orc_camera_rays(C.byref(self.s), C.byref(o), iteration, org.ctypes.data_as(fp),
+                                   drc.ctypes.data_as(fp))
+        if rc:
+            raise RuntimeError(f"orc_camera_rays rc={rc}")
+        return org, drc
+
+    def render_rays(self, origins, directions, iter_first=1, iter_count=1, nthreads=0, **opts):
+        """orc_render_rays: the radiance of n caller-supplied rays (kdpt_trace_rays' definition), (n, 3) float32,
+        and the stats."""
+        org = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        drc = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+        if len(org) != len(drc):
+            raise ValueError(f"{len(org)} origins but {len(drc)} directions")
+        rad = np.zeros((len(org), 3), dtype=np.float32)
+        st = OStats()
+        o = default_opts(**opts)
+        fp = C.POINTER(C.c_float)
+        rc = lib().orc_render_rays(C.byref(self.s), C.byref(o), org.ctypes.data_as(fp), drc.ctypes.data_as(fp),
+                                   len(org), iter_first, iter_count, rad.ctypes.data_as(fp), C.byref(st), nthreads)
+        if rc:
+            raise RuntimeError(f"orc_render_rays rc={rc}")
+        return rad, st
 
     def paths_after(self, iteration, stop_depth, **opts):
         from kdtreepathtraceroptimization_amd.runtime import PATH_DTYPE

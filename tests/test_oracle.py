@@ -130,3 +130,29 @@ def test_oracle_reproduces_committed_fullsize_pins(oracle):
         im, st = s.render(rec["iter"], 1, **c["options"])
         assert st.segments == rec["segments"], c["id"]
         assert hashlib.sha256(im.tobytes()).hexdigest() == rec["sha256"], c["id"]
+
+
+@pytest.mark.parametrize("mesh,it,opts", [
+    ("stanford_bunny", 1, {}),                                  # a KD scene
+    ("sphere_low_1", 3, {"enable_kd": 0}),                      # a brute scene
+    ("sphere_low_1", 3, {"enable_kd": 0, "usebbox": 1}),
+    ("stanford_bunny", 2, {}),                                  # iteration 2: the sort
+    ("sphere_low_1", 2, {"enable_kd": 0}),
+    ("stanford_bunny", 3, {"compaction": 0}),                   # finalGather
+    ("sphere_low_1", 1, {"enable_kd": 0, "compaction": 0}),
+], ids=["kd", "brute", "bbox", "kd-iter2", "brute-iter2", "kd-nocompact", "brute-nocompact"])
+def test_render_rays_of_the_camera_rays_is_render(oracle, mesh, it, opts):
+    """orc_render_rays is run_iteration with the camera stage replaced (both share run_bounces): fed orc_camera_rays'
+    output it reproduces orc_render's image bits, segments per bounce and intersect counters."""
+    s = oracle.OracleScene.from_description(load_fixture_scene("cornell", mesh, res=(40, 24), depth=8))
+    img, st = s.render(it, 1, **opts)
+    o, d = s.camera_rays(it, **opts)
+    assert o.shape == d.shape == (40 * 24, 3)
+    rad, rs = s.render_rays(o, d, it, 1, **opts)
+    assert np.array_equal(rad.view(np.uint32), img.reshape(-1, 3).view(np.uint32))
+    assert rs.segments == st.segments and list(rs.seg_per_bounce) == list(st.seg_per_bounce)
+    assert (rs.tri_tests, rs.tri_hits, rs.aabb_tests, rs.bounces) == (st.tri_tests, st.tri_hits, st.aabb_tests, st.bounces)
+    assert float(img.sum()) > 0 and st.segments > 40 * 24
+    # fewer rays than pixels: an n-pixel image of its own (slots, and so seeds, are the rays' indices)
+    half, hs = s.render_rays(o[:333], d[:333], it, 1, **opts)
+    assert half.shape == (333, 3) and hs.seg_per_bounce[0] == 333 and np.isfinite(half).all()
