@@ -431,6 +431,70 @@ int kdpt_trace_rays(kdpt_ctx *ctx, const float *origins, const float *directions
  * (hipEvents on the context's stream, from the zeroing of the radiance buffer to the copy out of it). */
 int kdpt_trace_rays_stats(kdpt_ctx *ctx, long long *segments, long long *traced, double *device_ms);
 
+/* ---- Second moments: per-pixel variance, a noise map and a stopping estimate ----
+ * A render accumulates S = sum of c over the iterations (the image).  With moments on the context also keeps
+ * Q = sum of c^2 (sumsq, 3*W*H floats, the image's layout) and the number of iterations added since both were
+ * zeroed.  For every iteration added to the image and each of its 3*W*H floats, with x that iteration's partial
+ * value: the image gets x exactly as with moments off (same bits), and sumsq = fadd(sumsq, fmul(x, x)), two
+ * float32 roundings, never a fused multiply-add, denormals kept, in the same iteration order as the image's adds.
+ * The oracle renders single iterations, so sumsq is checkable as a bit pattern.
+ *
+ * kdpt_set_moments(ctx, 1) allocates sumsq (zero) and the counter (0).  It is accepted only while nothing has
+ * been added to the image since kdpt_create / kdpt_reset (kdpt_stats.iterations == 0, and no
+ * kdpt_trace_iteration_async or frame either); otherwise KDPT_ERR_UNSUPPORTED -- call kdpt_reset first -- and
+ * nothing changes: the image and the moments must describe the same samples.  enable = 0 waits for the queued work
+ * and frees the buffers; the context is then what it was before.  Setting the state it already has is KDPT_OK.
+ * kdpt_reset zeroes sumsq and the counter with the image; kdpt_set_options, kdpt_set_camera and kdpt_set_tuning
+ * keep them, as they keep the image; kdpt_destroy frees them.
+ *
+ * While moments are on: kdpt_trace_iterations adds each batch with a kernel that reads and writes the image and
+ * sumsq once per batch; kdpt_trace_iteration[_async] gathers into a partial image of the context's, added the
+ * same way (image bits, kdpt_stats and ms_last_iteration keep their meaning); kdpt_render_frames on the context
+ * returns KDPT_ERR_UNSUPPORTED before anything is queued (frames reach the image through a cross-rank reduce that
+ * does not carry second moments; kdpt_render_sharded makes contexts of its own and is unaffected).
+ * kdpt_count_iteration, kdpt_debug_paths, kdpt_cast_rays, kdpt_trace_rays[_moments] and kdpt_camera_rays touch
+ * neither the image nor the moments.  With moments off every path is the one it was.
+ *
+ * kdpt_read_moments copies sumsq (3*W*H floats, host memory; may be NULL) and reports the counter (may be NULL),
+ * after the pipelined adds queued so far.  KDPT_ERR_UNSUPPORTED while moments are off.
+ *
+ * kdpt_noise_map writes, for each pixel p, the relative standard error of its mean, computed on the device in
+ * double arithmetic from the float sums in exactly this order (S = image, Q = sumsq, c = r, g, b):
+ *   n = (double)samples;  m_c = (double)S_c / n;  v_c = ((double)Q_c - (double)S_c * m_c) / (n - 1), < 0 -> 0;
+ *   mbar = ((m_r + m_g) + m_b) / 3;  vbar = ((v_r + v_g) + v_b) / 3;  d = mbar > floor ? mbar : floor;
+ *   noise[p] = (float)(sqrt(vbar / n) / d)
+ * (W*H floats, host memory or memory of the context's device, told apart as kdpt_write_pbo does).  A NaN sum
+ * gives a NaN entry; a pixel that only ever saw black gives exactly 0.  `floor` keeps dark pixels from dominating
+ * and must be finite and > 0, and at least 2 iterations must have been accumulated: KDPT_ERR_ARG otherwise;
+ * KDPT_ERR_UNSUPPORTED while moments are off.  Synchronous; the render state is left alone.  The float32 sums carry
+ * their own rounding (about 2^-24 sqrt(n) relative each), so Q - S^2/n is meaningful only down to a relative
+ * variance of about 1e-6 sqrt(n): below that the estimate is rounding noise (clamped at 0), not signal.
+ *
+ * kdpt_noise_estimate reduces the same per-pixel values on the device: pixels = W*H, nonfinite = the entries that
+ * are NaN or inf, max and mean over the finite entries (the mean summed in double; 0 when there is none), above =
+ * the finite entries > threshold (NaN: KDPT_ERR_ARG).  Other errors as kdpt_noise_map.  The reduction has a fixed
+ * order and uses no floating-point atomics: two calls on the same state return identical bytes, so a stopping rule
+ * built on it is reproducible. */
+int kdpt_set_moments(kdpt_ctx *ctx, int enable);
+int kdpt_read_moments(kdpt_ctx *ctx, float *sumsq, long long *samples);
+int kdpt_noise_map(kdpt_ctx *ctx, float floor, float *noise);
+typedef struct kdpt_noise {  /* 48 bytes */
+    long long samples, pixels, above, nonfinite;
+    double mean;   /* over the finite pixels */
+    float max;     /* over the finite pixels */
+    float pad_;
+} kdpt_noise;
+int kdpt_noise_estimate(kdpt_ctx *ctx, float floor, float threshold, kdpt_noise *out);
+/* kdpt_trace_rays with one more output, and its contract for n, first_iter, count and flags, its acceptance rule,
+ * the n <= W*H limit and what it leaves alone.  radiance is bit-equal to kdpt_trace_rays' for the same arguments;
+ * sumsq[3 i + c] (3*n floats, host or device memory) is the sum over the call's iterations, in order, of
+ * fl(x * x), x being what that iteration's gathers add to ray i -- so per-ray error bars take one call, not
+ * `count` calls.  A rejected ray is NaN in both.  sumsq == NULL with work to do is KDPT_ERR_ARG.  Each iteration
+ * gathers into a buffer of the query's own: nothing is shared with the render's moments, and the call works
+ * whether kdpt_set_moments is on or off.  kdpt_trace_rays_stats reports it as it reports kdpt_trace_rays. */
+int kdpt_trace_rays_moments(kdpt_ctx *ctx, const float *origins, const float *directions, long long n,
+                            int first_iter, int count, int flags, float *radiance, float *sumsq);
+
 int kdpt_destroy(kdpt_ctx *ctx);
 /* The message of the most recent failing call of any kdpt_* function on the calling thread (each thread has its
  * own; "" before the first failure).  A successful call leaves it alone, so read it only after a non-OK return.

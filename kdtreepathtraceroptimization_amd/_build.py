@@ -32,7 +32,7 @@ DEVICE_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 # the sources whose device code the runtime's kernels are compiled from
 KERNEL_SOURCES = ["kdpt_device.h", "kdpt_math.h", "kdpt_runtime.hip", "glibc_sincostab.h", "kernels_gen.h",
                   "kernels_trace.h", "kernels_brute.h", "kernels_shade.h", "kernels_image.h", "kernels_cast.h",
-                  "kernels_rays.h", "kernels_selftest.h"]
+                  "kernels_rays.h", "kernels_selftest.h", "kernels_moments.h"]
 
 
 def _run(cmd, log=None):

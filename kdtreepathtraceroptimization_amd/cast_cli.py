@@ -13,7 +13,9 @@ saved PNGs are that image flipped in x).  One JSON line reports the counts and t
 With --radiance SPP the rays are path traced instead (kdpt_trace_rays, iterations 1 .. SPP): --rays writes the mean
 radiance (n x 3 float32; n at most the context's W H, which --res sets) to --out, and --camera traces the rays the
 device itself generates for each iteration (kdpt_camera_rays: jitter and depth of field included) and writes
-BASE.radiance.npy (H x W x 3), the render's image divided by SPP.  A rejected ray's radiance is NaN.
+BASE.radiance.npy (H x W x 3), the render's image divided by SPP.  A rejected ray's radiance is NaN.  With --stderr
+(SPP >= 2) the per-ray, per-channel standard error of that mean is written beside it (OUT.stderr.npy /
+BASE.stderr.npy, float64), computed from the sum and the sum of squares (kdpt_trace_rays_moments).
 
 Directions are normalised with the reference's glm::normalize unless --no-normalize is given; then a direction
 that is not unit length (|dot(d, d) - 1| > 1e-6) is rejected, like any ray with a non-finite component (kind -1).
@@ -67,6 +69,9 @@ def parse_args(argv=None) -> argparse.Namespace:
                     help="path trace the rays instead (kdpt_trace_rays): mean radiance over SPP iterations, written "
                          "as float32 .npy -- n x 3 to --out with --rays (n <= W H of the context: see --res), "
                          "H x W x 3 to BASE.radiance.npy with --camera (the device's own camera rays)")
+    ap.add_argument("--stderr", action="store_true",
+                    help="with --radiance SPP (>= 2): also write the standard error of the mean per ray and channel "
+                         "(float64 .npy; OUT.stderr.npy / BASE.stderr.npy), from kdpt_trace_rays_moments' two sums")
     ap.add_argument("--chunk", type=int, default=None, help="rays per chunk (knob cast_chunk)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--kd-build", choices=["gpu", "host"], default="gpu")
@@ -80,26 +85,55 @@ def radiance_main(a: argparse.Namespace, sd, rays) -> int:
     from .runtime import PathTracer, default_options
     if a.radiance < 1:
         raise SystemExit("--radiance: SPP must be >= 1")
+    if a.stderr and a.radiance < 2:
+        raise SystemExit("--stderr: a standard error needs --radiance SPP >= 2")
     W, H = sd.resolution
+    sumsq = None
     with PathTracer(sd, default_options(short_stack=0 if a.bare else 1), device=a.device) as pt:
         t0 = time.perf_counter()
         if rays is not None:
             if len(rays[0]) > W * H:
                 raise SystemExit(f"--radiance: {len(rays[0])} rays exceed the context's {W} x {H} paths (raise --res)")
-            total = pt.trace_rays(rays[0], rays[1], 1, a.radiance, normalize=not a.no_normalize)
+            if a.stderr:
+                total, sumsq = pt.trace_rays(rays[0], rays[1], 1, a.radiance, normalize=not a.no_normalize,
+                                             moments=True)
+            else:
+                total = pt.trace_rays(rays[0], rays[1], 1, a.radiance, normalize=not a.no_normalize)
         else:
             total = np.zeros((W * H, 3), np.float32)
+            sumsq = np.zeros((W * H, 3), np.float32) if a.stderr else None
             for it in range(1, a.radiance + 1):
                 o, d = pt.camera_rays(it)
-                total += pt.trace_rays(o, d, it, 1, normalize=False)
+                r = pt.trace_rays(o, d, it, 1, normalize=False)
+                total += r
+                if a.stderr:
+                    sumsq += r * r
         dt = time.perf_counter() - t0
     mean = total / np.float32(a.radiance)
     out = a.out if rays is not None else a.out + ".radiance.npy"
     np.save(out, mean if rays is not None else mean.reshape(H, W, 3))
+    written = [out]
+    if a.stderr:
+        se = standard_error(total, sumsq, a.radiance)
+        se_out = (out[:-4] if out.endswith(".npy") else out) + ".stderr.npy" if rays is not None else a.out + ".stderr.npy"
+        np.save(se_out, se if rays is not None else se.reshape(H, W, 3))
+        written.append(se_out)
     print(json.dumps({"scene": a.scene, "mesh": a.mesh, "n": len(mean), "spp": a.radiance,
                       "invalid": int(np.sum(np.isnan(mean).all(axis=1))), "seconds": round(dt, 4),
-                      "written": [out]}), flush=True)
+                      "written": written}), flush=True)
     return 0
+
+
+def standard_error(total: np.ndarray, sumsq: np.ndarray, samples: int) -> np.ndarray:
+    """The standard error of the mean per ray and channel, in float64 from the two float32 sums, with
+    kdpt_noise_map's formula without its division by the floored mean: m = S / n, v = max((Q - S m) / (n - 1), 0),
+    sqrt(v / n)."""
+    n = float(samples)
+    s, q = total.astype(np.float64), sumsq.astype(np.float64)
+    m = s / n
+    v = (q - s * m) / (n - 1.0)
+    v = np.where(v < 0, 0.0, v)  # (NaN stays NaN)
+    return np.sqrt(v / n)
 
 
 def main(argv=None) -> int:

@@ -17,6 +17,11 @@ optionally the Radiance HDR image::saveHDR writes).  Flag -> reference variable:
     --brute            ENABLEKD = false                --bbox           USEBBOX = true (with --brute)
     --viz-kd           VIZKD = true                    --testing        TESTINGMODE (per-bounce timing)
     --iterations N     the scene's ITERATIONS          --res W H / --depth D   scene overrides
+
+Not in the reference: --target-noise E renders until the image's mean relative standard error (kdpt_noise_estimate
+over the per-pixel second moments, --noise-floor F) is <= E, checking after each round of pipeline x batch
+iterations from --min-spp N on, with --iterations as the upper limit; --noise-map also writes BASE.noise.npy.  The
+PNG / HDR are divided by the samples actually rendered.  Without --target-noise nothing changes.
 """
 from __future__ import annotations
 
@@ -72,7 +77,29 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--kd-build", choices=["gpu", "host"], default="gpu",
                     help="build the KD tree on the GPU (default; byte-identical) or with the host recursion")
     ap.add_argument("--dry-run", action="store_true", help="load and build the scene, print it, render nothing")
-    return ap.parse_args(argv)
+    ap.add_argument("--target-noise", type=float, default=None, metavar="E",
+                    help="adaptive stop: render in rounds of pipeline x batch iterations and stop once the mean "
+                         "relative standard error of the pixel means (kdpt_noise_estimate) is <= E; --iterations "
+                         "becomes the upper limit")
+    ap.add_argument("--noise-floor", type=float, default=1e-2, metavar="F",
+                    help="the noise estimate's floor on the pixel mean (default 1e-2)")
+    ap.add_argument("--min-spp", type=int, default=2, metavar="N",
+                    help="with --target-noise: no estimate before N samples per pixel (at least 2)")
+    ap.add_argument("--noise-map", action="store_true",
+                    help="with --target-noise: also write BASE.noise.npy (H x W float32, kdpt_noise_map)")
+    a = ap.parse_args(argv)
+    if a.target_noise is None and a.noise_map:
+        ap.error("--noise-map needs --target-noise")
+    if a.target_noise is not None:
+        if not a.target_noise >= 0:
+            ap.error("--target-noise must be >= 0")
+        if not (a.noise_floor > 0 and a.noise_floor < float("inf")):
+            ap.error("--noise-floor must be finite and > 0")
+        if a.min_spp < 2:
+            ap.error("--min-spp must be >= 2 (a variance needs two samples)")
+        if a.testing:
+            ap.error("--target-noise renders in pipelined rounds; it cannot be combined with --testing")
+    return a
 
 
 def options_from_args(a: argparse.Namespace):
@@ -82,6 +109,26 @@ def options_from_args(a: argparse.Namespace):
                            testing_mode=int(a.testing), compaction=0 if a.no_compaction else 1,
                            enable_kd=0 if a.brute else 1, viz_kd=int(a.viz_kd), use_bbox=int(a.bbox),
                            short_stack=0 if a.bare else 1, bounce_cap=a.bounce_cap)
+
+
+def render_to_noise(pt, a: argparse.Namespace, limit: int):
+    """--target-noise E: rounds of pipeline x batch iterations (one full pipeline each), with second moments on;
+    after every round from --min-spp on, kdpt_noise_estimate, and the render stops once its mean is <= E or `limit`
+    iterations are done.  Returns the samples per pixel rendered and the last estimate (None: fewer than --min-spp
+    were allowed)."""
+    pt.set_moments(True)
+    per_round = max(1, min(16, a.pipeline)) * max(1, min(16, a.batch))
+    done, est = 0, None
+    while done < limit:
+        n = min(per_round, limit - done)
+        pt.trace_iterations(a.first_iteration + done, n, pipeline=a.pipeline, batch=a.batch)
+        pt.synchronize()
+        done += n
+        if done >= a.min_spp:
+            est = pt.noise_estimate(a.noise_floor, a.target_noise)
+            if est.mean <= a.target_noise:
+                break
+    return done, est
 
 
 def main(argv=None) -> int:
@@ -103,9 +150,12 @@ def main(argv=None) -> int:
         sd.close()
         return 0
     opt = options_from_args(a)
+    spp, est = iterations, None  # the samples per pixel actually rendered, and the adaptive stop's last estimate
     with PathTracer(sd, opt, device=a.device) as pt:
         t0 = time.perf_counter()
-        if a.testing:  # one synchronous pathtrace() per iteration, like TESTINGMODE
+        if a.target_noise is not None:
+            spp, est = render_to_noise(pt, a, iterations)
+        elif a.testing:  # one synchronous pathtrace() per iteration, like TESTINGMODE
             for it in range(a.first_iteration, a.first_iteration + iterations):
                 pt.trace_iteration(it)
         else:
@@ -113,17 +163,26 @@ def main(argv=None) -> int:
             pt.synchronize()
         dt = time.perf_counter() - t0
         st = pt.stats()
-        base = a.out or f"{hdr['file'] or os.path.splitext(os.path.basename(a.scene))[0]}.{iterations}samp"
+        base = a.out or f"{hdr['file'] or os.path.splitext(os.path.basename(a.scene))[0]}.{spp}samp"
         written = []
         if not a.no_png:
-            pt.save_png(base + ".png", float(iterations))
+            pt.save_png(base + ".png", float(spp))
             written.append(base + ".png")
         if a.hdr:
-            pt.save_hdr(base + ".hdr", float(iterations))
+            pt.save_hdr(base + ".hdr", float(spp))
             written.append(base + ".hdr")
+        if a.noise_map and spp >= 2:
+            import numpy as np
+            np.save(base + ".noise.npy", pt.noise_map(a.noise_floor))
+            written.append(base + ".noise.npy")
     info.update({"segments": int(st.total_segments), "seconds": round(dt, 4),
                  "mrays_per_s": round(st.total_segments / dt / 1e6, 2) if dt > 0 else None,
-                 "ms_per_iteration": round(dt * 1e3 / iterations, 4), "written": written})
+                 "ms_per_iteration": round(dt * 1e3 / spp, 4), "written": written})
+    if a.target_noise is not None:
+        info.update({"spp": spp, "target_noise": a.target_noise, "noise_floor": a.noise_floor,
+                     "noise": None if est is None else {
+                         "mean": est.mean, "max": est.max, "above": int(est.above), "nonfinite": int(est.nonfinite),
+                         "pixels": int(est.pixels), "samples": int(est.samples)}})
     if a.testing:
         info["intersect_ms_total"] = round(st.intersect_ms_total, 4)
     print(json.dumps(info), flush=True)

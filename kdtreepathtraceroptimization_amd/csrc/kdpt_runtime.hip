@@ -64,6 +64,7 @@ bool g_cu_mask_streams = true;  // kdpt_set_tuning(NULL, "cu_mask_streams", v): 
 #include "kernels_cast.h"
 #include "kernels_rays.h"
 #include "kernels_selftest.h"
+#include "kernels_moments.h"
 
 // ---------------------------------------------------------------------------
 // Context
@@ -240,6 +241,22 @@ struct kdpt_ctx {
   unsigned long long* query_totals = nullptr;  // [0] ShadeArgs::total_segments, [1..3] trace_total / trace_rays
   long long query_segments = 0, query_traced = 0;  // of the last kdpt_trace_rays (kdpt_trace_rays_stats)
   double query_ms = 0;                             // ... and its device time
+  // kdpt_trace_rays_moments: the partial buffer each of the query's iterations gathers into (zeroed by a fill on
+  // the stream) and the query's second moments, made on first use; nothing here is shared with the render's moments
+  float* query_partial = nullptr;  // [3 npix]
+  float* query_sumsq = nullptr;    // [3 npix]
+  // per-pixel second moments (kdpt_set_moments): sumsq beside the image, the partial image the solo state gathers
+  // into while they are on (added with k_accumulate_moments at nb = 1), the number of iterations added since both
+  // were zeroed, and kdpt_noise_map's / kdpt_noise_estimate's buffers.  All null / 0 while moments are off.
+  bool moments = false;
+  float* mom_sumsq = nullptr;    // [3 npix]
+  float* mom_partial = nullptr;  // [3 npix]
+  long long mom_samples = 0;
+  float* noise_stage = nullptr;         // [npix] kdpt_noise_map into host memory
+  NoisePartial* noise_parts = nullptr;  // [workgroups + 1] k_noise_partials' partials, then k_noise_final's result
+  // an iteration (or a frame) has been added into the image since create / kdpt_reset: with stats.iterations what
+  // kdpt_set_moments(1) refuses on (kdpt_trace_iteration_async counts no iteration)
+  bool accumulated = false;
 };
 
 namespace {
@@ -290,9 +307,11 @@ int dupload(kdpt_ctx* c, T** p, const T* src, size_t n) {
 }
 
 int launch_iteration(kdpt_ctx* c, int iter, int stop_depth, bool count);
+int accumulate_iteration(kdpt_ctx* c, int iter);
 void release_comm(kdpt_ctx* c);  // (multi-GPU section, end of file)
 void unregister_host(kdpt_ctx* c);
 void free_cast_buffers(kdpt_ctx* c);  // (ray queries, end of file)
+void free_moments(kdpt_ctx* c);       // (second moments, end of file)
 // A batch that starts from caller-supplied rays instead of the camera's (kdpt_trace_rays; one iteration per
 // batch): the rays in device memory, and where the shading adds what it would add to the context's intersect
 // totals (kdpt_ctx::trace_total's layout).
@@ -429,6 +448,27 @@ __global__ void k_accumulate_batch(float* __restrict__ image, PartialImages part
   float v = image[i];
   for (int b = 0; b < parts.nb; b++) v += parts.p[b][i];
   image[i] = v;
+}
+
+// The add of nb partial images (iteration order) into `target` on stream st: k_accumulate_batch, or, when the
+// context keeps second moments and the target is its image, k_accumulate_moments, which adds the squares into
+// mom_sumsq in the same pass.
+int launch_accumulate(kdpt_ctx* c, float* target, const float* const* partials, int nb, hipStream_t st) {
+  const int n3 = 3 * c->npix;
+  if (c->moments && target == c->image) {
+    MomentParts parts{};
+    parts.nb = nb;
+    for (int b = 0; b < nb; b++) parts.p[b] = partials[b];
+    hipLaunchKernelGGL(k_accumulate_moments, dim3((n3 + 255) / 256), dim3(256), 0, st, target, c->mom_sumsq, parts,
+                       n3);
+  } else {
+    PartialImages parts{};
+    parts.nb = nb;
+    for (int b = 0; b < nb; b++) parts.p[b] = partials[b];
+    hipLaunchKernelGGL(k_accumulate_batch, dim3((n3 + 255) / 256), dim3(256), 0, st, target, parts, n3);
+  }
+  HIP_TRY(hipGetLastError());
+  return KDPT_OK;
 }
 
 // Read back the intersect-kernel events of finished iterations (testing_mode).
@@ -1137,7 +1177,10 @@ int kdpt_reset(kdpt_ctx* c) {
   HIP_TRY(hipMemsetAsync(c->image, 0, sizeof(float) * 3 * (size_t)c->npix, c->stream));
   HIP_TRY(hipMemsetAsync(c->total_segments, 0, sizeof(unsigned long long), c->stream));
   HIP_TRY(hipMemsetAsync(c->trace_total, 0, 3 * sizeof(unsigned long long), c->stream));
+  if (c->moments) HIP_TRY(hipMemsetAsync(c->mom_sumsq, 0, sizeof(float) * 3 * (size_t)c->npix, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  c->mom_samples = 0;
+  c->accumulated = false;
   memset(&c->stats, 0, sizeof c->stats);
   c->stats.intersect_grid_share = 1.0f;
   c->cast_rays = c->cast_traced = 0;
@@ -1148,7 +1191,7 @@ int kdpt_reset(kdpt_ctx* c) {
 int kdpt_trace_iteration_async(kdpt_ctx* c, int frame, int iter) {
   (void)frame;  // unused by the reference too
   if (!c) return fail(KDPT_ERR_ARG, "null ctx");
-  return launch_iteration(c, iter, -1, false);
+  return accumulate_iteration(c, iter);
 }
 
 int kdpt_synchronize(kdpt_ctx* c) {
@@ -1176,7 +1219,7 @@ int kdpt_trace_iteration(kdpt_ctx* c, int frame, int iter) {
   HIP_TRY(hipSetDevice(c->device));
   IterState& it = c->solo;
   HIP_TRY(hipEventRecord(it.ev0, c->stream));
-  int rc = launch_iteration(c, iter, -1, false);
+  int rc = accumulate_iteration(c, iter);
   if (rc) return rc;
   HIP_TRY(hipEventRecord(it.ev1, c->stream));
   HIP_TRY(hipMemcpyAsync(it.h_counts, it.counts, sizeof(int) * (c->cap + 3), hipMemcpyDeviceToHost, c->stream));
@@ -1289,14 +1332,15 @@ int enqueue_iterations(kdpt_ctx* c, int first_iter, int count, int stride, int p
       }
       first = false;
     }
-    const int n3 = 3 * c->npix;
-    PartialImages parts{};
-    parts.nb = nb;
-    for (int b = 0; b < nb; b++) parts.p[b] = its[b]->image;  // in iteration order
-    hipLaunchKernelGGL(k_accumulate_batch, dim3((n3 + 255) / 256), dim3(256), 0, st, target, parts, n3);
-    HIP_TRY(hipGetLastError());
+    const float* partials[MAXB];
+    for (int b = 0; b < nb; b++) partials[b] = its[b]->image;  // in iteration order
+    if ((rc = launch_accumulate(c, target, partials, nb, st))) return rc;
     HIP_TRY(hipEventRecord(grp.acc_ev, st));
     c->acc_last = grp.acc_ev;
+    if (target == c->image) {
+      c->accumulated = true;
+      if (c->moments) c->mom_samples += nb;
+    }
   }
   c->stats.iterations += count;
   return KDPT_OK;
@@ -1480,6 +1524,7 @@ int kdpt_destroy(kdpt_ctx* c) {
   if (c->reduce_stream) (void)hipStreamDestroy(c->reduce_stream);
   for (void* p : c->allocs) (void)hipFree(p);
   if (c->pbo_staging) (void)hipFree(c->pbo_staging);
+  free_moments(c);
   free_cast_buffers(c);
   for (auto e : c->cast_ev)
     if (e) (void)hipEventDestroy(e);
@@ -1950,6 +1995,21 @@ int launch_iteration(kdpt_ctx* c, int iter, int stop_depth, bool count) {
   return launch_batch(c, &it, &iter, 1, c->stream, c->trace_grid, stop_depth, count, &it->bounce_ev);
 }
 
+// kdpt_trace_iteration[_async]: one whole iteration of the solo state added to the image.  With moments off the
+// state gathers straight into the image; with moments on into the context's partial image (mom_partial, which the
+// camera kernel clears as it clears the pipeline states'), added to the image and to the second moments on the
+// same stream at nb = 1.
+int accumulate_iteration(kdpt_ctx* c, int iter) {
+  int rc = launch_iteration(c, iter, -1, false);
+  if (rc) return rc;
+  c->accumulated = true;
+  if (!c->moments) return KDPT_OK;
+  const float* partial = c->mom_partial;
+  if ((rc = launch_accumulate(c, c->image, &partial, 1, c->stream))) return rc;
+  c->mom_samples++;
+  return KDPT_OK;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -2112,6 +2172,7 @@ int finish_frame(kdpt_ctx* c, const float* sum, float* out, int k, hipStream_t s
   parts.nb = 1;
   hipLaunchKernelGGL(k_accumulate_batch, dim3((n3 + 255) / 256), dim3(256), 0, st, c->image, parts, n3);
   HIP_TRY(hipGetLastError());
+  c->accumulated = true;
   if (out) HIP_TRY(hipMemcpyAsync(out + (size_t)k * n3, sum, sizeof(float) * n3, hipMemcpyDefault, st));
   return KDPT_OK;
 }
@@ -2172,6 +2233,10 @@ int kdpt_comm_init(kdpt_ctx* c, int nranks, int rank, const unsigned char* id) {
 int kdpt_render_frames(kdpt_ctx* c, int first_frame, int frames, int spp, int pipeline, int batch, float* out) {
   int rc = check_frames_args(c, first_frame, frames, spp);
   if (rc) return rc;
+  if (c->moments)
+    return fail(KDPT_ERR_UNSUPPORTED,
+                "kdpt_render_frames: the context keeps second moments (kdpt_set_moments), and frames reach the "
+                "image through a cross-rank reduce that does not carry them; turn moments off first");
   HIP_TRY(hipSetDevice(c->device));
   const Rccl* R = c->comm ? rccl() : nullptr;
   if (c->nranks > 1 && !R && !c->external_reduce) return fail(KDPT_ERR_ARG, "kdpt_comm_init first");
@@ -2526,20 +2591,27 @@ int kdpt_camera_rays(kdpt_ctx* c, int iter, float* origins, float* directions) {
   return KDPT_OK;
 }
 
-int kdpt_trace_rays(kdpt_ctx* c, const float* origins, const float* directions, long long n, int first_iter,
-                    int count, int flags, float* radiance) {
-  if (n < 0) return fail(KDPT_ERR_ARG, "kdpt_trace_rays: n must be >= 0");
-  if (count < 0) return fail(KDPT_ERR_ARG, "kdpt_trace_rays: count must be >= 0");
-  if (first_iter < 1) return fail(KDPT_ERR_ARG, "kdpt_trace_rays: first_iter must be >= 1");
-  if (flags & ~KDPT_CAST_NORMALIZE) return fail(KDPT_ERR_ARG, "kdpt_trace_rays: unknown bit in flags");
-  if (!c) return fail(KDPT_ERR_ARG, "kdpt_trace_rays: null ctx");
+namespace {
+
+// kdpt_trace_rays (moments = false: the query's state gathers straight into its radiance buffer) and
+// kdpt_trace_rays_moments (each iteration gathers into the query's partial buffer, zeroed by a fill on the stream,
+// which k_accumulate_moments then adds into the radiance and sumsq buffers over the 3 n floats).  `who` names the
+// entry point in the messages.
+int trace_rays_query(kdpt_ctx* c, const float* origins, const float* directions, long long n, int first_iter,
+                     int count, int flags, float* radiance, float* sumsq, bool moments, const std::string& who) {
+  if (n < 0) return fail(KDPT_ERR_ARG, who + ": n must be >= 0");
+  if (count < 0) return fail(KDPT_ERR_ARG, who + ": count must be >= 0");
+  if (first_iter < 1) return fail(KDPT_ERR_ARG, who + ": first_iter must be >= 1");
+  if (flags & ~KDPT_CAST_NORMALIZE) return fail(KDPT_ERR_ARG, who + ": unknown bit in flags");
+  if (!c) return fail(KDPT_ERR_ARG, who + ": null ctx");
   if (n > (long long)c->npix)
-    return fail(KDPT_ERR_ARG, "kdpt_trace_rays: n = " + std::to_string(n) + " exceeds the context's W * H = " +
+    return fail(KDPT_ERR_ARG, who + ": n = " + std::to_string(n) + " exceeds the context's W * H = " +
                                   std::to_string(c->npix) + " paths (create a context of a larger resolution)");
   const bool work = n > 0 && count > 0;
-  if (work && !origins) return fail(KDPT_ERR_ARG, "kdpt_trace_rays: null origins");
-  if (work && !directions) return fail(KDPT_ERR_ARG, "kdpt_trace_rays: null directions");
-  if (work && !radiance) return fail(KDPT_ERR_ARG, "kdpt_trace_rays: null radiance");
+  if (work && !origins) return fail(KDPT_ERR_ARG, who + ": null origins");
+  if (work && !directions) return fail(KDPT_ERR_ARG, who + ": null directions");
+  if (work && !radiance) return fail(KDPT_ERR_ARG, who + ": null radiance");
+  if (work && moments && !sumsq) return fail(KDPT_ERR_ARG, who + ": null sumsq");
   if (!work) return KDPT_OK;
   if (c->shade_oob) return refuse_shading();
   int rc = kdpt_synchronize(c);  // everything queued on the context first
@@ -2547,6 +2619,10 @@ int kdpt_trace_rays(kdpt_ctx* c, const float* origins, const float* directions, 
   const hipStream_t st = c->stream;
   IterState* q = &c->query;
   const size_t m = (size_t)n, npix = (size_t)c->npix;
+  if (moments && ((!c->query_partial && (rc = dalloc(c, &c->query_partial, 3 * npix))) ||
+                  (!c->query_sumsq && (rc = dalloc(c, &c->query_sumsq, 3 * npix)))))
+    return rc;
+  q->image = moments ? c->query_partial : c->query_image;  // where this call's gathers add
   RaySource src{{origins, directions, (int)n, (flags & KDPT_CAST_NORMALIZE) ? 1 : 0}, c->query_totals + 1};
   if (!on_context_device(c, origins)) {
     HIP_TRY(hipMemcpyAsync(c->query_stage, origins, sizeof(float) * 3 * m, hipMemcpyHostToDevice, st));
@@ -2560,12 +2636,26 @@ int kdpt_trace_rays(kdpt_ctx* c, const float* origins, const float* directions, 
   // pixel i of the query's image is ray i: the gathers add into it in iteration order, from zero
   HIP_TRY(hipMemsetAsync(c->query_image, 0, sizeof(float) * 3 * m, st));
   HIP_TRY(hipMemsetAsync(c->query_totals, 0, sizeof(unsigned long long) * 4, st));
+  if (moments) HIP_TRY(hipMemsetAsync(c->query_sumsq, 0, sizeof(float) * 3 * m, st));
   for (int k = 0; k < count; k++) {
     const int iter = first_iter + k;
+    if (moments) HIP_TRY(hipMemsetAsync(c->query_partial, 0, sizeof(float) * 3 * m, st));
     if ((rc = launch_batch(c, &q, &iter, 1, st, c->trace_grid, -1, false, nullptr, &src))) return rc;
+    if (moments) {
+      const int m3 = 3 * (int)n;
+      MomentParts parts{};
+      parts.p[0] = c->query_partial;
+      parts.nb = 1;
+      hipLaunchKernelGGL(k_accumulate_moments, dim3((m3 + 255) / 256), dim3(256), 0, st, c->query_image,
+                         c->query_sumsq, parts, m3);
+      HIP_TRY(hipGetLastError());
+    }
   }
   HIP_TRY(hipMemcpyAsync(radiance, c->query_image, sizeof(float) * 3 * m,
                          on_context_device(c, radiance) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  if (moments)
+    HIP_TRY(hipMemcpyAsync(sumsq, c->query_sumsq, sizeof(float) * 3 * m,
+                           on_context_device(c, sumsq) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
   HIP_TRY(hipEventRecord(q->ev1, st));
   unsigned long long totals[4] = {0, 0, 0, 0};
   HIP_TRY(hipMemcpyAsync(totals, c->query_totals, sizeof totals, hipMemcpyDeviceToHost, st));
@@ -2578,10 +2668,155 @@ int kdpt_trace_rays(kdpt_ctx* c, const float* origins, const float* directions, 
   return check_fault(q, st);
 }
 
+}  // namespace
+
+int kdpt_trace_rays(kdpt_ctx* c, const float* origins, const float* directions, long long n, int first_iter,
+                    int count, int flags, float* radiance) {
+  return trace_rays_query(c, origins, directions, n, first_iter, count, flags, radiance, nullptr, false,
+                          "kdpt_trace_rays");
+}
+
+int kdpt_trace_rays_moments(kdpt_ctx* c, const float* origins, const float* directions, long long n, int first_iter,
+                            int count, int flags, float* radiance, float* sumsq) {
+  return trace_rays_query(c, origins, directions, n, first_iter, count, flags, radiance, sumsq, true,
+                          "kdpt_trace_rays_moments");
+}
+
 int kdpt_trace_rays_stats(kdpt_ctx* c, long long* segments, long long* traced, double* device_ms) {
   if (!c) return fail(KDPT_ERR_ARG, "kdpt_trace_rays_stats: null ctx");
   if (segments) *segments = c->query_segments;
   if (traced) *traced = c->query_traced;
   if (device_ms) *device_ms = c->query_ms;
+  return KDPT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Per-pixel second moments (include/kdpt.h "Second moments"): kdpt_set_moments, kdpt_read_moments,
+// kdpt_noise_map and kdpt_noise_estimate.  While they are on, every add of partial images into the image goes
+// through k_accumulate_moments (launch_accumulate), which adds the squares into mom_sumsq in the same pass; the
+// shading, intersect and gather kernels never know.
+// ---------------------------------------------------------------------------
+namespace {
+
+// The buffers of kdpt_set_moments go, and the solo state gathers straight into the image again.  (The caller has
+// drained the context's streams.)
+void free_moments(kdpt_ctx* c) {
+  void* const bufs[] = {c->mom_sumsq, c->mom_partial, c->noise_stage, c->noise_parts};
+  for (void* p : bufs)
+    if (p) (void)hipFree(p);
+  c->mom_sumsq = c->mom_partial = c->noise_stage = nullptr;
+  c->noise_parts = nullptr;
+  c->mom_samples = 0;
+  c->moments = false;
+  if (c->solo.zero_partial) {
+    c->solo.image = c->image;
+    c->solo.zero_partial = false;
+  }
+}
+
+// k_noise_partials' workgroups: NOISE_BLOCK * NOISE_PER_LANE pixels each.
+int noise_blocks(const kdpt_ctx* c) {
+  const int per = NOISE_BLOCK * NOISE_PER_LANE;
+  return (int)(((long long)c->npix + per - 1) / per);
+}
+
+// What kdpt_noise_map and kdpt_noise_estimate refuse, in the same order.
+int check_noise_args(const kdpt_ctx* c, float floor, const std::string& who) {
+  if (!c) return fail(KDPT_ERR_ARG, who + ": null ctx");
+  if (!(std::isfinite(floor) && floor > 0.0f)) return fail(KDPT_ERR_ARG, who + ": floor must be finite and > 0");
+  if (!c->moments) return fail(KDPT_ERR_UNSUPPORTED, who + ": moments are off (kdpt_set_moments)");
+  if (c->mom_samples < 2)
+    return fail(KDPT_ERR_ARG, who + ": " + std::to_string(c->mom_samples) +
+                                  " iteration(s) accumulated, a variance needs at least 2");
+  return KDPT_OK;
+}
+
+}  // namespace
+
+int kdpt_set_moments(kdpt_ctx* c, int enable) {
+  if (!c) return fail(KDPT_ERR_ARG, "kdpt_set_moments: null ctx");
+  const bool on = enable != 0;
+  if (on == c->moments) return KDPT_OK;
+  if (on && (c->stats.iterations != 0 || c->accumulated))
+    return fail(KDPT_ERR_UNSUPPORTED,
+                "kdpt_set_moments: iterations have been accumulated into the image since the last kdpt_reset; "
+                "call kdpt_reset first, so that the image and the moments describe the same samples");
+  int rc = kdpt_synchronize(c);  // everything queued on the context first (the solo state changes its target)
+  if (rc) return rc;
+  if (!on) {
+    free_moments(c);
+    return KDPT_OK;
+  }
+  const size_t n3 = 3 * (size_t)c->npix;
+  hipError_t e;
+  if ((e = hipMalloc((void**)&c->mom_sumsq, sizeof(float) * n3)) != hipSuccess ||
+      (e = hipMalloc((void**)&c->mom_partial, sizeof(float) * n3)) != hipSuccess ||
+      (e = hipMalloc((void**)&c->noise_stage, sizeof(float) * (size_t)c->npix)) != hipSuccess ||
+      (e = hipMalloc((void**)&c->noise_parts, sizeof(NoisePartial) * ((size_t)noise_blocks(c) + 1))) != hipSuccess ||
+      (e = hipMemsetAsync(c->mom_sumsq, 0, sizeof(float) * n3, c->stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(c->stream)) != hipSuccess) {
+    free_moments(c);
+    return hip_fail("kdpt_set_moments", e);
+  }
+  c->solo.image = c->mom_partial;
+  c->solo.zero_partial = true;  // the camera kernel clears it, as it clears a pipeline state's
+  c->mom_samples = 0;
+  c->moments = true;
+  return KDPT_OK;
+}
+
+int kdpt_read_moments(kdpt_ctx* c, float* sumsq, long long* samples) {
+  if (!c) return fail(KDPT_ERR_ARG, "kdpt_read_moments: null ctx");
+  if (!c->moments) return fail(KDPT_ERR_UNSUPPORTED, "kdpt_read_moments: moments are off (kdpt_set_moments)");
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = join_accum(c);
+  if (rc) return rc;
+  if (sumsq)
+    HIP_TRY(hipMemcpyAsync(sumsq, c->mom_sumsq, sizeof(float) * 3 * (size_t)c->npix, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (samples) *samples = c->mom_samples;
+  return KDPT_OK;
+}
+
+int kdpt_noise_map(kdpt_ctx* c, float floor, float* noise) {
+  int rc = check_noise_args(c, floor, "kdpt_noise_map");
+  if (rc) return rc;
+  if (!noise) return fail(KDPT_ERR_ARG, "kdpt_noise_map: null noise");
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = join_accum(c))) return rc;
+  const bool dev = on_context_device(c, noise);
+  float* const d = dev ? noise : c->noise_stage;
+  hipLaunchKernelGGL(k_noise_map, dim3((c->npix + 255) / 256), dim3(256), 0, c->stream, c->image, c->mom_sumsq,
+                     c->npix, c->mom_samples, floor, d);
+  HIP_TRY(hipGetLastError());
+  if (!dev) HIP_TRY(hipMemcpyAsync(noise, d, sizeof(float) * (size_t)c->npix, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return KDPT_OK;
+}
+
+int kdpt_noise_estimate(kdpt_ctx* c, float floor, float threshold, kdpt_noise* out) {
+  int rc = check_noise_args(c, floor, "kdpt_noise_estimate");
+  if (rc) return rc;
+  if (std::isnan(threshold)) return fail(KDPT_ERR_ARG, "kdpt_noise_estimate: threshold is NaN");
+  if (!out) return fail(KDPT_ERR_ARG, "kdpt_noise_estimate: null out");
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = join_accum(c))) return rc;
+  const int nb = noise_blocks(c);
+  hipLaunchKernelGGL(k_noise_partials, dim3(nb), dim3(NOISE_BLOCK), 0, c->stream, c->image, c->mom_sumsq, c->npix,
+                     c->mom_samples, floor, threshold, c->noise_parts);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_noise_final, dim3(1), dim3(NOISE_BLOCK), 0, c->stream, c->noise_parts, nb, c->noise_parts + nb);
+  HIP_TRY(hipGetLastError());
+  NoisePartial r{};
+  HIP_TRY(hipMemcpyAsync(&r, c->noise_parts + nb, sizeof r, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const long long finite = (long long)c->npix - r.nonfinite;
+  memset(out, 0, sizeof *out);
+  out->samples = c->mom_samples;
+  out->pixels = c->npix;
+  out->above = r.above;
+  out->nonfinite = r.nonfinite;
+  out->mean = finite > 0 ? r.sum / (double)finite : 0.0;
+  out->max = r.max;
   return KDPT_OK;
 }

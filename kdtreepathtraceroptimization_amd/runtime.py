@@ -126,6 +126,12 @@ class TraceRaysStats(NamedTuple):  # kdpt_trace_rays_stats: of the last kdpt_tra
     traced: int       # ... of which were handed to the KD traversal kernel
     device_ms: float  # the call's device time
 
+class Noise(C.Structure):  # kdpt_noise: kdpt_noise_estimate's result
+    _fields_ = [("samples", C.c_longlong), ("pixels", C.c_longlong), ("above", C.c_longlong),
+                ("nonfinite", C.c_longlong), ("mean", C.c_double), ("max", C.c_float), ("pad_", C.c_float)]
+
+
+assert C.sizeof(Noise) == 48
 assert C.sizeof(Geom) == 236 and C.sizeof(Material) == 56 and C.sizeof(Camera) == 84
 assert C.sizeof(NodeBare) == 64 and C.sizeof(TriBare) == 76 and C.sizeof(PathSegment) == 56
 
@@ -140,6 +146,7 @@ EXPORTS = [
     "kdpt_cull_margin", "kdpt_comm_unique_id", "kdpt_comm_init", "kdpt_render_frames", "kdpt_render_sharded",
     "kdpt_comm_library", "kdpt_cull_masks", "kdpt_cast_rays", "kdpt_cast_stats",
     "kdpt_set_camera", "kdpt_camera_rays", "kdpt_trace_rays", "kdpt_trace_rays_stats", "kdpt_shade_staged",
+    "kdpt_set_moments", "kdpt_read_moments", "kdpt_noise_map", "kdpt_noise_estimate", "kdpt_trace_rays_moments",
 ]
 
 REDUCE_RCCL, REDUCE_COPY = 0, 1  # kdpt_render_sharded's reduce (KDPT_REDUCE_*)
@@ -244,6 +251,13 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.kdpt_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p]
         lib.kdpt_trace_rays_stats.argtypes = [C.c_void_p, P(C.c_longlong), P(C.c_longlong), P(C.c_double)]
+    if hasattr(lib, "kdpt_set_moments"):  # absent from older builds used in A/B runs
+        lib.kdpt_set_moments.argtypes = [C.c_void_p, C.c_int]
+        lib.kdpt_read_moments.argtypes = [C.c_void_p, P(C.c_float), P(C.c_longlong)]
+        lib.kdpt_noise_map.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
+        lib.kdpt_noise_estimate.argtypes = [C.c_void_p, C.c_float, C.c_float, P(Noise)]
+        lib.kdpt_trace_rays_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int,
+                                                C.c_int, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -551,19 +565,67 @@ class PathTracer:
                                          C.c_void_p(int(directions_ptr))), "kdpt_camera_rays")
 
     def trace_rays(self, origins, directions, first_iter: int = 1, count: int = 1,
-                   normalize: bool = True) -> np.ndarray:
+                   normalize: bool = True, moments: bool = False):
         """kdpt_trace_rays on host arrays: the radiance the path tracer gathers for each of n <= W*H rays
         (origins, directions: n x 3 float32), summed over iterations first_iter .. first_iter + count - 1, as an
         (n, 3) float32 array.  Ray i is traced as pixel i of an n-pixel image whose camera produced these rays.
-        normalize as in cast_rays; a rejected ray's radiance is NaN in all three channels."""
+        normalize as in cast_rays; a rejected ray's radiance is NaN in all three channels.
+        moments=True (kdpt_trace_rays_moments) returns (radiance, sumsq): sumsq is the sum over the iterations of
+        the squared per-iteration contributions, same shape, for per-ray error bars."""
         o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
         if len(o) != len(d):
             raise ValueError(f"{len(o)} origins but {len(d)} directions")
         out = np.empty((len(o), 3), dtype=np.float32)
+        if moments:
+            sq = np.empty((len(o), 3), dtype=np.float32)
+            self.trace_rays_moments_ptr(o.ctypes.data, d.ctypes.data, len(o), out.ctypes.data, sq.ctypes.data,
+                                        first_iter=first_iter, count=count, normalize=normalize)
+            return out, sq
         self.trace_rays_ptr(o.ctypes.data, d.ctypes.data, len(o), out.ctypes.data, first_iter=first_iter,
                             count=count, normalize=normalize)
         return out
+
+    def trace_rays_moments_ptr(self, origins_ptr: int, directions_ptr: int, n: int, radiance_ptr: int,
+                               sumsq_ptr: int, first_iter: int = 1, count: int = 1, normalize: bool = True):
+        """kdpt_trace_rays_moments on raw pointers, each host memory or memory of the context's device: 3 n floats
+        each.  Synchronous."""
+        _check(self.lib.kdpt_trace_rays_moments(self._ctx, C.c_void_p(int(origins_ptr)),
+                                                C.c_void_p(int(directions_ptr)), int(n), int(first_iter), int(count),
+                                                CAST_NORMALIZE if normalize else 0, C.c_void_p(int(radiance_ptr)),
+                                                C.c_void_p(int(sumsq_ptr))), "kdpt_trace_rays_moments")
+
+    def set_moments(self, on: bool = True):
+        """kdpt_set_moments: keep (or drop) the per-pixel sum of squares beside the image.  Turning it on is
+        accepted only on a context nothing has been accumulated into since create / reset()."""
+        _check(self.lib.kdpt_set_moments(self._ctx, 1 if on else 0), "kdpt_set_moments")
+
+    def moments(self):
+        """kdpt_read_moments: (sumsq, samples) -- the (H*W, 3) float32 sum over the accumulated iterations of the
+        squared per-iteration pixel values, and the number of those iterations."""
+        sq = np.empty((self.height * self.width, 3), dtype=np.float32)
+        n = C.c_longlong()
+        _check(self.lib.kdpt_read_moments(self._ctx, _fptr(sq), C.byref(n)), "kdpt_read_moments")
+        return sq, int(n.value)
+
+    def noise_map(self, floor: float = 1e-2, out_ptr: Optional[int] = None):
+        """kdpt_noise_map: the per-pixel relative standard error of the mean, (H, W) float32 (formula in
+        include/kdpt.h).  out_ptr: write W*H floats to that raw pointer (host or the context's device) instead and
+        return None."""
+        if out_ptr is not None:
+            _check(self.lib.kdpt_noise_map(self._ctx, float(floor), C.c_void_p(int(out_ptr))), "kdpt_noise_map")
+            return None
+        out = np.empty((self.height, self.width), dtype=np.float32)
+        _check(self.lib.kdpt_noise_map(self._ctx, float(floor), C.c_void_p(out.ctypes.data)), "kdpt_noise_map")
+        return out
+
+    def noise_estimate(self, floor: float = 1e-2, threshold: float = 0.0) -> Noise:
+        """kdpt_noise_estimate: the noise map reduced on the device (samples, pixels, above, nonfinite, mean,
+        max); deterministic, for stopping rules."""
+        r = Noise()
+        _check(self.lib.kdpt_noise_estimate(self._ctx, float(floor), float(threshold), C.byref(r)),
+               "kdpt_noise_estimate")
+        return r
 
     def trace_rays_ptr(self, origins_ptr: int, directions_ptr: int, n: int, radiance_ptr: int, first_iter: int = 1,
                        count: int = 1, normalize: bool = True):

@@ -1,0 +1,165 @@
+"""Second moments (kdpt_set_moments, kdpt_read_moments, kdpt_noise_map, kdpt_noise_estimate,
+kdpt_trace_rays_moments): what can be checked without a device -- every entry point's null-context refusal with a
+message of its own, the layout of kdpt_noise against the header, the Python mirror's argtypes, and the new flags of
+the two command lines (cli.py --dry-run unchanged)."""
+import ctypes as C
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from kdtreepathtraceroptimization_amd import cast_cli, cli
+from kdtreepathtraceroptimization_amd.meshes import write_obj
+from scene_text import write_scene_text
+
+KDPT_ERR_ARG = -1
+ENTRY_POINTS = ["kdpt_set_moments", "kdpt_read_moments", "kdpt_noise_map", "kdpt_noise_estimate",
+                "kdpt_trace_rays_moments"]
+
+
+def _call_with_null_ctx(kdpt, lib, name):
+    buf = (C.c_float * 6)()
+    if name == "kdpt_set_moments":
+        return lib.kdpt_set_moments(None, 1)
+    if name == "kdpt_read_moments":
+        return lib.kdpt_read_moments(None, buf, C.byref(C.c_longlong()))
+    if name == "kdpt_noise_map":
+        return lib.kdpt_noise_map(None, 1e-2, C.cast(buf, C.c_void_p))
+    if name == "kdpt_noise_estimate":
+        return lib.kdpt_noise_estimate(None, 1e-2, 0.5, C.byref(kdpt.Noise()))
+    p = C.cast(buf, C.c_void_p)
+    return lib.kdpt_trace_rays_moments(None, p, p, 1, 1, 1, 0, p, p)
+
+
+@pytest.mark.parametrize("name", ENTRY_POINTS)
+def test_null_context_is_an_argument_error_with_its_own_message(kdpt, name):
+    lib = kdpt.load_library()
+    assert lib.kdpt_create(None, None, 0, C.byref(C.c_void_p())) != 0  # another call's message is current
+    before = lib.kdpt_last_error()
+    assert _call_with_null_ctx(kdpt, lib, name) == KDPT_ERR_ARG
+    msg = lib.kdpt_last_error()
+    assert msg != before and msg.startswith(name.encode() + b":") and b"null ctx" in msg, msg
+
+
+def test_trace_rays_moments_reports_argument_errors_before_the_context(kdpt):
+    """kdpt_trace_rays' order: n, count, first_iter and flags are judged before the context is looked at."""
+    lib = kdpt.load_library()
+    p = C.cast((C.c_float * 6)(), C.c_void_p)
+    for args, word in (((-1, 1, 1, 0), b"n must be"), ((1, 1, -1, 0), b"count must be"),
+                       ((1, 0, 1, 0), b"first_iter must be"), ((1, 1, 1, 2), b"flags")):
+        n, first, count, flags = args
+        assert lib.kdpt_trace_rays_moments(None, p, p, n, first, count, flags, p, p) == KDPT_ERR_ARG
+        msg = lib.kdpt_last_error()
+        assert msg.startswith(b"kdpt_trace_rays_moments:") and word in msg, msg
+
+
+def _header_struct(name):
+    src = open(os.path.join(ROOT, "include", "kdpt.h")).read()
+    body = re.search(r"typedef struct " + name + r" \{(.*?)\} " + name + r";", src, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = []
+    for decl in body.split(";"):
+        decl = decl.strip()
+        if decl:
+            m = re.match(r"((?:long long|double|float|int))\s+(.*)", decl)
+            ctype, names = m.group(1), [s.strip() for s in m.group(2).split(",")]
+            fields += [(n, ctype) for n in names]
+    return fields
+
+
+def test_kdpt_noise_layout_matches_the_header(kdpt):
+    sizes = {"long long": (C.c_longlong, 8), "double": (C.c_double, 8), "float": (C.c_float, 4), "int": (C.c_int, 4)}
+    declared = _header_struct("kdpt_noise")
+    assert [n for n, _ in declared] == ["samples", "pixels", "above", "nonfinite", "mean", "max", "pad_"]
+    assert [n for n, _ in kdpt.Noise._fields_] == [n for n, _ in declared]
+    off = 0
+    for (name, ctype), (_, mirror) in zip(declared, kdpt.Noise._fields_):
+        want, size = sizes[ctype]
+        assert mirror is want, name
+        off = (off + size - 1) // size * size  # natural alignment
+        assert getattr(kdpt.Noise, name).offset == off, name
+        off += size
+    assert C.sizeof(kdpt.Noise) == 48 == off
+    assert kdpt.Noise.mean.offset == 32 and kdpt.Noise.max.offset == 40 and kdpt.Noise.pad_.offset == 44
+    # kdpt_stats keeps its layout
+    assert kdpt.Stats.iterations.offset == 8 + 32 * 8 + 4 and kdpt.Stats.total_segments.offset == 280
+
+
+def test_python_mirror_declares_the_argtypes(kdpt):
+    lib = kdpt.load_library()
+    P = C.POINTER
+    assert lib.kdpt_set_moments.argtypes == [C.c_void_p, C.c_int]
+    assert lib.kdpt_read_moments.argtypes == [C.c_void_p, P(C.c_float), P(C.c_longlong)]
+    assert lib.kdpt_noise_map.argtypes == [C.c_void_p, C.c_float, C.c_void_p]
+    assert lib.kdpt_noise_estimate.argtypes == [C.c_void_p, C.c_float, C.c_float, P(kdpt.Noise)]
+    assert lib.kdpt_trace_rays_moments.argtypes == [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int,
+                                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    for name in ENTRY_POINTS:
+        assert name in kdpt.EXPORTS
+    for method in ("set_moments", "moments", "noise_map", "noise_estimate", "trace_rays_moments_ptr"):
+        assert callable(getattr(kdpt.PathTracer, method)), method
+
+
+def test_section_header_holds_device_code_only():
+    """csrc/kernels_moments.h is a section of kdpt_runtime.hip: kernels and argument structs, no HIP host call
+    (tests/test_stream_discipline.py reads kdpt_runtime.hip alone)."""
+    csrc = os.path.join(ROOT, "kdtreepathtraceroptimization_amd", "csrc")
+    src = open(os.path.join(csrc, "kernels_moments.h")).read()
+    src = re.sub(r"//[^\n]*", "", src)
+    assert not re.search(r"\bhip[A-Z]\w*\s*\(", src)
+    for kernel in ("k_accumulate_moments", "k_noise_map", "k_noise_partials", "k_noise_final"):
+        assert re.search(r"__global__[^;{]*\b" + kernel + r"\b", src), kernel
+    assert "atomic" not in src  # the reduction is ordered: no atomics, floating-point or other
+    runtime = open(os.path.join(csrc, "kdpt_runtime.hip")).read()
+    sections = re.findall(r'#include "(kernels_\w+\.h)"', runtime)
+    assert sections[-1] == "kernels_moments.h"
+
+
+def test_cli_parses_the_adaptive_flags():
+    a = cli.parse_args(["s.txt", "--target-noise", "0.05", "--noise-floor", "0.02", "--min-spp", "8", "--noise-map",
+                        "--iterations", "64"])
+    assert (a.target_noise, a.noise_floor, a.min_spp, a.noise_map, a.iterations) == (0.05, 0.02, 8, True, 64)
+    d = cli.parse_args(["s.txt"])
+    assert (d.target_noise, d.noise_floor, d.min_spp, d.noise_map) == (None, 1e-2, 2, False)
+    for bad in (["--noise-map"], ["--target-noise", "-1"], ["--target-noise", "nan"],
+                ["--target-noise", "0.1", "--noise-floor", "0"], ["--target-noise", "0.1", "--min-spp", "1"],
+                ["--target-noise", "0.1", "--testing"]):
+        with pytest.raises(SystemExit):
+            cli.parse_args(["s.txt", *bad])
+
+
+def test_cast_cli_parses_stderr():
+    a = cast_cli.parse_args(["s.txt", "--rays", "r.npy", "--out", "o.npy", "--radiance", "4", "--stderr"])
+    assert a.stderr and a.radiance == 4
+    assert not cast_cli.parse_args(["s.txt", "--rays", "r.npy", "--out", "o.npy"]).stderr
+
+
+def test_standard_error_formula():
+    """cast_cli.standard_error: float64, m = S / n, v = max((Q - S m) / (n - 1), 0), sqrt(v / n); against the
+    textbook estimate on samples whose float32 sums are exact."""
+    x = np.array([[1.0, 0.5, 0.0], [3.0, 0.5, 0.0], [2.0, 0.5, 0.0], [6.0, 0.5, 0.0]], np.float32)
+    s, q = x.sum(0, dtype=np.float32)[None], (x * x).sum(0, dtype=np.float32)[None]
+    se = cast_cli.standard_error(s, q, 4)
+    assert se.dtype == np.float64 and se.shape == (1, 3)
+    want = x.astype(np.float64).std(0, ddof=1) / 2.0
+    assert np.allclose(se[0], want, rtol=1e-15, atol=0) and se[0, 1] == 0 and se[0, 2] == 0
+    nan = cast_cli.standard_error(np.full((1, 3), np.nan, np.float32), np.full((1, 3), np.nan, np.float32), 4)
+    assert np.isnan(nan).all()
+
+
+def test_dry_run_is_unchanged(tmp_path, capsys):
+    """--dry-run prints the same record with and without the new flags, with the keys it always had."""
+    scene = write_scene_text("cornell", str(tmp_path / "cornell.txt"), iterations=7)
+    obj = str(tmp_path / "ico.obj")
+    write_obj(obj, 2)
+    assert cli.main([scene, obj, "--res", "32", "24", "--dry-run"]) == 0
+    plain = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert cli.main([scene, obj, "--res", "32", "24", "--dry-run", "--target-noise", "0.1", "--noise-map"]) == 0
+    adaptive = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert plain == adaptive
+    assert sorted(plain) == sorted(["scene", "mesh", "resolution", "iterations", "geoms", "materials", "kd_nodes",
+                                    "kd_tri_refs", "kd_build", "kd_build_ms"])
+    assert plain["resolution"] == [32, 24] and plain["iterations"] == 7
