@@ -28,6 +28,12 @@ namespace kdpt {
 
 constexpr int TILE = 256;  // paths per workgroup (4 waves of 64): the only block_size
 constexpr int MAX_KEYS = 64;  // materials (the keys of iteration 2's sort)
+// Iterations per batch (kdpt_trace_iterations): they share one intersect launch and one ray queue of
+// MAXB x npix int entries (kernels_gen.h TraceArgs).
+#ifndef KDPT_MAXB
+#define KDPT_MAXB 16  // tools/build_variant.sh experiments only
+#endif
+constexpr int MAXB = KDPT_MAXB;
 
 // One OBJ shape of the brute-force route (BruteArgs::shapes).
 struct BruteShape {
@@ -419,6 +425,9 @@ inline int prepare_scene(const kdpt_scene* sc, const kdpt_options* opt, double c
   if (o.block_size && o.block_size != TILE) return fail(KDPT_ERR_UNSUPPORTED, "block_size must be 0 or 256");
   const int W = sc->camera.resolution[0], H = sc->camera.resolution[1];
   if (W <= 0 || H <= 0 || (long long)W * H >= (1ll << 30)) return fail(KDPT_ERR_ARG, "bad resolution");
+  if ((long long)MAXB * W * H >= (1ll << 31))  // a batch's ray-queue entries are ints
+    return fail(KDPT_ERR_UNSUPPORTED,
+                "resolution too large for a batch's ray queue: (iterations per batch) x width x height >= 2^31");
   if (sc->num_materials > MAX_KEYS) return fail(KDPT_ERR_UNSUPPORTED, "more than 64 materials");
   p.brute = !o.enable_kd && sc->has_obj;
   p.kd = sc->has_obj && sc->num_nodes > 0 && !p.brute;

@@ -9,8 +9,8 @@ namespace {
 
 // ---------------------------------------------------------------------------
 // Ray queries (kdpt_cast_rays): caller-supplied rays through the intersect stage of the path tracer, one
-// chunk at a time -- k_cast_prep (validation + the stage's first part, geoms_core), k_trace (unchanged, a batch
-// of one "iteration" at depth 0 over the query's own queue) and k_cast_resolve (the hit code turned into a
+// chunk at a time -- k_cast_prep (validation + the stage's first part, geoms_core), k_trace (unchanged, over the
+// query's own queue, a group of one at depth 0) and k_cast_resolve (the hit code turned into a
 // kdpt_ray_hit with the calls shade_one makes).  No PathSegment, iteration number or image is involved.
 // ---------------------------------------------------------------------------
 struct CastArgs {
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_cast_prep(CastArgs A) {
     live = cast_load(A, i, o, d);
     if (!live) A.hits[i] = make_int2(-1, CAST_REJECTED);
   }
-  geoms_core<GEN_BLOCK>(A.S, live, i, o, d, A.cray, A.hits, A.cand, A.cnt + 1, nullptr);
+  geoms_core<GEN_BLOCK>(A.S, live, i, o, d, A.cray, A.hits, A.cand, A.cnt + 1, 0, nullptr);
 }
 
 // (code, objMaterialIdx) + the ray -> kdpt_ray_hit: t, point and normal recomputed exactly as shade_one

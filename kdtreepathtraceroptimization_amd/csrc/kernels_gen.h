@@ -159,22 +159,21 @@ template <int MODE>
 constexpr int trace_block() { return MODE == 2 ? TRACE_BLOCK : (MODE >= 3 ? TRACE_BLOCK16 : 256); }
 
 // Up to MAXB iterations (each its own path buffers) at the same bounce share one intersect launch:
-// more rays per launch keep the lanes of the persistent waves busy.
-#ifndef KDPT_MAXB
-#define KDPT_MAXB 16  // tools/build_variant.sh experiments only
-#endif
-constexpr int MAXB = KDPT_MAXB;
-struct TraceIter {
-  const int* cand;      // k_geoms' list of the paths whose ray meets the KD root box (queue slot -> path)
-  const int* ccount;    // ... and its length per bounce
-  const float4* cray;   // ... and their rays in queue order: [2 slot] = {origin, t_min}, [2 slot + 1] = {dir, geom}
-  int2* hits;
-};
-
+// more rays per launch keep the lanes of the persistent waves busy.  (MAXB: kdpt_scene_prep.h, whose shape
+// check keeps MAXB x npix below 2^31.)
+//
+// The batch's candidate queue is one list for all its iterations: every producer (geoms_core, k_shade_fused,
+// k_scatter) appends to it through the one counter of the bounce, an entry being qbase + path with qbase =
+// (the iteration's place in its group) x npix -- which is also the path's place in the group's hit records
+// (hits0; iteration b's own view of them starts at hits0 + b npix).  k_trace therefore never learns which
+// iteration a ray belongs to.  The queue's order only decides which lane traces which ray.
 struct TraceArgs {
   DevScene S;
-  TraceIter it[MAXB];
-  int nb;
+  const int* cand;      // the producers' list of the rays that meet the KD root box (queue slot -> hits0 entry)
+  const float4* cray;   // ... and their rays in queue order: [2 slot] = {origin, t_min}, [2 slot + 1] = {dir, geom}
+  const int* count;     // ... and its length at this bounce
+  int2* hits0;          // the group's hit records
+  unsigned long long* trace_rays;  // rays handed to the intersect kernel, summed (null: not kept)
   int prof_steps;  // count mode, "profile_batches" = 2: per-ray node-step histogram
   int* work;  // chunk counters, zeroed by k_gen_rays (of iteration 0 of the batch)
   int depth;
@@ -236,12 +235,12 @@ constexpr int GEN_BLOCK = KDPT_GEN_BLOCK;
 // One workgroup's part: the analytic geoms + root-box test of its paths (live: the lane holds a path still
 // bouncing), the final hit record of the rays that end there, and the others appended to the candidate list
 // through *ccnt (one atomic per workgroup; a single counter hit once per wave by ~10k waves serialises for
-// ~100 us at 800x800).  Every thread of the workgroup must call it.
+// ~100 us at 800x800) as entry qbase + i (see TraceArgs).  Every thread of the workgroup must call it.
 template <int TB = GEN_BLOCK>
 __device__ __attribute__((always_inline)) inline void geoms_core(const DevScene& S, bool live, int i, f3 o, f3 d,
                                                                  float4* __restrict__ cray, int2* __restrict__ hits,
                                                                  int* __restrict__ cand, int* __restrict__ ccnt,
-                                                                 Counters* count_aabb) {
+                                                                 int qbase, Counters* count_aabb) {
   const bool kd = S.has_obj && S.num_nodes > 0;
   bool tested = false, walk = false;  // traversed at all / goes on to the intersect kernel
   float t_min = 0.0f;
@@ -276,17 +275,17 @@ __device__ __attribute__((always_inline)) inline void geoms_core(const DevScene&
   __syncthreads();
   if (walk) {
     const int slot = s_base + s_wcount[wv] + (int)lane_prefix(wm);
-    cand[slot] = i;
-    cray[2 * slot] = make_float4(o.x, o.y, o.z, t_min);
-    cray[2 * slot + 1] = make_float4(d.x, d.y, d.z, ibits(hit));
+    cand[slot] = qbase + i;
+    cray[2 * (size_t)slot] = make_float4(o.x, o.y, o.z, t_min);
+    cray[2 * (size_t)slot + 1] = make_float4(d.x, d.y, d.z, ibits(hit));
   }
 }
 
 __device__ __attribute__((always_inline)) inline void geoms_body(const DevScene& S, PathBuf paths, const int* counts,
                                                                  int depth, float4* __restrict__ cray,
                                                                  int2* __restrict__ hits, int* __restrict__ cand,
-                                                                 int* __restrict__ ccount, Counters* count_aabb,
-                                                                 unsigned long long* gspan) {
+                                                                 int* __restrict__ ccount, int qbase,
+                                                                 Counters* count_aabb, unsigned long long* gspan) {
   const int n = counts[depth];
   if ((int)(blockIdx.x * blockDim.x) >= n) return;  // uniform per block
   if (threadIdx.x == 0) atomicMin(&gspan[2 * depth], (unsigned long long)__builtin_amdgcn_s_memrealtime());
@@ -299,7 +298,7 @@ __device__ __attribute__((always_inline)) inline void geoms_body(const DevScene&
     o = mk3(q0.x, q0.y, q0.z);
     d = mk3(q1.x, q1.y, q1.z);
   }
-  geoms_core<GEN_BLOCK>(S, live, i, o, d, cray, hits, cand, ccount + depth, count_aabb);
+  geoms_core<GEN_BLOCK>(S, live, i, o, d, cray, hits, cand, ccount + depth, qbase, count_aabb);
   if (threadIdx.x == 0) atomicMax(&gspan[2 * depth + 1], (unsigned long long)__builtin_amdgcn_s_memrealtime());
 }
 
@@ -307,10 +306,11 @@ __device__ __attribute__((always_inline)) inline void geoms_body(const DevScene&
 struct GeomsIter {
   PathBuf paths;
   const int* counts;
-  float4* cray;
-  int2* hits;
+  float4* cray;   // the group's queue
+  int2* hits;     // the iteration's own hit records
   int* cand;
-  int* ccount;
+  int* ccount;    // the group's candidate counters
+  int qbase;
 };
 struct GeomsBatch {
   DevScene S;
@@ -321,21 +321,22 @@ struct GeomsBatch {
 };
 __global__ __launch_bounds__(GEN_BLOCK) void k_geoms_b(GeomsBatch B) {
   const GeomsIter& g = B.it[blockIdx.y];
-  geoms_body(B.S, g.paths, g.counts, B.depth, g.cray, g.hits, g.cand, g.ccount, B.count_aabb, B.gspan);
+  geoms_body(B.S, g.paths, g.counts, B.depth, g.cray, g.hits, g.cand, g.ccount, g.qbase, B.count_aabb, B.gspan);
 }
 
 // A batch's camera rays and their bounce-0 intersect-stage first part in one launch (blockIdx.y = iteration):
 // each lane generates its pixel's ray (written out for the shading) and tests it against the analytic geoms
 // and the KD root box straight from registers.  The bounce-0 candidate counter cannot be the one the
 // generation zeroes (other workgroups of this launch already add to it), so bounce 0 counts into
-// ccount0[parity] of the context, and the launch zeroes ccount0[!parity] for the context's next use (always
+// ccount0[parity] of the group, and the launch zeroes ccount0[!parity] for the group's next use (always
 // on the same stream, so nothing still reads it).
 struct GenGeomsIter {
-  int* ccount0;       // this use's bounce-0 candidate counter
+  int* ccount0;       // this use's bounce-0 candidate counter (the group's: the same for every iteration)
   int* ccount0_next;  // the next use's (zeroed here)
-  float4* cray;
-  int2* hits;
+  float4* cray;       // the group's queue
+  int2* hits;         // the iteration's own hit records
   int* cand;
+  int qbase;
 };
 struct GenGeomsBatch {
   GenBatch g;
@@ -352,7 +353,7 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_gen_geoms_b(GenGeomsBatch B) {
                                    g.zero_image, o, d);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i == 0) *q.ccount0_next = 0;
-  geoms_core<GEN_BLOCK>(B.S, valid && B.g.traceDepth > 0, i, o, d, q.cray, q.hits, q.cand, q.ccount0,
+  geoms_core<GEN_BLOCK>(B.S, valid && B.g.traceDepth > 0, i, o, d, q.cray, q.hits, q.cand, q.ccount0, q.qbase,
                         B.count_aabb);
 }
 

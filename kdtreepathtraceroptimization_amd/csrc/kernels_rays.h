@@ -72,7 +72,7 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_user_geoms_b(UserGeomsBatch B) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i == 0) *B.q.ccount0_next = 0;
   geoms_core<GEN_BLOCK>(B.S, ok && B.u.traceDepth > 0, i, o, d, B.q.cray, B.q.hits, B.q.cand, B.q.ccount0,
-                        B.count_aabb);
+                        B.q.qbase, B.count_aabb);
 }
 
 }  // namespace

@@ -31,15 +31,12 @@ struct ShadeArgs {
   const unsigned long long* trace_t;   // this bounce's intersect launch record (see TraceArgs)
   const unsigned long long* gspan;     // ... and the k_geoms launches' record
   unsigned long long* trace_total;     // [2]: summed launch ticks, launches (the batch's first iteration only)
-  unsigned long long* trace_rays;      // rays handed to the intersect kernel, summed (every iteration)
-  const int* ccount;                   // ... per bounce (this iteration's candidate counts)
   // next bounce's intersect-stage first part (prep_ray) for every surviving path, fused here instead of a
   // k_geoms pass: {t_min bits, (geom + 1) | walks << 16} at the path's current slot (k_scatter moves it)
   int image_zeroed;  // `image` is this iteration's partial image, zeroed by its camera-ray launch: a pixel's
                      // partialGather then reads +0 (each pixel's path ends once), so its load is skipped
   int prep_on;
   int2* prep;
-  int* tile_ccounts;   // [ntiles] walking survivors per tile
   Counters* count_aabb;  // count mode: root tests of the rays that end there
 };
 
@@ -161,7 +158,6 @@ __device__ inline void shade_stats(const ShadeArgs& A, int n) {
     atomicAdd(&A.trace_total[0], span);
     atomicAdd(&A.trace_total[1], 1ull);
   }
-  if (A.trace_rays) atomicAdd(A.trace_rays, (unsigned long long)A.ccount[A.depth]);
 }
 
 __device__ inline void count_prep(const ShadeArgs& A, bool tested, bool walk) {
@@ -223,11 +219,7 @@ __global__ __launch_bounds__(TILE) void k_shade(ShadeArgs A) {
     const int c = __syncthreads_count(alive);
     if (threadIdx.x == 0) A.tile_counts[tile] = c;
   }
-  if (COMPACT && A.prep_on) {
-    const int cw = __syncthreads_count(walk);
-    if (threadIdx.x == 0) A.tile_ccounts[tile] = cw;
-    if (A.count_aabb) count_prep(A, tested, walk);
-  }
+  if (COMPACT && A.prep_on && A.count_aabb) count_prep(A, tested, walk);
 }
 
 // Single-pass shading + stable stream compaction (the usual case: compaction on, no material sort).
@@ -242,10 +234,11 @@ struct FuseArgs {
   int* tickets;               // [cap] tile tickets per bounce
   unsigned long long* lb;     // [cap][ntiles] look-back records
   int* counts;                // [cap + 2] live paths per bounce
-  int* ccount;                // [cap] candidates per bounce
-  float4* cray;
-  int2* hits;
+  int* ccount;                // [cap] the group's candidates per bounce
+  float4* cray;               // the group's queue (TraceArgs), an entry being qbase + path
+  int2* hits;                 // the iteration's own hit records
   int* cand;
+  int qbase;
 };
 
 __device__ inline unsigned long long lb_load(const unsigned long long* p) {
@@ -412,9 +405,9 @@ __device__ __attribute__((always_inline)) inline void shade_tile(const ShadeArgs
     if (A.prep_on) {
       if (o.walk) {
         const int slot = (int)(bW + lane_prefix(mw));
-        F.cand[slot] = d;
-        F.cray[2 * slot] = make_float4(o.q0.x, o.q0.y, o.q0.z, o.tm);
-        F.cray[2 * slot + 1] = make_float4(o.q1.x, o.q1.y, o.q1.z, ibits(o.gh));
+        F.cand[slot] = F.qbase + d;
+        F.cray[2 * (size_t)slot] = make_float4(o.q0.x, o.q0.y, o.q0.z, o.tm);
+        F.cray[2 * (size_t)slot + 1] = make_float4(o.q1.x, o.q1.y, o.q1.z, ibits(o.gh));
       } else {
         F.hits[d] = make_int2(o.gh, -1);  // final: the analytic geoms' hit (code -1: none)
       }
@@ -473,9 +466,8 @@ __global__ __launch_bounds__(SHADE_TB) __attribute__((amdgpu_waves_per_eu(KDPT_S
   shade_fused_body<HYBRID, STAGE>(B.a[blockIdx.y], B.f[blockIdx.y]);
 }
 
-// Exclusive scan of the tile counts (one workgroup; <= MAX_KEYS * ntiles entries).
-// One workgroup per scan job: job 0 = the survivors (or, when sorting, the per-material histogram),
-// job 1 = the walking survivors of the intersect-stage hand-off (launched only when it runs).
+// Exclusive scan of the tile counts (one workgroup; <= MAX_KEYS * ntiles entries): the survivors, or, when
+// sorting, the per-material histogram.
 struct ScanJob {
   const int* tile_counts;
   int* tile_off;
@@ -485,9 +477,7 @@ struct ScanJob {
 // 256 threads: every kernel a batch launches fits beside a resident intersect workgroup (4 waves x 96 VGPRs per
 // SIMD, 150 KB of LDS per CU), which a 1024-thread workgroup never does
 constexpr int SCAN_TB = 256;
-__global__ __launch_bounds__(SCAN_TB) void k_scan(ScanJob j0, ScanJob j1, const int* counts, int depth,
-                                                  int ntiles_alloc) {
-  const ScanJob& J = blockIdx.x == 0 ? j0 : j1;
+__global__ __launch_bounds__(SCAN_TB) void k_scan(ScanJob J, const int* counts, int depth, int ntiles_alloc) {
   const int* __restrict__ tile_counts = J.tile_counts;
   int* __restrict__ tile_off = J.tile_off;
   const int nkeys = J.nkeys;
@@ -538,15 +528,16 @@ __global__ __launch_bounds__(SCAN_TB) void k_scan(ScanJob j0, ScanJob j1, const 
 
 // Stable compaction (and, on iter 2, the stable sort by materialIdHit).
 // The next bounce's intersect-stage hand-off, moved with the survivors by k_scatter: walking rays get their
-// geoms record at the new slot and a candidate-list entry (stable: tile order, offsets from k_scan), the
-// others their final hit record.
+// geoms record and a candidate-list entry (qbase + the new slot) in the group's queue, one add of the bounce's
+// counter per tile, the others their final hit record.
 struct ScatterPrep {
   int on;
   const int2* prep;
-  float4* cray;
-  int2* hits;
+  float4* cray;   // the group's queue (TraceArgs)
+  int2* hits;     // the iteration's own hit records
   int* cand;
-  const int* tile_coff;
+  int* ccount;    // the next bounce's candidate counter (the group's)
+  int qbase;
 };
 
 template <bool SORT>
@@ -593,21 +584,27 @@ __global__ __launch_bounds__(TILE) void k_scatter(PathBuf src, PathBuf dst, cons
     dst.pm[dst_i] = pm;
   }
   if (P.on) {
-    __shared__ int s_walk[TILE / 64];
+    __shared__ int s_walk[TILE / 64], s_cbase;
     const int2 pr = alive ? P.prep[i] : make_int2(0, 0);
     const bool w = alive && (pr.y & 0x10000);
     const int geom = (pr.y & 0xffff) - 1;
     const unsigned long long m = __ballot(w);
     if (lane == 0) s_walk[wid] = __popcll(m);
     __syncthreads();
+    if (threadIdx.x == 0) {
+      int tot = 0;
+      for (int k = 0; k < TILE / 64; k++) tot += s_walk[k];
+      s_cbase = tot ? atomicAdd(P.ccount, tot) : 0;
+    }
+    __syncthreads();
     if (alive) {
       if (w) {
         int before = 0;
         for (int k = 0; k < wid; k++) before += s_walk[k];
-        const int slot = P.tile_coff[tile] + before + (int)lane_prefix(m);
-        P.cand[slot] = dst_i;
-        P.cray[2 * slot] = make_float4(q0.x, q0.y, q0.z, u2f((uint32_t)pr.x));
-        P.cray[2 * slot + 1] = make_float4(q1.x, q1.y, q1.z, ibits(geom));
+        const int slot = s_cbase + before + (int)lane_prefix(m);
+        P.cand[slot] = P.qbase + dst_i;
+        P.cray[2 * (size_t)slot] = make_float4(q0.x, q0.y, q0.z, u2f((uint32_t)pr.x));
+        P.cray[2 * (size_t)slot + 1] = make_float4(q1.x, q1.y, q1.z, ibits(geom));
       } else {
         P.hits[dst_i] = make_int2(geom, -1);  // final: the analytic geoms' hit (code -1: none)
       }

@@ -31,11 +31,7 @@ __global__ __launch_bounds__(trace_block<MODE>()) KDPT_TRACE_ATTR void k_trace(T
   __shared__ WaveLeafLDS s_leaf[TB / 64];
   __shared__ WaveProf s_prof[COUNT ? TB / 64 : 1];
   const DevScene& S = A.S;
-  int pre[MAXB + 1];  // the batch's paths, concatenated: iteration b owns queue slots [pre[b], pre[b+1])
-  pre[0] = 0;
-#pragma unroll
-  for (int b = 0; b < MAXB; b++) pre[b + 1] = pre[b] + (b < A.nb ? A.it[b].ccount[A.depth] : 0);
-  const int n = pre[MAXB];
+  const int n = *A.count;  // the batch's rays: one queue for all its iterations (TraceArgs)
   // tree copy: NodesPacked (2 x 16 bytes per node) or NodesDerived (16 bytes), then the cluster boxes
   constexpr int NODE_WORDS = MODE == TREE_LDS ? 2 : 1;
   if (tree_in_lds(MODE)) {
@@ -69,6 +65,7 @@ __global__ __launch_bounds__(trace_block<MODE>()) KDPT_TRACE_ATTR void k_trace(T
   if (threadIdx.x == 0) {
     s_waves_done = 0;
     atomicMin(&A.trace_t[2 * A.depth], (unsigned long long)__builtin_amdgcn_s_memrealtime());
+    if (blockIdx.x == 0 && A.trace_rays) atomicAdd(A.trace_rays, (unsigned long long)n);
 #ifdef KDPT_TAIL_PROF
     s_t0 = __builtin_amdgcn_s_memrealtime();
     s_tex = ~0ull;
@@ -82,8 +79,7 @@ __global__ __launch_bounds__(trace_block<MODE>()) KDPT_TRACE_ATTR void k_trace(T
   WaveRay R;  // every field defined: idle lanes take part in the wave-level code with a finished ray
   wave_ray_start(S, R, mk3(0.0f, 0.0f, 0.0f), mk3(0.0f, 0.0f, 1.0f), FLT_MAXV, -1, W);
   R.done = true;
-  int pidx = -1;  // the lane's path (-1: idle)
-  int pb = 0;     // ... and the batch iteration it belongs to
+  int pidx = -1;  // the lane's ray: its entry of hits0 (-1: idle)
   // Path slots: each wave first takes a static run of 64 consecutive slots, the runs dealt out wave-major
   // across the workgroups (run r goes to wave r / grid of workgroup r % grid): a bounce with few rays then
   // still fills every CU (the kernel is issue-bound: rays piled onto a few CUs would leave the others idle)
@@ -124,25 +120,11 @@ __global__ __launch_bounds__(trace_block<MODE>()) KDPT_TRACE_ATTR void k_trace(T
       if (exhausted && !tex_seen) tex_seen = __builtin_amdgcn_s_memrealtime();
 #endif
       if (pidx < 0 && k < n) {
-        int b = 0;
-#pragma unroll
-        for (int q = 1; q < MAXB; q++) b += k >= pre[q];
-        const int* cand = A.it[0].cand;
-        const float4* cray = A.it[0].cray;
-        int local = k;
-#pragma unroll
-        for (int q = 1; q < MAXB; q++)
-          if (b == q) {
-            cand = A.it[q].cand;
-            cray = A.it[q].cray;
-            local = k - pre[q];
-          }
-        // the slot's path index and its ray (written in queue order with the slot): three independent loads
-        // of consecutive slots, not a slot load followed by scattered path loads
-        const int i = cand[local];
-        const float4 q0 = cray[2 * local], q1 = cray[2 * local + 1];
+        // the slot's entry and its ray (written in queue order with the slot): three independent loads
+        // of consecutive slots from uniform bases, not a slot load followed by scattered path loads
+        const int i = A.cand[k];
+        const float4 q0 = A.cray[2 * (size_t)k], q1 = A.cray[2 * (size_t)k + 1];
         pidx = i;
-        pb = b;
         wave_ray_start(S, R, mk3(q0.x, q0.y, q0.z), mk3(q1.x, q1.y, q1.z), q0.w, fbits(q1.w), W);
       }
     }
@@ -194,11 +176,7 @@ __global__ __launch_bounds__(trace_block<MODE>()) KDPT_TRACE_ATTR void k_trace(T
       }
       const Hit& h = R.h;
       const int code = h.hit_geom_index == -1 ? -1 : (h.obj_intersect ? -(R.objTri + 2) : h.hit_geom_index);
-      int2* hits = A.it[0].hits;
-#pragma unroll
-      for (int q = 1; q < MAXB; q++)
-        if (pb == q) hits = A.it[q].hits;
-      hits[pidx] = make_int2(code, h.objMaterialIdx);
+      A.hits0[pidx] = make_int2(code, h.objMaterialIdx);
       pidx = -1;
     }
     if (exhausted && !__any(pidx >= 0)) break;

@@ -16,14 +16,14 @@ BENCH=(bench.py --full --no-cpu-baseline "$@")
 # the fixed step counts come last (argparse: the last one wins), so workload args pass through but the PMC
 # passes always count exactly the dispatches of the one timed step the summariser divides by
 PMC_BENCH=(bench.py --full --no-cpu-baseline "$@" --steps 1 --warmup 0 --spp-per-step 16)
-run() {  # name, then rocprofv3 args; a time-out or crash stops the script
+run() {  # name, then rocprofv3 args; any failure stops the script: nothing more starts on a GPU that may have faulted
   local name=$1
   shift
   timeout -s KILL 180 rocprofv3 "$@" > "$OUT/$name.log" 2>&1
   local rc=$?
   echo "[pmc] $name rc=$rc"
   tail -2 "$OUT/$name.log"
-  if [ $rc -ge 124 ]; then exit $rc; fi
+  if [ $rc -ne 0 ]; then exit $rc; fi
   return 0
 }
 timeout -s KILL 60 rocprofv3 -L > "$OUT/counters_avail.txt" 2>&1
