@@ -37,8 +37,12 @@
 #include "kd_build.h"
 #define KDPT_HIP_STAGE "device KD build: "  // what this file's HIP_TRY messages begin with
 #include "kdpt_error.h"
+#include "kdpt_owned.h"
 
 namespace {
+
+using kdpt::Arena;
+using kdpt::DeviceBuf;
 
 constexpr int BLK = 256;
 inline int blocks(long long n) { return (int)std::max(1ll, (n + BLK - 1) / BLK); }
@@ -313,31 +317,7 @@ __global__ void k_iota(int* a, int n) {
 // Helpers that wrap HIP calls return hipError_t and are called under HIP_TRY, whose message names the call;
 // the stages of the build return the library's int status.
 
-// Device memory owned by one build; freed on every exit path.
-struct Arena {
-  std::vector<void*> p;
-  ~Arena() {
-    for (void* q : p) (void)hipFree(q);
-  }
-  hipError_t alloc_bytes(void** out, size_t bytes) {
-    *out = nullptr;
-    hipError_t e = hipMalloc(out, std::max<size_t>(bytes, 1));
-    if (e == hipSuccess) p.push_back(*out);
-    return e;
-  }
-  template <typename T>
-  hipError_t alloc(T** out, size_t n) {
-    return alloc_bytes((void**)out, n * sizeof(T));
-  }
-  // frees one of the arena's buffers now (the caller has synchronised every use of it)
-  hipError_t release(void* q) {
-    auto it = std::find(p.begin(), p.end(), q);
-    if (it == p.end()) return hipErrorInvalidValue;
-    p.erase(it);
-    return hipFree(q);
-  }
-};
-
+// (An Arena, kdpt_owned.h, owns what lives as long as the build; the stores that grow own theirs: BufferGroup.)
 struct Scanner {
   void* tmp = nullptr;
   size_t bytes = 0;
@@ -356,37 +336,41 @@ struct Scanner {
 };
 
 // The device buffers sized by one capacity (cap + extra elements each).  A buffer is named once, where it is
-// added; allocation and growth are loops over the list, so no buffer can be left at the old size.
+// added; allocation and growth are loops over the list, so no buffer can be left at the old size.  The group owns
+// the buffers; the build reads them through the pointers it named (`view`), which follow every reallocation.
 struct BufferGroup {
   struct Buf {
-    void** p;
+    void** view;
     size_t elem;
     int extra;
+    DeviceBuf<char> own;
     size_t bytes(long long cap) const { return (size_t)(cap + extra) * elem; }
   };
   long long cap = 0;
   std::vector<Buf> bufs;
   template <typename... T>
   void add(int extra, T**... p) {
-    (bufs.push_back(Buf{(void**)p, sizeof(T), extra}), ...);
+    (bufs.push_back(Buf{(void**)p, sizeof(T), extra, {}}), ...);
   }
-  hipError_t alloc_all(Arena& A, long long capacity) {
+  hipError_t alloc_all(long long capacity) {
     cap = capacity;
-    for (const Buf& b : bufs)
-      if (hipError_t e = A.alloc_bytes(b.p, b.bytes(cap))) return e;
+    for (Buf& b : bufs) {
+      if (hipError_t e = b.own.alloc(b.bytes(cap))) return e;
+      *b.view = b.own.get();
+    }
     return hipSuccess;
   }
   // Every buffer's contents move to a buffer of the new capacity.  Each old buffer is freed once its own copy
   // has run, so the peak device memory is the new capacity plus one old buffer, not the sum of every size.
-  hipError_t grow(Arena& A, hipStream_t st, long long new_cap) {
-    for (const Buf& b : bufs) {
-      void* q;
-      hipError_t e = A.alloc_bytes(&q, b.bytes(new_cap));
-      if (e == hipSuccess) e = hipMemcpyAsync(q, *b.p, b.bytes(cap), hipMemcpyDeviceToDevice, st);
+  hipError_t grow(hipStream_t st, long long new_cap) {
+    for (Buf& b : bufs) {
+      DeviceBuf<char> q;
+      hipError_t e = q.alloc(b.bytes(new_cap));
+      if (e == hipSuccess) e = hipMemcpyAsync(q.get(), b.own.get(), b.bytes(cap), hipMemcpyDeviceToDevice, st);
       if (e == hipSuccess) e = hipStreamSynchronize(st);
-      if (e == hipSuccess) e = A.release(*b.p);
       if (e != hipSuccess) return e;
-      *b.p = q;
+      b.own = std::move(q);
+      *b.view = b.own.get();
     }
     cap = new_cap;
     return hipSuccess;
@@ -407,7 +391,7 @@ struct Build {
   float4 rlo, rhi, rctr;  // the root's box and centre
   Nodes N{};
   int *cl, *cr, *nsplit, *npair, *nleaf, *nsplit_ex, *npair_ex, *nleaf_ex;  // a level's nodes: counts, scans
-  int *ptri, *pnode, *ntri_, *nnode;  // (triangle, node) pairs of the current and the next level
+  int *ptri[2], *pnode[2];  // (triangle, node) pairs: level l's in [l & 1], the next level's in the other
   int *fl, *fr, *sl, *sr;             // a level's pairs: side flags and their scans
   int *leaf_tri, *leaf_node;          // leaf store
   BufferGroup nodes, pairs, leaves;
@@ -420,7 +404,7 @@ struct Build {
     nodes.add(0, &N.lo, &N.hi, &N.ctr, &N.parent, &N.left, &N.right, &N.axis, &N.split_pos, &N.pstart, &N.pcnt,
               &N.leaf_start, &N.leaf_cnt, &N.size, &N.id, &cl, &cr);
     nodes.add(1, &nsplit, &npair, &nleaf, &nsplit_ex, &npair_ex, &nleaf_ex);  // scans: a total slot each
-    pairs.add(0, &ptri, &pnode, &ntri_, &nnode);
+    pairs.add(0, &ptri[0], &pnode[0], &ptri[1], &pnode[1]);
     pairs.add(1, &fl, &fr, &sl, &sr);
     leaves.add(0, &leaf_tri, &leaf_node);
   }
@@ -489,9 +473,9 @@ int init_store(Build& B) {
   const int ntri = B.ntri;
   // every split makes two non-empty children and levels stop past maxdepth: < 2^(maxdepth + 2) nodes
   HIP_TRY(B.nodes.alloc_all(
-      B.A, std::max<long long>(1024, std::min<long long>(4ll * ntri + 16, 1ll << std::min(B.maxdepth + 2, 20)))));
-  HIP_TRY(B.pairs.alloc_all(B.A, std::max<long long>(3 * (long long)ntri, 1024)));
-  HIP_TRY(B.leaves.alloc_all(B.A, std::max<long long>(3 * (long long)ntri, 1024)));
+      std::max<long long>(1024, std::min<long long>(4ll * ntri + 16, 1ll << std::min(B.maxdepth + 2, 20)))));
+  HIP_TRY(B.pairs.alloc_all(std::max<long long>(3 * (long long)ntri, 1024)));
+  HIP_TRY(B.leaves.alloc_all(std::max<long long>(3 * (long long)ntri, 1024)));
   // root: KDnode defaults (axis 0, splitPos 0, parent -1), all triangles in file order
   const int m1 = -1, z = 0;
   const float zf = 0.0f;
@@ -505,9 +489,9 @@ int init_store(Build& B) {
   HIP_TRY(hipMemcpyAsync(N.pstart, &z, 4, hipMemcpyHostToDevice, B.st));
   HIP_TRY(hipMemcpyAsync(N.pcnt, &ntri, 4, hipMemcpyHostToDevice, B.st));
   HIP_TRY(hipMemcpyAsync(N.id, &z, 4, hipMemcpyHostToDevice, B.st));
-  hipLaunchKernelGGL(k_iota, dim3(blocks(ntri)), dim3(BLK), 0, B.st, B.ptri, ntri);
+  hipLaunchKernelGGL(k_iota, dim3(blocks(ntri)), dim3(BLK), 0, B.st, B.ptri[0], ntri);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemsetAsync(B.pnode, 0, 4 * (size_t)ntri, B.st));
+  HIP_TRY(hipMemsetAsync(B.pnode[0], 0, 4 * (size_t)ntri, B.st));
   return KDPT_OK;
 }
 
@@ -522,8 +506,9 @@ int levels_stage(Build& B) {
     const int nl = B.lvl_count.back(), lb = B.lvl_begin.back();
     if (nl == 0) break;
     LevelArgs L{level, level % 3, B.maxdepth, lb, nl, npairs};
-    hipLaunchKernelGGL(k_side, dim3(blocks(npairs + 1)), dim3(BLK), 0, st, L, B.ptri, B.pnode, B.N, B.d_tlo, B.d_thi,
-                       B.fl, B.fr);
+    const int cur = level & 1;
+    hipLaunchKernelGGL(k_side, dim3(blocks(npairs + 1)), dim3(BLK), 0, st, L, B.ptri[cur], B.pnode[cur], B.N, B.d_tlo,
+                       B.d_thi, B.fl, B.fr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(B.scan.exclusive(B.fl, B.sl, npairs + 1));
     HIP_TRY(B.scan.exclusive(B.fr, B.sr, npairs + 1));
@@ -539,17 +524,15 @@ int levels_stage(Build& B) {
     HIP_TRY(hipMemcpyAsync(&tot[2], B.nleaf_ex + nl, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const long long nnodes_next = B.nnodes + 2ll * tot[0], npairs_next = tot[1], nleaf_next = B.leaf_total + tot[2];
-    if (nnodes_next > B.nodes.cap) HIP_TRY(B.nodes.grow(B.A, st, std::max(2 * B.nodes.cap, nnodes_next + 16)));
-    if (npairs_next > B.pairs.cap) HIP_TRY(B.pairs.grow(B.A, st, std::max(2 * B.pairs.cap, npairs_next + 16)));
-    if (nleaf_next > B.leaves.cap) HIP_TRY(B.leaves.grow(B.A, st, std::max(2 * B.leaves.cap, nleaf_next + 16)));
+    if (nnodes_next > B.nodes.cap) HIP_TRY(B.nodes.grow(st, std::max(2 * B.nodes.cap, nnodes_next + 16)));
+    if (npairs_next > B.pairs.cap) HIP_TRY(B.pairs.grow(st, std::max(2 * B.pairs.cap, npairs_next + 16)));
+    if (nleaf_next > B.leaves.cap) HIP_TRY(B.leaves.grow(st, std::max(2 * B.leaves.cap, nleaf_next + 16)));
     hipLaunchKernelGGL(k_children, dim3(blocks(nl)), dim3(BLK), 0, st, L, B.N, B.nsplit_ex, B.npair_ex, B.nleaf_ex,
                        B.nsplit, B.cl, B.cr, (int)B.leaf_total);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_scatter, dim3(blocks(npairs)), dim3(BLK), 0, st, L, B.N, B.ptri, B.pnode, B.fl, B.fr, B.sl,
-                       B.sr, B.nsplit, B.ntri_, B.nnode, B.leaf_tri, B.leaf_node);
+    hipLaunchKernelGGL(k_scatter, dim3(blocks(npairs)), dim3(BLK), 0, st, L, B.N, B.ptri[cur], B.pnode[cur], B.fl, B.fr,
+                       B.sl, B.sr, B.nsplit, B.ptri[cur ^ 1], B.pnode[cur ^ 1], B.leaf_tri, B.leaf_node);
     HIP_TRY(hipGetLastError());
-    std::swap(B.ptri, B.ntri_);
-    std::swap(B.pnode, B.nnode);
     npairs = npairs_next;
     B.leaf_total = nleaf_next;
     B.lvl_begin.push_back(lb + nl);
@@ -616,12 +599,8 @@ int build_kd_device(const float* v9, const float* n9, const int* mtl, int ntri, 
   if (ntri <= 0) return KDPT_OK;
   const auto t0 = std::chrono::steady_clock::now();
   HIP_TRY(hipSetDevice(device));
-  hipStream_t st;
-  HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  struct StreamGuard {
-    hipStream_t s;
-    ~StreamGuard() { (void)hipStreamDestroy(s); }
-  } sg{st};
+  kdpt::Stream st;  // (destroyed after the build's buffers)
+  HIP_TRY(st.create());
   Arena A;
   Build B(v9, n9, mtl, ntri, maxdepth, st, A);
   int rc;

@@ -41,6 +41,7 @@
 
 #include "../../include/kdpt.h"
 #include "kdpt_error.h"
+#include "kdpt_owned.h"
 #include "kdpt_device.h"
 #include "kdpt_clusters.h"
 #include "kdpt_scene_prep.h"
@@ -92,11 +93,13 @@ struct RayQueue {
   int* count_at(int depth, bool gen_geoms) const { return (depth == 0 && gen_geoms) ? cc0_cur : ccount + depth; }
 };
 
-// One iteration's working set (alloc_iter / free_iter).  The context has one for the one-at-a-time entry points
+// One iteration's working set (alloc_iter).  The context has one for the one-at-a-time entry points
 // (a group of one) and B per pipeline group; everything an iteration shares with the others (scene, options,
-// knobs, counters) stays in the context.
+// knobs, counters) stays in the context.  A state does not move or copy (its arena does not): `q` of every state
+// of a group points into the first state's own_queue, so states live in place (in the context, or behind a
+// unique_ptr).
 struct IterState {
-  std::vector<void*> allocs;  // the device memory below
+  Arena allocs;  // the device memory below
   PathBuf buf[2]{};
   int cur = 0;
   int* counts = nullptr;  // [cap + 2] live paths per bounce, [1] fault word, then [cap] work counters, ...
@@ -112,9 +115,9 @@ struct IterState {
   int* tile_off = nullptr;
   unsigned long long* lb = nullptr;       // [cap][ntiles] k_shade_fused's look-back records
   unsigned long long* trace_t = nullptr;  // per-bounce intersect launch record
-  int* h_counts = nullptr;  // pinned
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  std::vector<hipEvent_t> bounce_ev;
+  PinnedBuf<int> h_counts;
+  Event ev0, ev1;
+  std::vector<Event> bounce_ev;
   // where the iteration's light goes: the context's image, or a pipeline state's own partial image, which
   // k_gen_rays zeroes first (zero_partial); and where its segment count is added
   float* image = nullptr;
@@ -135,27 +138,133 @@ struct IterState {
 
 // A pipeline group: `batch` iterations at a time in lockstep on the group's own stream; acc_ev: its last
 // batch's add into the target done.
+// Ownership (DESIGN.md "Ownership"): members are released in reverse order of declaration, here and in kdpt_ctx,
+// so an owner's stream is declared first and goes after the buffers and events used on it; a group's states go
+// last first, because state 0 owns the slabs the others view.
 struct IterGroup {
-  hipStream_t stream = nullptr;
-  hipEvent_t acc_ev = nullptr;
+  Stream stream;
+  Event acc_ev;
   std::vector<std::unique_ptr<IterState>> its;
+  IterGroup() = default;
+  IterGroup(IterGroup&&) = default;
+  ~IterGroup() {
+    while (!its.empty()) its.pop_back();
+  }
+};
+
+// The exact one-level cull's direction masks (kdpt_clusters.h build_dir_masks), built when the scene's rigorous
+// margin is above the cap; S.cl_mask points at them unless a knob chose another cull.  A rebuild swaps `dev`.
+struct MaskTables {
+  DeviceBuf<unsigned long long> dev;
+  DeviceBuf<float4> tn;  // the clusters' per-entry normal records (DevScene::cl_tn)
+  int n = 0;
+  std::unique_ptr<ClusterSet> cs;  // the clusters the masks were built from ("cull_mask_n" rebuilds)
+  double build_ms = 0;             // kdpt_stats
+};
+
+// enable_kd = 0: the brute-force intersect kernel's view of the OBJ triangles in file order (the context's arena)
+struct BruteScene {
+  const BruteShape* shapes = nullptr;
+  int num_shapes = 0;
+  const float4* chunk_lo = nullptr;  // boxes of 64 file-order triangles
+  const float4* chunk_hi = nullptr;
+  float chunk_k_min = 0.0f;    // the smallest of the chunks' own cull coefficients (chunk_lo[j].w)
+};
+
+// Pipelined iterations (kdpt_trace_iterations): groups of `batch` iteration states, each state with a partial
+// image of its own; the partial images are added into `image` in iteration order, each batch's add on its
+// group's stream after the previous batch's add (acc_ev / acc_last: the chain).
+struct Pipeline {
+  Event entry_ev;  // enqueue_iterations: what the context's own stream held when the call began
+  std::vector<IterGroup> groups;
+  int batch = 1;
+  int next = 0;                   // the group the next batch goes to
+  hipEvent_t acc_last = nullptr;  // the most recent add (a group's acc_ev): the next add follows it
+  hipEvent_t img_last = nullptr;  // the most recent frame reduce + image add (one of ShardedFrames::ev)
+  // intersect-kernel timing (testing_mode) of every iteration, read back at synchronisation: a pool
+  std::vector<std::vector<Event>> pending_ev;  // per launched iteration: 2 events per bounce
+  std::vector<Event> free_ev;
+  // Drop the groups (their streams drained here), last first.
+  void drop_groups() {
+    for (; !groups.empty(); groups.pop_back())
+      if (groups.back().stream) (void)hipStreamSynchronize(groups.back().stream.get());
+    acc_last = nullptr;
+  }
+};
+
+// spp-sharded frames (kdpt_comm_init / kdpt_render_frames / kdpt_render_sharded): this context's rank, the
+// RCCL communicator (null: one rank, or the in-process copy reduce of kdpt_render_sharded), two frame
+// buffers (frame f accumulates into buf[f & 1] while f - 1 is reduced) and rank 0's reduced frame
+struct ShardedFrames {
+  int nranks = 1, rank = 0;
+  void* comm = nullptr;  // ncclComm_t (release_comm)
+  bool owns_comm = false;
+  bool external_reduce = false;  // kdpt_comm_init without an id: each rank hands its frame shares out
+  Stream reduce_stream;          // the frames' reduces and image adds, beside the accumulation stream
+  DeviceBuf<float> buf[2], sum;
+  Event ev[2];                   // buf[k] consumed by its reduce
+  double reduce_spin_us = 0;     // "reduce_spin_us" knob: a device spin before every frame's reduce (a slow peer)
+  HostRegistrations host_reg;    // pageable host `out` ranges pinned for kdpt_render_frames (until synchronize)
+};
+
+// Ray queries (kdpt_cast_rays): buffers of one chunk, made on first use and remade when "cast_chunk" changes --
+// the input and output staging buffers (host arrays go through them), the query's own candidate queue, hit
+// records and counters (CastArgs); nothing here is shared with the render path.  `b = {}` drops the buffers.
+struct CastQuery {
+  int chunk = 1 << 20;  // "cast_chunk" knob: rays per chunk
+  struct Buffers {
+    int alloc = 0;                    // the chunk size the buffers were made for (0: none)
+    DeviceBuf<float> in;              // [6 chunk] origins, then directions
+    DeviceBuf<kdpt_ray_hit> out;      // [chunk]
+    DeviceBuf<float4> cray;           // [2 chunk]
+    DeviceBuf<int> cand;              // [chunk]
+    DeviceBuf<int2> hits;             // [chunk]
+    DeviceBuf<int> cnt;               // [2]
+    DeviceBuf<unsigned long long> tt; // [3]
+  } b;
+  Event ev[2];
+  long long rays = 0, traced = 0;  // since create/reset (kdpt_cast_stats)
+  double ms = 0;                   // the last call's device time
+};
+
+// Path-traced ray queries (kdpt_trace_rays, kdpt_camera_rays): an iteration state of their own, made on first
+// use (query_state) -- its image is the query's radiance buffer, its segment and intersect totals go to `totals`
+// instead of the context's -- and a staging buffer for host arrays; kdpt_trace_rays_moments' partial buffer (each
+// iteration gathers into it, zeroed by a fill) and second moments.  Nothing is shared with the render path.
+struct RayQuery {
+  std::unique_ptr<IterState> state;
+  DeviceBuf<float> image;   // [3 npix]
+  DeviceBuf<float> stage;   // [6 npix] origins, then directions (inputs of host callers, camera rays on their way out)
+  DeviceBuf<unsigned long long> totals;  // [0] ShadeArgs::total_segments, [1..3] trace_total / trace_rays
+  DeviceBuf<float> partial, sumsq;       // [3 npix] each
+  long long segments = 0, traced = 0;  // of the last kdpt_trace_rays (kdpt_trace_rays_stats)
+  double ms = 0;                       // ... and its device time
+};
+
+// Per-pixel second moments (kdpt_set_moments): sumsq beside the image, the partial image the solo state gathers
+// into while they are on (added with k_accumulate_moments at nb = 1), the number of iterations added since both
+// were zeroed, and kdpt_noise_map's / kdpt_noise_estimate's buffers.  All null / 0 while moments are off.
+struct Moments {
+  bool on = false;
+  DeviceBuf<float> sumsq, partial;  // [3 npix]
+  long long samples = 0;
+  DeviceBuf<float> noise_stage;         // [npix] kdpt_noise_map into host memory
+  DeviceBuf<NoisePartial> noise_parts;  // [workgroups + 1] k_noise_partials' partials, then k_noise_final's result
 };
 
 struct kdpt_ctx {
   int device = 0;
-  hipStream_t stream = nullptr;
+  Stream stream;  // (declared before every other resource: destroyed last)
   kdpt_options opt{};
   kdpt_camera cam{};
   int traceDepth = 0;
   int W = 0, H = 0, npix = 0, ntiles = 0, nkeys = 1;
   int cap = 8;
   DevScene S{};
-  // owned device memory
-  std::vector<void*> allocs;
-  uchar4* pbo_staging = nullptr;  // kdpt_write_pbo into host memory
+  Arena allocs;  // what lives as long as the context: the scene's uploads, the image, the counters
+  DeviceBuf<uchar4> pbo_staging;  // kdpt_write_pbo into host memory
   IterState solo;         // kdpt_trace_iteration[_async], kdpt_debug_paths, kdpt_count_iteration; into `image`
-  float* image = nullptr;
-  bool image_external = false;
+  float* image = nullptr;  // in `allocs`, or the caller's (options.external_image: not owned)
   int tree_mode = 0;      // TreeMode
   int trace_grid = 0;     // persistent intersect workgroups (a pipelined call's launches take a share of them)
   int full_trace_grid = 0;  // the occupancy-derived grid (trace_grid before a "trace_grid_frac" knob)
@@ -168,17 +277,12 @@ struct kdpt_ctx {
   bool shade_oob = false;
   bool super_cull = true;          // "super_cull" tuning knob: 0 = no TREE_LDS16S route (one-level cull)
   CullMargin cull{};                // the scene's cluster-cull margins (kdpt_clusters.h cluster_margin)
-  // the exact one-level cull's direction masks (kdpt_clusters.h build_dir_masks), built when the scene's rigorous
-  // margin is above the cap; S.cl_mask points at them unless a knob chose another cull
-  unsigned long long* mask_dev = nullptr;
-  float4* tn_dev = nullptr;  // the clusters' per-entry normal records (DevScene::cl_tn)
-  int mask_n = 0;
+  MaskTables masks;
   bool cull_exact = true;   // "cull_exact" knob: 0 = the fast-margin cull (not exact for such scenes)
-  double create_ms = 0, mask_build_ms = 0;  // kdpt_create's host wall time, and the masks' (kdpt_stats)
+  double create_ms = 0;     // kdpt_create's host wall time (kdpt_stats)
   bool cu_mask_streams = false;  // batch and reduce streams created with an all-CU mask (create_stream)
   bool cull_scene = true;   // false after "cluster_cull" = 0 or a fixed "cull_margin"
-  std::unique_ptr<ClusterSet> mask_cs;  // the clusters the masks were built from ("cull_mask_n" rebuilds)
-  int tree_format = 0;             // "tree_format" knob: 16 / 32 = LDS node records of that size only
+  int tree_format = 0;            // "tree_format" knob: 16 / 32 = LDS node records of that size only
   size_t tree_lds = 0;    // dynamic LDS bytes of the intersect kernel (TREE_LDS)
   bool no_fuse = false;         // "shade_fused" = 0: k_shade + k_scan + k_scatter instead of k_shade_fused
   bool shade_batch = true;      // "shade_batch": a batch's fused shading in one launch (k_shade_fused_b)
@@ -191,82 +295,18 @@ struct kdpt_ctx {
   double wall_khz = 100000.0;                    // s_memrealtime frequency
   kdpt_stats stats{};
   bool sync_debug = false;  // "sync_debug" = 1: synchronise and log after every launch
-  // Pipelined iterations (kdpt_trace_iterations): groups of `group_batch` iteration states, each state with a
-  // partial image of its own; the partial images are added into `image` in iteration order, each batch's add
-  // on its group's stream after the previous batch's add (acc_ev / acc_last: the chain).
-  std::vector<IterGroup> groups;
-  int group_batch = 1;
-  int next_group = 0;  // the group the next batch goes to
   bool profile_batches = false;
   bool profile_steps = false;  // "profile_batches" = 2
-  hipEvent_t entry_ev = nullptr;   // enqueue_iterations: what the context's own stream held when the call began
-  hipEvent_t acc_last = nullptr;   // the most recent add (a group's acc_ev): the next add follows it
-  hipEvent_t img_last = nullptr;   // the most recent frame reduce + image add (one of frame_ev)
-  // intersect-kernel timing (testing_mode) of every iteration, read back at synchronisation
-  std::vector<std::vector<hipEvent_t>> pending_ev;  // per launched iteration: 2 events per bounce
-  std::vector<hipEvent_t> free_ev;
   double intersect_ms_total = 0;
   long long intersect_launches_total = 0;
-  // enable_kd = 0: brute-force intersect kernel over the OBJ triangles in file order
-  bool brute = false;
-  bool viz = false;  // viz_kd: the KD node boxes drawn as boxes (k_viz)
-  BruteShape* shapes = nullptr;
-  int num_shapes = 0;
-  float4* chunk_lo = nullptr;  // brute force: boxes of 64 file-order triangles
-  float4* chunk_hi = nullptr;
-  float chunk_k_min = 0.0f;    // brute force: the smallest of the chunks' own cull coefficients (chunk_lo[j].w)
-  // spp-sharded frames (kdpt_comm_init / kdpt_render_frames / kdpt_render_sharded): this context's rank, the
-  // RCCL communicator (null: one rank, or the in-process copy reduce of kdpt_render_sharded), two frame
-  // buffers (frame f accumulates into frame_buf[f & 1] while f - 1 is reduced) and rank 0's reduced frame
-  int nranks = 1, rank = 0;
-  void* comm = nullptr;  // ncclComm_t
-  bool owns_comm = false;
-  bool external_reduce = false;  // kdpt_comm_init without an id: each rank hands its frame shares out
-  float* frame_buf[2] = {nullptr, nullptr};
-  float* frame_sum = nullptr;
-  hipEvent_t frame_ev[2] = {nullptr, nullptr};      // frame_buf[k] consumed by its reduce
-  hipStream_t reduce_stream = nullptr;  // the frames' reduces and image adds, beside the accumulation stream
-  double reduce_spin_us = 0;  // "reduce_spin_us" knob: a device spin before every frame's reduce (a slow peer)
-  std::vector<void*> host_reg;  // pageable host `out` ranges pinned for kdpt_render_frames (released at synchronize)
-  // ray queries (kdpt_cast_rays): buffers of one chunk, made on first use and remade when "cast_chunk" changes --
-  // the input and output staging buffers (host arrays go through them), the query's own candidate queue, hit
-  // records and counters (CastArgs); nothing here is shared with the render path
-  int cast_chunk = 1 << 20;     // "cast_chunk" knob: rays per chunk
-  int cast_alloc = 0;           // the chunk size the buffers below were made for (0: none yet)
-  float* cast_in = nullptr;     // [6 chunk] origins, then directions
-  kdpt_ray_hit* cast_out = nullptr;  // [chunk]
-  float4* cast_cray = nullptr;  // [2 chunk]
-  int* cast_cand = nullptr;     // [chunk]
-  int2* cast_hits = nullptr;    // [chunk]
-  int* cast_cnt = nullptr;      // [2]
-  unsigned long long* cast_tt = nullptr;  // [3]
-  hipEvent_t cast_ev[2] = {nullptr, nullptr};
-  long long cast_rays = 0, cast_traced = 0;  // since create/reset (kdpt_cast_stats)
-  double cast_ms = 0;                        // the last call's device time
-  // path-traced ray queries (kdpt_trace_rays, kdpt_camera_rays): an iteration state of their own, made on first
-  // use (query_state) -- its image is the query's radiance buffer, its segment and intersect totals go to
-  // query_totals instead of the context's -- and a staging buffer for host arrays; nothing here is shared with
-  // the render path or with kdpt_cast_rays
-  IterState query;
-  bool query_ready = false;
-  float* query_image = nullptr;  // [3 npix]
-  float* query_stage = nullptr;  // [6 npix] origins, then directions (inputs of host callers, camera rays on their way out)
-  unsigned long long* query_totals = nullptr;  // [0] ShadeArgs::total_segments, [1..3] trace_total / trace_rays
-  long long query_segments = 0, query_traced = 0;  // of the last kdpt_trace_rays (kdpt_trace_rays_stats)
-  double query_ms = 0;                             // ... and its device time
-  // kdpt_trace_rays_moments: the partial buffer each of the query's iterations gathers into (zeroed by a fill on
-  // the stream) and the query's second moments, made on first use; nothing here is shared with the render's moments
-  float* query_partial = nullptr;  // [3 npix]
-  float* query_sumsq = nullptr;    // [3 npix]
-  // per-pixel second moments (kdpt_set_moments): sumsq beside the image, the partial image the solo state gathers
-  // into while they are on (added with k_accumulate_moments at nb = 1), the number of iterations added since both
-  // were zeroed, and kdpt_noise_map's / kdpt_noise_estimate's buffers.  All null / 0 while moments are off.
-  bool moments = false;
-  float* mom_sumsq = nullptr;    // [3 npix]
-  float* mom_partial = nullptr;  // [3 npix]
-  long long mom_samples = 0;
-  float* noise_stage = nullptr;         // [npix] kdpt_noise_map into host memory
-  NoisePartial* noise_parts = nullptr;  // [workgroups + 1] k_noise_partials' partials, then k_noise_final's result
+  bool brute = false;  // enable_kd = 0: brute-force intersect kernel over the OBJ triangles in file order
+  bool viz = false;    // viz_kd: the KD node boxes drawn as boxes (k_viz)
+  BruteScene bf;
+  Pipeline pipe;
+  ShardedFrames frames;
+  CastQuery cast;
+  RayQuery query;
+  Moments mom;
   // an iteration (or a frame) has been added into the image since create / kdpt_reset: with stats.iterations what
   // kdpt_set_moments(1) refuses on (kdpt_trace_iteration_async counts no iteration)
   bool accumulated = false;
@@ -288,43 +328,36 @@ int refuse_shading() {
               "kdpt_cast_rays and enable_kd = 0 remain available");
 }
 
-int create_stream(kdpt_ctx* c, hipStream_t* st) {
+int create_stream(kdpt_ctx* c, Stream* st) {
+  int cus = 0;
   if (c->cu_mask_streams) {
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, c->device));
-    const int n = std::max(1, prop.multiProcessorCount);
-    std::vector<uint32_t> mask((n + 31) / 32, 0xffffffffu);
-    if (n % 32) mask.back() = (1u << (n % 32)) - 1u;
-    if (hipExtStreamCreateWithCUMask(st, (uint32_t)mask.size(), mask.data()) == hipSuccess) return KDPT_OK;
-    (void)hipGetLastError();
+    cus = std::max(1, prop.multiProcessorCount);
   }
-  HIP_TRY(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
+  HIP_TRY(st->create(cus));
   return KDPT_OK;
 }
 
-template <typename Owner, typename T>  // a context or an iteration state
+// n elements in the arena of a context or an iteration state
+template <typename Owner, typename T>
 int dalloc(Owner* c, T** p, size_t n) {
-  void* q = nullptr;
-  HIP_TRY(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
-  c->allocs.push_back(q);
-  *p = (T*)q;
+  if (const hipError_t e = c->allocs.alloc(p, n)) return hip_fail("hipMalloc", e);
   return KDPT_OK;
 }
 
+// A prepared array into the context's arena, and the field (of DevScene, or a view of the context's) pointed at it.
 template <typename T>
-int dupload(kdpt_ctx* c, T** p, const T* src, size_t n) {
-  int rc = dalloc(c, p, n);
-  if (rc) return rc;
-  if (n) HIP_TRY(hipMemcpy(*p, src, n * sizeof(T), hipMemcpyHostToDevice));
+int dupload(kdpt_ctx* c, const T** field, const std::vector<T>& v) {
+  T* d = nullptr;
+  if (const hipError_t e = c->allocs.alloc(&d, v.size())) return hip_fail("hipMalloc", e);
+  if (!v.empty()) HIP_TRY(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  *field = d;
   return KDPT_OK;
 }
 
 int launch_iteration(kdpt_ctx* c, int iter, int stop_depth, bool count);
 int accumulate_iteration(kdpt_ctx* c, int iter);
-void release_comm(kdpt_ctx* c);  // (multi-GPU section, end of file)
-void unregister_host(kdpt_ctx* c);
-void free_cast_buffers(kdpt_ctx* c);  // (ray queries, end of file)
-void free_moments(kdpt_ctx* c);       // (second moments, end of file)
 // A batch that starts from caller-supplied rays instead of the camera's (kdpt_trace_rays; one iteration per
 // batch): the rays in device memory, and where the shading adds what it would add to the context's intersect
 // totals (kdpt_ctx::trace_total's layout).
@@ -333,21 +366,29 @@ struct RaySource {
   unsigned long long* trace_total;
 };
 int launch_batch(kdpt_ctx* c, IterState* const* its, const int* iters, int nb, hipStream_t st, int trace_grid,
-                 int stop_depth, bool count, std::vector<hipEvent_t>* bev, const RaySource* rays = nullptr);
+                 int stop_depth, bool count, std::vector<Event>* bev, const RaySource* rays = nullptr);
 
 // Work queued on the context's own stream that reads or writes `image` must follow the pipelined
 // accumulation (kdpt_trace_iterations adds partial images on the batch streams without a host sync) and the
 // frames' image adds (kdpt_render_frames, on the reduce stream).
 int join_accum(kdpt_ctx* c) {
-  if (c->acc_last) HIP_TRY(hipStreamWaitEvent(c->stream, c->acc_last, 0));
-  if (c->img_last) HIP_TRY(hipStreamWaitEvent(c->stream, c->img_last, 0));
+  if (c->pipe.acc_last) HIP_TRY(hipStreamWaitEvent(c->stream, c->pipe.acc_last, 0));
+  if (c->pipe.img_last) HIP_TRY(hipStreamWaitEvent(c->stream, c->pipe.img_last, 0));
   return KDPT_OK;
 }
 
+// Is p memory of the context's device?  (What a caller hands in may be host memory or another device's.)
+bool on_context_device(const kdpt_ctx* c, const void* p) {
+  hipPointerAttribute_t attr{};
+  const bool dev = hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeDevice &&
+                   attr.device == c->device;
+  (void)hipGetLastError();  // a plain host pointer is an error for hipPointerGetAttributes on some runtimes
+  return dev;
+}
 
 // stats.segments / seg_per_bounce / bounces of the iteration whose counts are in the solo state's h_counts
 int segments_from_counts(kdpt_ctx* c) {
-  const int* h_counts = c->solo.h_counts;
+  const int* h_counts = c->solo.h_counts.get();
   long long seg = 0;
   int bounces = 0;
   for (int d = 0; d < 32; d++) c->stats.seg_per_bounce[d] = 0;
@@ -364,16 +405,6 @@ int segments_from_counts(kdpt_ctx* c) {
   return bounces;
 }
 
-void free_iter(IterState* it) {
-  for (void* p : it->allocs) (void)hipFree(p);
-  if (it->h_counts) (void)hipHostFree(it->h_counts);
-  if (it->ev0) (void)hipEventDestroy(it->ev0);
-  if (it->ev1) (void)hipEventDestroy(it->ev1);
-  for (auto e : it->bounce_ev)
-    if (e) (void)hipEventDestroy(e);
-  *it = IterState{};
-}
-
 // Per-iteration device state: two path buffers, tile counts/offsets, live counts + fault word + work counters, and
 // the events; and in a group's first state (head null: `it` is state 0 of a group of B) the group's ray queue and
 // hit records, of which state b of the group (head: the first state) takes its view.  (The scene, image and
@@ -382,7 +413,7 @@ void free_iter(IterState* it) {
 // on a non-blocking stream, which does not order itself after the null stream, so a plain hipMemset there could
 // land after the first iteration's camera-ray kernel had set its path count (that iteration would vanish).
 // partial: with a partial image of its own (a pipeline state); else the caller points `image` at its target.
-// A failed allocation leaves what was made to free_iter.
+// A failed allocation leaves what was made in the state, for the caller to drop with it.
 int alloc_iter(kdpt_ctx* c, IterState* it, hipStream_t st, bool partial, IterState* head = nullptr, int b = 0,
                int B = 1) {
   int rc;
@@ -407,7 +438,7 @@ int alloc_iter(kdpt_ctx* c, IterState* it, hipStream_t st, bool partial, IterSta
         (rc = dalloc(it, &q.cray, 2 * B * npix)))
       return rc;
   }
-  HIP_TRY(hipHostMalloc((void**)&it->h_counts, sizeof(int) * (cap + 3), hipHostMallocDefault));
+  HIP_TRY(it->h_counts.alloc(cap + 3));
   HIP_TRY(hipMemsetAsync(it->counts, 0, sizeof(int) * (4 * cap + 5), st));
   HIP_TRY(hipMemsetAsync(it->lb, 0, sizeof(unsigned long long) * cap * ntiles, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -426,37 +457,24 @@ int alloc_iter(kdpt_ctx* c, IterState* it, hipStream_t st, bool partial, IterSta
     it->zero_partial = true;  // k_gen_rays clears the partial image
   }
   it->total_segments = c->total_segments;
-  HIP_TRY(hipEventCreate(&it->ev0));
-  HIP_TRY(hipEventCreate(&it->ev1));
+  HIP_TRY(it->ev0.create());
+  HIP_TRY(it->ev1.create());
   it->bounce_ev.resize(2 * cap);
-  for (auto& e : it->bounce_ev) HIP_TRY(hipEventCreate(&e));
+  for (Event& e : it->bounce_ev) HIP_TRY(e.create());
   return KDPT_OK;
-}
-
-// Drop the pipeline's groups (their streams drained here), last first.
-void drop_groups(kdpt_ctx* c) {
-  for (size_t g = c->groups.size(); g-- > 0;) {
-    IterGroup& grp = c->groups[g];
-    if (grp.stream) (void)hipStreamSynchronize(grp.stream);
-    for (size_t k = grp.its.size(); k-- > 0;) free_iter(grp.its[k].get());
-    if (grp.acc_ev) (void)hipEventDestroy(grp.acc_ev);
-    if (grp.stream) (void)hipStreamDestroy(grp.stream);
-  }
-  c->groups.clear();
-  c->acc_last = nullptr;
 }
 
 // One more pipeline group: its stream, then its B iteration states, the first with the group's ray queue.
 int make_group(kdpt_ctx* c, int B) {
-  c->groups.emplace_back();
-  IterGroup& grp = c->groups.back();
+  c->pipe.groups.emplace_back();
+  IterGroup& grp = c->pipe.groups.back();
   if (int rc = create_stream(c, &grp.stream)) return rc;
   for (int b = 0; b < B; b++) {
     grp.its.emplace_back(new IterState());
     int rc = alloc_iter(c, grp.its.back().get(), grp.stream, true, b ? grp.its[0].get() : nullptr, b, B);
     if (rc) return rc;
   }
-  HIP_TRY(hipEventCreateWithFlags(&grp.acc_ev, hipEventDisableTiming));
+  HIP_TRY(grp.acc_ev.create_untimed());
   return KDPT_OK;
 }
 
@@ -466,6 +484,14 @@ struct PartialImages {
   const float* p[MAXB];
   int nb;
 };
+// (PartialImages or MomentParts: the first nb of `partials`)
+template <typename Parts>
+Parts fill_parts(const float* const* partials, int nb) {
+  Parts parts{};
+  parts.nb = nb;
+  for (int b = 0; b < nb; b++) parts.p[b] = partials[b];
+  return parts;
+}
 __global__ void k_accumulate_batch(float* __restrict__ image, PartialImages parts, int n3) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n3) return;
@@ -479,17 +505,12 @@ __global__ void k_accumulate_batch(float* __restrict__ image, PartialImages part
 // mom_sumsq in the same pass.
 int launch_accumulate(kdpt_ctx* c, float* target, const float* const* partials, int nb, hipStream_t st) {
   const int n3 = 3 * c->npix;
-  if (c->moments && target == c->image) {
-    MomentParts parts{};
-    parts.nb = nb;
-    for (int b = 0; b < nb; b++) parts.p[b] = partials[b];
-    hipLaunchKernelGGL(k_accumulate_moments, dim3((n3 + 255) / 256), dim3(256), 0, st, target, c->mom_sumsq, parts,
-                       n3);
+  if (c->mom.on && target == c->image) {
+    hipLaunchKernelGGL(k_accumulate_moments, dim3((n3 + 255) / 256), dim3(256), 0, st, target, c->mom.sumsq.get(),
+                       fill_parts<MomentParts>(partials, nb), n3);
   } else {
-    PartialImages parts{};
-    parts.nb = nb;
-    for (int b = 0; b < nb; b++) parts.p[b] = partials[b];
-    hipLaunchKernelGGL(k_accumulate_batch, dim3((n3 + 255) / 256), dim3(256), 0, st, target, parts, n3);
+    hipLaunchKernelGGL(k_accumulate_batch, dim3((n3 + 255) / 256), dim3(256), 0, st, target,
+                       fill_parts<PartialImages>(partials, nb), n3);
   }
   HIP_TRY(hipGetLastError());
   return KDPT_OK;
@@ -497,7 +518,7 @@ int launch_accumulate(kdpt_ctx* c, float* target, const float* const* partials, 
 
 // Read back the intersect-kernel events of finished iterations (testing_mode).
 int drain_intersect_events(kdpt_ctx* c) {
-  for (auto& evs : c->pending_ev) {
+  for (auto& evs : c->pipe.pending_ev) {
     for (size_t k = 0; k + 1 < evs.size(); k += 2) {
       float ms = 0;
       HIP_TRY(hipEventSynchronize(evs[k + 1]));
@@ -506,9 +527,9 @@ int drain_intersect_events(kdpt_ctx* c) {
         c->intersect_launches_total++;
       }
     }
-    for (auto e : evs) c->free_ev.push_back(e);
+    for (Event& e : evs) c->pipe.free_ev.push_back(std::move(e));
   }
-  c->pending_ev.clear();
+  c->pipe.pending_ev.clear();
   return KDPT_OK;
 }
 
@@ -528,9 +549,9 @@ void fix_cull(kdpt_ctx* c, float K) {
 // The one-level route's cull: the exact masked one when the scene has masks and the knobs leave the scene's
 // margins in place, else the margin-only cull.
 void apply_cull_route(kdpt_ctx* c) {
-  c->S.cl_mask = (c->mask_dev && c->cull_exact && c->cull_scene) ? c->mask_dev : nullptr;
-  c->S.mask_n = c->mask_n;
-  c->S.cl_tn = c->tn_dev;
+  c->S.cl_mask = (c->cull_exact && c->cull_scene) ? c->masks.dev.get() : nullptr;
+  c->S.mask_n = c->masks.n;
+  c->S.cl_tn = c->masks.tn.get();
 }
 // The masked cull's cells on the device (kdpt_device.h dir_mask_cell, the code the host builder runs): one
 // workgroup per (cluster, 256 buckets), the cluster's 64 entries staged in LDS (every lane reads the same entry:
@@ -552,21 +573,13 @@ __global__ void __launch_bounds__(256) k_build_masks(const double* __restrict__ 
   masks[(size_t)b * ncl + c] = dir_mask_cell(se[0], se[1], se[2], se[3], se[4], sk, bd + 4 * (size_t)b, Kf);
 }
 
-// Release one of the context's device allocations before kdpt_destroy (a rebuilt table).
-void dfree(kdpt_ctx* c, void* p) {
-  if (!p) return;
-  auto it = std::find(c->allocs.begin(), c->allocs.end(), p);
-  if (it != c->allocs.end()) c->allocs.erase(it);
-  (void)hipFree(p);
-}
-
 // The direction masks of the scene's clusters at resolution n (cube-map cells per face edge), built on the device (k_build_masks) from the per-entry records and the bucket directions the host
 // computes (kdpt_clusters.h mask_entries / mask_buckets; tests/test_gpu_parity.py checks the cells against the
 // host builder).  A rebuild (knobs "cull_mask_n", "cull_fast_k") frees the previous table once the new one is
 // filled; a failed one changes nothing in the context.
 int build_masks(kdpt_ctx* c, int n) {
   const auto t0 = std::chrono::steady_clock::now();
-  const ClusterSet& cs = *c->mask_cs;
+  const ClusterSet& cs = *c->masks.cs;
   const int ncl = (int)cs.info.size(), nb = 6 * n * n;
   // the intersect kernel indexes the table with 32 bits (kdpt_device.h, S.cl_mask[bucket * num_clusters + c]): a
   // resolution whose table has 2^32 cells or more is refused here, before anything is freed or allocated
@@ -589,56 +602,41 @@ int build_masks(kdpt_ctx* c, int n) {
     ent[3 * ne + k] = me.beta[k];
     ent[4 * ne + k] = me.dthr[k];
   }
-  // The new table is the context's only once it is filled: until then mask_dev, mask_n and S.cl_mask keep
+  // The new table is the context's only once it is filled: until then masks.dev, masks.n and S.cl_mask keep
   // describing the previous one, which a failure below leaves in place.
-  unsigned long long* dm = nullptr;
-  double* d_ent = nullptr;
-  float* d_krig = nullptr;
-  double* d_bd = nullptr;
-  auto release = [&]() {
-    (void)hipFree(d_ent);
-    (void)hipFree(d_krig);
-    (void)hipFree(d_bd);
-  };
+  DeviceBuf<unsigned long long> dm;
+  DeviceBuf<double> d_ent, d_bd;
+  DeviceBuf<float> d_krig;
   // (the uploads on the context's stream, ahead of the kernel; pageable sources are staged before each call
   // returns, and the stream is drained before the temporaries go)
   hipError_t e;
-  if ((e = hipMalloc((void**)&dm, std::max<size_t>((size_t)nb * ncl, 1) * sizeof(unsigned long long))) != hipSuccess ||
-      (e = hipMalloc(&d_ent, ent.size() * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc(&d_krig, me.krig.size() * sizeof(float))) != hipSuccess ||
-      (e = hipMalloc(&d_bd, bd.size() * sizeof(double))) != hipSuccess ||
-      (e = hipMemcpyAsync(d_ent, ent.data(), ent.size() * sizeof(double), hipMemcpyHostToDevice, c->stream)) !=
+  if ((e = dm.alloc((size_t)nb * ncl)) != hipSuccess || (e = d_ent.alloc(ent.size())) != hipSuccess ||
+      (e = d_krig.alloc(me.krig.size())) != hipSuccess || (e = d_bd.alloc(bd.size())) != hipSuccess ||
+      (e = hipMemcpyAsync(d_ent.get(), ent.data(), ent.size() * sizeof(double), hipMemcpyHostToDevice, c->stream)) !=
           hipSuccess ||
-      (e = hipMemcpyAsync(d_krig, me.krig.data(), me.krig.size() * sizeof(float), hipMemcpyHostToDevice, c->stream)) !=
-          hipSuccess ||
-      (e = hipMemcpyAsync(d_bd, bd.data(), bd.size() * sizeof(double), hipMemcpyHostToDevice, c->stream)) != hipSuccess) {
+      (e = hipMemcpyAsync(d_krig.get(), me.krig.data(), me.krig.size() * sizeof(float), hipMemcpyHostToDevice,
+                          c->stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(d_bd.get(), bd.data(), bd.size() * sizeof(double), hipMemcpyHostToDevice, c->stream)) !=
+          hipSuccess) {
     (void)hipStreamSynchronize(c->stream);
-    release();
-    (void)hipFree(dm);
     return hip_fail("mask build: device buffers", e);
   }
-  hipLaunchKernelGGL(k_build_masks, dim3(ncl, (nb + 255) / 256), dim3(256), 0, c->stream, d_ent, d_krig, d_bd, ncl,
-                     nb, Kf, dm);
+  hipLaunchKernelGGL(k_build_masks, dim3(ncl, (nb + 255) / 256), dim3(256), 0, c->stream, d_ent.get(), d_krig.get(),
+                     d_bd.get(), ncl, nb, Kf, dm.get());
   const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(c->stream);
-  release();
-  int rc = (e1 != hipSuccess || e2 != hipSuccess) ? hip_fail("k_build_masks", e1 != hipSuccess ? e1 : e2) : KDPT_OK;
-  if (!rc && !c->tn_dev) {
+  if (e1 != hipSuccess || e2 != hipSuccess) return hip_fail("k_build_masks", e1 != hipSuccess ? e1 : e2);
+  if (!c->masks.tn) {
     std::vector<float4> tn;
     build_entry_normals(cs, tn);
-    float4* d_tn = nullptr;
-    if ((rc = dupload(c, &d_tn, tn.data(), tn.size()))) dfree(c, d_tn);
-    else c->tn_dev = d_tn;
-  }
-  if (rc) {
-    (void)hipFree(dm);
-    return rc;
+    DeviceBuf<float4> d_tn;
+    if ((e = d_tn.alloc(tn.size())) != hipSuccess) return hip_fail("hipMalloc", e);
+    if (!tn.empty()) HIP_TRY(hipMemcpy(d_tn.get(), tn.data(), tn.size() * sizeof(float4), hipMemcpyHostToDevice));
+    c->masks.tn = std::move(d_tn);
   }
   // the swap: the previous table is freed before the call returns (the stream was drained above)
-  dfree(c, c->mask_dev);
-  c->allocs.push_back(dm);
-  c->mask_dev = dm;
-  c->mask_n = n;
-  c->mask_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  c->masks.dev = std::move(dm);
+  c->masks.n = n;
+  c->masks.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   apply_cull_route(c);
   return KDPT_OK;
 }
@@ -823,30 +821,25 @@ int check_fault(IterState* it, hipStream_t st) {
 
 // The solo state's next iteration into a scratch image and a scratch segment total (zeroed on the context's
 // stream), so that the accumulation image and stats.total_segments stay as they are; the scope's end puts the
-// state's targets back and frees the scratch buffers.
+// state's targets back, and the scratch buffer goes with the object.
 struct ScratchTargets {
   IterState& it;
   float* const image;
   unsigned long long* const total_segments;
-  void* scratch = nullptr;  // the image, then the total
+  DeviceBuf<char> scratch;  // the image, then the total
   explicit ScratchTargets(IterState& s) : it(s), image(s.image), total_segments(s.total_segments) {}
   int redirect(kdpt_ctx* c) {
     const size_t img = sizeof(float) * 3 * (size_t)c->npix;
-    HIP_TRY(hipMalloc(&scratch, img + sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(scratch, 0, img + sizeof(unsigned long long), c->stream));
-    it.image = static_cast<float*>(scratch);
-    it.total_segments = reinterpret_cast<unsigned long long*>(static_cast<char*>(scratch) + img);
+    HIP_TRY(scratch.alloc(img + sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(scratch.get(), 0, img + sizeof(unsigned long long), c->stream));
+    it.image = reinterpret_cast<float*>(scratch.get());
+    it.total_segments = reinterpret_cast<unsigned long long*>(scratch.get() + img);
     return KDPT_OK;
   }
-  ~ScratchTargets() {
+  ~ScratchTargets() {  // (hipFree, after this body, waits for whatever an early return left running)
     it.image = image;
     it.total_segments = total_segments;
-    if (scratch) (void)hipFree(scratch);  // (hipFree waits for whatever an early return left running)
   }
-};
-
-struct DeviceFree {
-  void operator()(void* p) const { (void)hipFree(p); }
 };
 
 }  // namespace
@@ -877,7 +870,6 @@ extern "C" {
 
 void kdpt_default_options(kdpt_options* o) { default_options(o); }
 
-
 int kdpt_create(const kdpt_scene* sc, const kdpt_options* opt, int device, kdpt_ctx** out) {
   const auto t_create = std::chrono::steady_clock::now();
   if (!sc || !out) return fail(KDPT_ERR_ARG, "null scene/out");
@@ -890,7 +882,8 @@ int kdpt_create(const kdpt_scene* sc, const kdpt_options* opt, int device, kdpt_
     if (prc) return fail(prc, err);
   }
   const kdpt_options& o = p.opt;
-  kdpt_ctx* c = new kdpt_ctx();
+  std::unique_ptr<kdpt_ctx, int (*)(kdpt_ctx*)> owner(new kdpt_ctx(), kdpt_destroy);  // (gone at an early return)
+  kdpt_ctx* const c = owner.get();
   c->shade_oob = p.shade_oob;
   c->device = device;
   c->opt = o;
@@ -902,28 +895,19 @@ int kdpt_create(const kdpt_scene* sc, const kdpt_options* opt, int device, kdpt_
   c->ntiles = (c->npix + TILE - 1) / TILE;
   c->cap = o.bounce_cap;
   c->nkeys = std::max(1, sc->num_materials);
-  auto bail = [&](int rc) {
-    kdpt_destroy(c);
-    return rc;
-  };
   int rc;
   hipError_t e;
-  if ((e = hipSetDevice(device)) != hipSuccess) return bail(hip_fail("hipSetDevice", e));
+  if ((e = hipSetDevice(device)) != hipSuccess) return hip_fail("hipSetDevice", e);
   c->cu_mask_streams = g_cu_mask_streams;
-  if ((rc = create_stream(c, &c->stream))) return bail(rc);
-  if ((e = hipEventCreateWithFlags(&c->entry_ev, hipEventDisableTiming)) != hipSuccess)
-    return bail(hip_fail("hipEventCreateWithFlags", e));
-  // the prepared arrays onto the device, DevScene pointed at them
-  auto up = [&](auto** d, const auto& v) { return dupload(c, d, v.data(), v.size()); };
+  if ((rc = create_stream(c, &c->stream))) return rc;
+  if ((e = c->pipe.entry_ev.create_untimed()) != hipSuccess) return hip_fail("hipEventCreateWithFlags", e);
+  // the prepared arrays onto the device, straight into the DevScene fields that point at them
+  auto up = [&](auto* field, const auto& v) { return dupload(c, field, v); };
   DevScene& S = c->S;
-  DevGeom* d_geoms;
-  DevMaterial* d_mats;
-  if ((rc = up(&d_geoms, p.geoms)) || (rc = up(&d_mats, p.materials))) return bail(rc);
-  S.geoms = d_geoms;
+  if ((rc = up(&S.geoms, p.geoms)) || (rc = up(&S.materials, p.materials))) return rc;
   S.num_geoms = p.num_geoms;
   S.num_boxes = p.num_boxes;
   c->viz = p.viz;
-  S.materials = d_mats;
   S.num_materials = sc->num_materials;
   S.has_obj = (p.kd || p.brute) ? 1 : 0;
   S.num_nodes = p.num_nodes;
@@ -937,82 +921,52 @@ int kdpt_create(const kdpt_scene* sc, const kdpt_options* opt, int device, kdpt_
   S.gc = p.gc;
   S.gh = p.gh;
   set_cull(c, p.cull);
-  if (p.kd || p.brute) {
-    float4 *dtv, *de1, *de2, *dn0, *dn1, *dn2;
-    if ((rc = up(&dtv, p.tri.tv0)) || (rc = up(&de1, p.tri.te1)) || (rc = up(&de2, p.tri.te2)) ||
-        (rc = up(&dn0, p.tri.tn0)) || (rc = up(&dn1, p.tri.tn1)) || (rc = up(&dn2, p.tri.tn2)))
-      return bail(rc);
-    S.tv0 = dtv;
-    S.te1 = de1;
-    S.te2 = de2;
-    S.tn0 = dn0;
-    S.tn1 = dn1;
-    S.tn2 = dn2;
-  }
+  if ((p.kd || p.brute) &&
+      ((rc = up(&S.tv0, p.tri.tv0)) || (rc = up(&S.te1, p.tri.te1)) || (rc = up(&S.te2, p.tri.te2)) ||
+       (rc = up(&S.tn0, p.tri.tn0)) || (rc = up(&S.tn1, p.tri.tn1)) || (rc = up(&S.tn2, p.tri.tn2))))
+    return rc;
   if (p.kd) {
     const ClusterSet& cs = p.clusters;
-    int4 *dnodes, *dpn = nullptr, *ddn = nullptr, *dsn = nullptr, *dsp;
-    int* doff;
-    int2 *dl, *di;
-    float4 *dlo, *dhi, *dv0, *dce1, *dce2, *dn, *du, *dv, *dw, *dsupn, *dsupb;
-    if ((rc = up(&dnodes, p.nodes)) || (rc = up(&doff, p.obj_material_offsets)) ||
-        (!p.pnodes.empty() && (rc = up(&dpn, p.pnodes))) || (!p.dnodes.empty() && (rc = up(&ddn, p.dnodes))) ||
-        (!p.snodes.empty() && (rc = up(&dsn, p.snodes))) ||
-        (rc = up(&dl, cs.leaf_cl)) || (rc = up(&di, cs.info)) || (rc = up(&dlo, cs.lo)) || (rc = up(&dhi, cs.hi)) ||
-        (rc = up(&dv0, cs.cv0)) || (rc = up(&dce1, cs.ce1)) || (rc = up(&dce2, cs.ce2)) ||
-        (rc = up(&dsp, cs.sup)) || (rc = up(&dn, cs.nrm)) || (rc = up(&du, cs.obb_u)) ||
-        (rc = up(&dv, cs.obb_v)) || (rc = up(&dw, cs.obb_w)) || (rc = up(&dsupn, cs.sup_n)) ||
-        (rc = up(&dsupb, cs.sup_b)))
-      return bail(rc);
-    S.nodes = dnodes;
-    S.pnodes = dpn;
-    S.dnodes = ddn;
-    S.snodes = dsn;
-    S.obj_material_offsets = doff;
-    S.leaf_cl = dl;
+    // (the packed, derived and super-cluster node records exist only where the tree is eligible: null otherwise)
+    if ((rc = up(&S.nodes, p.nodes)) || (rc = up(&S.obj_material_offsets, p.obj_material_offsets)) ||
+        (!p.pnodes.empty() && (rc = up(&S.pnodes, p.pnodes))) || (!p.dnodes.empty() && (rc = up(&S.dnodes, p.dnodes))) ||
+        (!p.snodes.empty() && (rc = up(&S.snodes, p.snodes))) ||
+        (rc = up(&S.leaf_cl, cs.leaf_cl)) || (rc = up(&S.cl_info, cs.info)) || (rc = up(&S.cl_lo, cs.lo)) ||
+        (rc = up(&S.cl_hi, cs.hi)) || (rc = up(&S.c_v0, cs.cv0)) || (rc = up(&S.c_e1, cs.ce1)) ||
+        (rc = up(&S.c_e2, cs.ce2)) || (rc = up(&S.sup, cs.sup)) || (rc = up(&S.cl_n, cs.nrm)) ||
+        (rc = up(&S.cl_u, cs.obb_u)) || (rc = up(&S.cl_v, cs.obb_v)) || (rc = up(&S.cl_w, cs.obb_w)) ||
+        (rc = up(&S.sup_n, cs.sup_n)) || (rc = up(&S.sup_b, cs.sup_b)))
+      return rc;
     S.num_clusters = (int)cs.info.size();
     S.cl_counts = p.cl_counts;
-    S.cl_info = di;
-    S.cl_lo = dlo;
-    S.cl_hi = dhi;
-    S.c_v0 = dv0;
-    S.c_e1 = dce1;
-    S.c_e2 = dce2;
-    S.sup = dsp;
     S.num_supers = p.num_supers;
-    S.cl_n = dn;
     S.cl_slab = 1;
-    S.cl_u = du;
-    S.cl_v = dv;
-    S.cl_w = dw;
     S.cl_obb = 1;
     S.flat_obb = 1;
-    S.sup_n = dsupn;
-    S.sup_b = dsupb;
     S.sup_slab = 1;
     // the masked one-level cull's direction masks, for the fast margin the box levels use
     if (p.wants_masks) {
-      c->mask_cs.reset(new ClusterSet(std::move(p.clusters)));
-      if ((rc = build_masks(c, dir_mask_resolution(S.num_clusters)))) return bail(rc);
+      c->masks.cs.reset(new ClusterSet(std::move(p.clusters)));
+      if ((rc = build_masks(c, dir_mask_resolution(S.num_clusters)))) return rc;
     }
   } else if (p.brute) {
-    if ((rc = up(&c->shapes, p.shapes)) || (rc = up(&c->chunk_lo, p.chunk_lo)) || (rc = up(&c->chunk_hi, p.chunk_hi)))
-      return bail(rc);
-    c->num_shapes = (int)p.shapes.size();
+    if ((rc = up(&c->bf.shapes, p.shapes)) || (rc = up(&c->bf.chunk_lo, p.chunk_lo)) ||
+        (rc = up(&c->bf.chunk_hi, p.chunk_hi)))
+      return rc;
+    c->bf.num_shapes = (int)p.shapes.size();
     c->brute = true;
-    c->chunk_k_min = HUGE_VALF;
-    for (const float4& q : p.chunk_lo) c->chunk_k_min = std::min(c->chunk_k_min, q.w);
+    c->bf.chunk_k_min = HUGE_VALF;
+    for (const float4& q : p.chunk_lo) c->bf.chunk_k_min = std::min(c->bf.chunk_k_min, q.w);
   }
   if (o.external_image) {
-    c->image = o.external_image;
-    c->image_external = true;
+    c->image = o.external_image;  // (the caller's: not owned)
   } else if ((rc = dalloc(c, &c->image, 3 * (size_t)c->npix))) {
-    return bail(rc);
+    return rc;
   }
   if ((rc = dalloc(c, &c->counters, 1)) || (rc = dalloc(c, &c->total_segments, 1)) ||
       (rc = dalloc(c, &c->trace_total, 3)))
-    return bail(rc);
-  if ((rc = alloc_iter(c, &c->solo, c->stream, false))) return bail(rc);
+    return rc;
+  if ((rc = alloc_iter(c, &c->solo, c->stream, false))) return rc;
   c->solo.image = c->image;
   // (the one-at-a-time launches and the ray queries report into the solo state's fault word; a pipelined
   // launch gets its own states' words, launch_batch)
@@ -1033,14 +987,14 @@ int kdpt_create(const kdpt_scene* sc, const kdpt_options* opt, int device, kdpt_
   // 5 798-5 802, C5 4 487 -> 4 544; 8 / 12 / 20 / 32 below 16, early_leaf 8 / 24 neutral; profiles/r05_ab_log.md)
   c->S.early_walk = 16;
   c->S.early_leaf = 1;
-  if ((rc = setup_trace(c))) return bail(rc);
+  if ((rc = setup_trace(c))) return rc;
   c->S.trip_limit = 8 * std::max(c->S.num_nodes, 1) + 64;
   // the scene's uploads (hipMemcpy) complete before any kernel of the context's non-blocking streams
-  if ((e = hipDeviceSynchronize()) != hipSuccess) return bail(hip_fail("hipDeviceSynchronize", e));
-  if ((rc = kdpt_reset(c))) return bail(rc);
-  c->reduce_spin_us = g_reduce_spin_us;
+  if ((e = hipDeviceSynchronize()) != hipSuccess) return hip_fail("hipDeviceSynchronize", e);
+  if ((rc = kdpt_reset(c))) return rc;
+  c->frames.reduce_spin_us = g_reduce_spin_us;
   c->create_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_create).count();
-  *out = c;
+  *out = owner.release();
   return KDPT_OK;
 }
 
@@ -1054,7 +1008,7 @@ int kdpt_set_options(kdpt_ctx* c, const kdpt_options* o) {
     return fail(KDPT_ERR_UNSUPPORTED, "enable_kd, viz_kd, use_bbox, bounce_cap, block_size and external_image "
                                       "are fixed at kdpt_create");
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->groups.empty()) {  // iterations in flight keep the options they were enqueued with
+  if (!c->pipe.groups.empty()) {  // iterations in flight keep the options they were enqueued with
     int rc = kdpt_synchronize(c);
     if (rc) return rc;
   }
@@ -1087,17 +1041,17 @@ int kdpt_set_tuning(kdpt_ctx* c, const char* name, double value) {
   if (!c) return fail(KDPT_ERR_ARG, "kdpt_set_tuning: null ctx, and no process-wide tuning knob is called " + k);
   if (k == "cast_chunk") {  // kdpt_cast_rays' chunk; its buffers are remade by the next call
     if (!(value >= 64.0 && value <= (double)(1 << 26))) return fail(KDPT_ERR_ARG, "cast_chunk must be in 64 .. 2^26");
-    c->cast_chunk = (int)value;
+    c->cast.chunk = (int)value;
     return KDPT_OK;
   }
   HIP_TRY(hipSetDevice(c->device));
   // queued iterations finish first: setup_trace and build_masks free and reallocate device memory their
   // kernels read.  The pipeline's states hold no knobs; they are still dropped, as include/kdpt.h documents
   // (the next kdpt_trace_iterations remakes them).
-  if (!c->groups.empty()) {
+  if (!c->pipe.groups.empty()) {
     int rc = kdpt_synchronize(c);
     if (rc) return rc;
-    drop_groups(c);
+    c->pipe.drop_groups();
   }
   const int v = (int)value;
   bool route = false;  // the knob can change the intersect kernel's route: setup_trace again
@@ -1158,11 +1112,11 @@ int kdpt_set_tuning(kdpt_ctx* c, const char* name, double value) {
     // the masked cull's box coefficient (default CULL_MARGIN_MASKED), its direction masks rebuilt for it: a
     // wider box sweeps more clusters, a narrower one leaves more danger triangles to decide
     if (!(value > 0.0 && value < 1.0)) return fail(KDPT_ERR_ARG, "cull_fast_k must be in (0, 1)");
-    if (!c->mask_cs) return fail(KDPT_ERR_ARG, "cull_fast_k: this scene has no direction masks");
+    if (!c->masks.cs) return fail(KDPT_ERR_ARG, "cull_fast_k: this scene has no direction masks");
     const CullMargin before = c->cull;
     c->cull.K = c->cull.K_lo = (float)value;
     if (c->cull_scene) set_cull(c, c->cull);
-    int rc = build_masks(c, c->mask_n);
+    int rc = build_masks(c, c->masks.n);
     if (rc) {  // the masks are still the old coefficient's: so is the margin again
       c->cull = before;
       if (c->cull_scene) set_cull(c, before);
@@ -1171,7 +1125,7 @@ int kdpt_set_tuning(kdpt_ctx* c, const char* name, double value) {
     cull = true;
   } else if (k == "cull_mask_n") {
     if (v < 1 || v > 512) return fail(KDPT_ERR_ARG, "cull_mask_n must be in 1 .. 512");
-    if (!c->mask_cs) return fail(KDPT_ERR_ARG, "cull_mask_n: this scene has no direction masks");
+    if (!c->masks.cs) return fail(KDPT_ERR_ARG, "cull_mask_n: this scene has no direction masks");
     int rc = build_masks(c, v);
     if (rc) return rc;
     cull = true;
@@ -1181,7 +1135,7 @@ int kdpt_set_tuning(kdpt_ctx* c, const char* name, double value) {
   } else if (k == "sync_debug") {
     c->sync_debug = v != 0;
   } else if (k == "reduce_spin_us") {
-    return set_reduce_spin(&c->reduce_spin_us, value);
+    return set_reduce_spin(&c->frames.reduce_spin_us, value);
   } else {
     return fail(KDPT_ERR_ARG, "unknown tuning knob " + k);
   }
@@ -1193,22 +1147,22 @@ int kdpt_set_tuning(kdpt_ctx* c, const char* name, double value) {
 int kdpt_reset(kdpt_ctx* c) {
   if (!c) return fail(KDPT_ERR_ARG, "null ctx");
   HIP_TRY(hipSetDevice(c->device));
-  for (auto& grp : c->groups) HIP_TRY(hipStreamSynchronize(grp.stream));
-  if (c->reduce_stream) HIP_TRY(hipStreamSynchronize(c->reduce_stream));
+  for (auto& grp : c->pipe.groups) HIP_TRY(hipStreamSynchronize(grp.stream));
+  if (c->frames.reduce_stream) HIP_TRY(hipStreamSynchronize(c->frames.reduce_stream));
   drain_intersect_events(c);
   c->intersect_ms_total = 0;
   c->intersect_launches_total = 0;
   HIP_TRY(hipMemsetAsync(c->image, 0, sizeof(float) * 3 * (size_t)c->npix, c->stream));
   HIP_TRY(hipMemsetAsync(c->total_segments, 0, sizeof(unsigned long long), c->stream));
   HIP_TRY(hipMemsetAsync(c->trace_total, 0, 3 * sizeof(unsigned long long), c->stream));
-  if (c->moments) HIP_TRY(hipMemsetAsync(c->mom_sumsq, 0, sizeof(float) * 3 * (size_t)c->npix, c->stream));
+  if (c->mom.on) HIP_TRY(hipMemsetAsync(c->mom.sumsq.get(), 0, sizeof(float) * 3 * (size_t)c->npix, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  c->mom_samples = 0;
+  c->mom.samples = 0;
   c->accumulated = false;
   memset(&c->stats, 0, sizeof c->stats);
   c->stats.intersect_grid_share = 1.0f;
-  c->cast_rays = c->cast_traced = 0;
-  c->cast_ms = 0;
+  c->cast.rays = c->cast.traced = 0;
+  c->cast.ms = 0;
   return KDPT_OK;
 }
 
@@ -1222,15 +1176,15 @@ int kdpt_synchronize(kdpt_ctx* c) {
   if (!c) return fail(KDPT_ERR_ARG, "null ctx");
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  for (auto& grp : c->groups) {
+  for (auto& grp : c->pipe.groups) {
     HIP_TRY(hipStreamSynchronize(grp.stream));
     for (auto& it : grp.its) {
       int rc = check_fault(it.get(), grp.stream);
       if (rc) return rc;
     }
   }
-  if (c->reduce_stream) HIP_TRY(hipStreamSynchronize(c->reduce_stream));
-  unregister_host(c);
+  if (c->frames.reduce_stream) HIP_TRY(hipStreamSynchronize(c->frames.reduce_stream));
+  c->frames.host_reg.clear();
   int rc = drain_intersect_events(c);
   if (rc) return rc;
   if (c->profile_batches) HIP_TRY(hipMemcpy(&c->last_profile, c->counters, sizeof(Counters), hipMemcpyDeviceToHost));
@@ -1246,9 +1200,9 @@ int kdpt_trace_iteration(kdpt_ctx* c, int frame, int iter) {
   int rc = accumulate_iteration(c, iter);
   if (rc) return rc;
   HIP_TRY(hipEventRecord(it.ev1, c->stream));
-  HIP_TRY(hipMemcpyAsync(it.h_counts, it.counts, sizeof(int) * (c->cap + 3), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(it.h_counts.get(), it.counts, sizeof(int) * (c->cap + 3), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (it.h_counts[c->cap + 2]) return fault_error(&it, c->stream, it.h_counts[c->cap + 2]);
+  if (it.h_counts.get()[c->cap + 2]) return fault_error(&it, c->stream, it.h_counts.get()[c->cap + 2]);
   float ms = 0;
   HIP_TRY(hipEventElapsedTime(&ms, it.ev0, it.ev1));
   c->stats.ms_last_iteration = ms;
@@ -1281,29 +1235,29 @@ int enqueue_iterations(kdpt_ctx* c, int first_iter, int count, int stride, int p
   const int B = std::min(MAXB, std::max(1, batch));
   // the first add follows everything already queued on the context's own stream (reset, ...); a wait of an
   // earlier call that is still queued keeps the record it was queued after
-  const hipEvent_t entry = c->entry_ev;
+  const hipEvent_t entry = c->pipe.entry_ev;
   HIP_TRY(hipEventRecord(entry, c->stream));
   // `depth` groups of B iteration states; a group runs one batch at a time on its stream
-  if ((int)c->groups.size() < depth || c->group_batch != B) {
-    if (!c->groups.empty()) {
+  if ((int)c->pipe.groups.size() < depth || c->pipe.batch != B) {
+    if (!c->pipe.groups.empty()) {
       int rc = kdpt_synchronize(c);
       if (rc) return rc;
-      drop_groups(c);
+      c->pipe.drop_groups();
     }
-    c->group_batch = B;
-    c->next_group = 0;
+    c->pipe.batch = B;
+    c->pipe.next = 0;
     // One stream per group, created one after another in group order: HIP maps streams onto its hardware
     // queues (GPU_MAX_HW_QUEUES) in creation order, reusing the least-used queue once all exist, so a stream per
     // iteration state (8 x 4) had put pairs of groups -- two batches' chains -- on one in-order queue.
-    while ((int)c->groups.size() < depth) {
+    while ((int)c->pipe.groups.size() < depth) {
       int rc = make_group(c, B);
       if (rc) {
-        drop_groups(c);
+        c->pipe.drop_groups();
         return rc;
       }
     }
   }
-  const int ngroups = (int)c->groups.size();
+  const int ngroups = (int)c->pipe.groups.size();
   // With several batches in flight each intersect launch gets a share of the chip (2/depth of the
   // persistent grid, all of it for depth <= 2, a quarter from depth 8 on): a launch's length is set by its
   // heaviest rays, so concurrent launches on disjoint CU subsets overlap those tails instead of queueing
@@ -1318,9 +1272,9 @@ int enqueue_iterations(kdpt_ctx* c, int first_iter, int count, int stride, int p
     const int nb = std::min(B, count - kb);
     // groups in turn, continuing across calls: kdpt_render_frames queues one call per frame, and a frame
     // shorter than the pipeline must not restart at group 0 (it would wait on that group's previous batch)
-    const int g = c->next_group % ngroups;
-    c->next_group = (g + 1) % ngroups;
-    IterGroup& grp = c->groups[g];
+    const int g = c->pipe.next % ngroups;
+    c->pipe.next = (g + 1) % ngroups;
+    IterGroup& grp = c->pipe.groups[g];
     hipStream_t st = grp.stream;
     // (the group's previous batch's partial images were added on this stream, before this batch's camera rays
     // clear them)
@@ -1330,26 +1284,26 @@ int enqueue_iterations(kdpt_ctx* c, int first_iter, int count, int stride, int p
       iters[b] = first_iter + (kb + b) * stride;
       its[b] = grp.its[b].get();
     }
-    std::vector<hipEvent_t>* bev = nullptr;
+    std::vector<Event>* bev = nullptr;
     if (c->opt.testing_mode) {
-      std::vector<hipEvent_t> evs;
+      std::vector<Event> evs;
       for (int e = 0; e < 2 * c->cap; e++) {
-        hipEvent_t ev;
-        if (!c->free_ev.empty()) { ev = c->free_ev.back(); c->free_ev.pop_back(); }
-        else HIP_TRY(hipEventCreate(&ev));
-        evs.push_back(ev);
+        Event ev;
+        if (!c->pipe.free_ev.empty()) { ev = std::move(c->pipe.free_ev.back()); c->pipe.free_ev.pop_back(); }
+        else HIP_TRY(ev.create());
+        evs.push_back(std::move(ev));
       }
-      c->pending_ev.push_back(evs);
-      bev = &c->pending_ev.back();
+      c->pipe.pending_ev.push_back(std::move(evs));
+      bev = &c->pipe.pending_ev.back();
     }
     int rc = launch_batch(c, its, iters, nb, st, trace_grid, -1, c->profile_batches, bev);
     if (rc) return rc;
     // the add: after the previous add (the chain), and for the call's first batch after the context's stream,
     // the frames' image adds (when the target is the image) and the target's zeroing
-    if (c->acc_last) HIP_TRY(hipStreamWaitEvent(st, c->acc_last, 0));
+    if (c->pipe.acc_last) HIP_TRY(hipStreamWaitEvent(st, c->pipe.acc_last, 0));
     if (first) {
       HIP_TRY(hipStreamWaitEvent(st, entry, 0));
-      if (c->img_last && target == c->image) HIP_TRY(hipStreamWaitEvent(st, c->img_last, 0));
+      if (c->pipe.img_last && target == c->image) HIP_TRY(hipStreamWaitEvent(st, c->pipe.img_last, 0));
       if (zero_after) {
         HIP_TRY(hipStreamWaitEvent(st, zero_after, 0));
         HIP_TRY(hipMemsetAsync(target, 0, sizeof(float) * 3 * (size_t)c->npix, st));
@@ -1360,10 +1314,10 @@ int enqueue_iterations(kdpt_ctx* c, int first_iter, int count, int stride, int p
     for (int b = 0; b < nb; b++) partials[b] = its[b]->image;  // in iteration order
     if ((rc = launch_accumulate(c, target, partials, nb, st))) return rc;
     HIP_TRY(hipEventRecord(grp.acc_ev, st));
-    c->acc_last = grp.acc_ev;
+    c->pipe.acc_last = grp.acc_ev;
     if (target == c->image) {
       c->accumulated = true;
-      if (c->moments) c->mom_samples += nb;
+      if (c->mom.on) c->mom.samples += nb;
     }
   }
   c->stats.iterations += count;
@@ -1407,7 +1361,7 @@ int kdpt_cull_margin(kdpt_ctx* c, float* margin, double* rigorous, int* exact) {
   if (!c) return fail(KDPT_ERR_ARG, "null ctx");
   if (c->brute && c->cull_scene) {
     // the chunk cull: every chunk at its own rigorous coefficient (the smallest is reported; +inf: no chunk culls)
-    if (margin) *margin = c->chunk_k_min;
+    if (margin) *margin = c->bf.chunk_k_min;
     if (rigorous) *rigorous = c->cull.rigorous;
     if (exact) *exact = 1;
     return KDPT_OK;
@@ -1428,14 +1382,11 @@ int kdpt_write_pbo(kdpt_ctx* c, int iter, uint8_t* rgba) {
   // The reference's pbo is the GL-mapped device buffer (src/main.cpp runCuda); a headless caller passes host
   // memory.  Memory of this context's device is written by the kernel directly; anything else (host memory,
   // another device's buffer) through the context's staging buffer and a copy.
-  hipPointerAttribute_t attr{};
-  const bool on_device = hipPointerGetAttributes(&attr, rgba) == hipSuccess && attr.type == hipMemoryTypeDevice &&
-                         attr.device == c->device;
-  (void)hipGetLastError();  // a plain host pointer is an error for hipPointerGetAttributes on some runtimes
+  const bool on_device = on_context_device(c, rgba);
   uchar4* d = reinterpret_cast<uchar4*>(rgba);
   if (!on_device) {
-    if (!c->pbo_staging) HIP_TRY(hipMalloc((void**)&c->pbo_staging, sizeof(uchar4) * (size_t)c->npix));
-    d = c->pbo_staging;
+    if (!c->pbo_staging) HIP_TRY(c->pbo_staging.alloc((size_t)c->npix));
+    d = c->pbo_staging.get();
   }
   hipLaunchKernelGGL(k_pbo, dim3((c->npix + 255) / 256), dim3(256), 0, c->stream, c->image, c->npix, iter, d);
   HIP_TRY(hipGetLastError());
@@ -1448,26 +1399,20 @@ int kdpt_write_pbo(kdpt_ctx* c, int iter, uint8_t* rgba) {
 // The saveImage pixel pass on the device; rgb (host, 3*W*H) and/or lin (host, 3*W*H floats).
 static int save_image_pass(kdpt_ctx* c, float samples, uint8_t* rgb, float* lin) {
   HIP_TRY(hipSetDevice(c->device));
-  for (auto& grp : c->groups) HIP_TRY(hipStreamSynchronize(grp.stream));
-  if (c->reduce_stream) HIP_TRY(hipStreamSynchronize(c->reduce_stream));
+  for (auto& grp : c->pipe.groups) HIP_TRY(hipStreamSynchronize(grp.stream));
+  if (c->frames.reduce_stream) HIP_TRY(hipStreamSynchronize(c->frames.reduce_stream));
   const size_t n3 = 3 * (size_t)c->npix;
-  uint8_t* d_rgb = nullptr;
-  float* d_lin = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_rgb, n3));
-  hipError_t e = lin ? hipMalloc((void**)&d_lin, n3 * sizeof(float)) : hipSuccess;
-  if (e != hipSuccess) {
-    (void)hipFree(d_rgb);
-    return hip_fail("save image: hipMalloc", e);
-  }
+  DeviceBuf<uint8_t> d_rgb;
+  DeviceBuf<float> d_lin;  // (null without `lin`)
+  HIP_TRY(d_rgb.alloc(n3));
+  if (lin) HIP_TRY(d_lin.alloc(n3));
   hipLaunchKernelGGL(k_save_image, dim3((c->npix + 255) / 256), dim3(256), 0, c->stream, c->image, c->W, c->H,
-                     samples, d_rgb, d_lin);
-  e = hipGetLastError();
-  if (e == hipSuccess && rgb) e = hipMemcpyAsync(rgb, d_rgb, n3, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess && lin) e = hipMemcpyAsync(lin, d_lin, n3 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d_rgb);
-  if (d_lin) (void)hipFree(d_lin);
-  return e == hipSuccess ? KDPT_OK : hip_fail("save image", e);
+                     samples, d_rgb.get(), d_lin.get());
+  HIP_TRY(hipGetLastError());
+  if (rgb) HIP_TRY(hipMemcpyAsync(rgb, d_rgb.get(), n3, hipMemcpyDeviceToHost, c->stream));
+  if (lin) HIP_TRY(hipMemcpyAsync(lin, d_lin.get(), n3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return KDPT_OK;
 }
 
 int kdpt_save_rgb8(kdpt_ctx* c, float samples, uint8_t* rgb) {
@@ -1494,13 +1439,13 @@ int kdpt_save_hdr(kdpt_ctx* c, const char* path, float samples) {
 int kdpt_cull_masks(kdpt_ctx* c, int* mask_n, int* num_clusters, unsigned long long* masks) {
   if (!c || !mask_n || !num_clusters) return fail(KDPT_ERR_ARG, "null arg");
   HIP_TRY(hipSetDevice(c->device));
-  *mask_n = c->mask_dev ? c->mask_n : 0;
+  *mask_n = c->masks.dev ? c->masks.n : 0;
   *num_clusters = c->S.num_clusters;
-  if (!c->mask_dev) return KDPT_OK;
-  const size_t cells = 6 * (size_t)c->mask_n * c->mask_n * (size_t)c->S.num_clusters;
+  if (!c->masks.dev) return KDPT_OK;
+  const size_t cells = 6 * (size_t)c->masks.n * c->masks.n * (size_t)c->S.num_clusters;
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (masks)
-    HIP_TRY(hipMemcpyAsync(masks, c->mask_dev, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(masks, c->masks.dev.get(), cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return KDPT_OK;
 }
@@ -1519,7 +1464,7 @@ int kdpt_get_stats(kdpt_ctx* c, kdpt_stats* st) {
   c->stats.intersect_ms_total = c->intersect_ms_total;
   c->stats.intersect_launches_total = c->intersect_launches_total;
   c->stats.create_ms = c->create_ms;
-  c->stats.mask_build_ms = c->mask_build_ms;
+  c->stats.mask_build_ms = c->masks.build_ms;
   *st = c->stats;
   return KDPT_OK;
 }
@@ -1530,36 +1475,6 @@ int kdpt_image_device_ptr(kdpt_ctx* c, void** p) {
   return KDPT_OK;
 }
 
-int kdpt_destroy(kdpt_ctx* c) {
-  if (!c) return KDPT_OK;
-  (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  drop_groups(c);  // (each group's stream drained first)
-  for (auto& evs : c->pending_ev)
-    for (auto e : evs) (void)hipEventDestroy(e);
-  for (auto e : c->free_ev) (void)hipEventDestroy(e);
-  // (a kdpt_render_frames that failed partway may have left a reduce queued: drain it before the communicator
-  // and the frame buffers go)
-  if (c->reduce_stream) (void)hipStreamSynchronize(c->reduce_stream);
-  release_comm(c);
-  unregister_host(c);
-  for (auto e : c->frame_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (c->reduce_stream) (void)hipStreamDestroy(c->reduce_stream);
-  for (void* p : c->allocs) (void)hipFree(p);
-  if (c->pbo_staging) (void)hipFree(c->pbo_staging);
-  free_moments(c);
-  free_cast_buffers(c);
-  for (auto e : c->cast_ev)
-    if (e) (void)hipEventDestroy(e);
-  free_iter(&c->solo);
-  free_iter(&c->query);  // (its image, staging buffer and totals were among c->allocs)
-  if (c->entry_ev) (void)hipEventDestroy(c->entry_ev);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
-  return KDPT_OK;
-}
-
 int kdpt_debug_paths(kdpt_ctx* c, int iter, int stop_depth, kdpt_path_segment* out, int* npaths) {
   if (!c || !out || stop_depth < 0 || stop_depth >= c->cap) return fail(KDPT_ERR_ARG, "bad arg");
   HIP_TRY(hipSetDevice(c->device));
@@ -1567,19 +1482,18 @@ int kdpt_debug_paths(kdpt_ctx* c, int iter, int stop_depth, kdpt_path_segment* o
   ScratchTargets targets(it);
   int rc = targets.redirect(c);
   if (rc || (rc = launch_iteration(c, iter, stop_depth, false))) return rc;
-  kdpt_path_segment* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, sizeof(kdpt_path_segment) * (size_t)c->npix));
-  std::unique_ptr<void, DeviceFree> d_owner(d);
+  DeviceBuf<kdpt_path_segment> d;
+  HIP_TRY(d.alloc((size_t)c->npix));
   const int depth_slot = stop_depth + 1;
   hipLaunchKernelGGL(k_unpack, dim3((c->npix + 255) / 256), dim3(256), 0, c->stream, it.buf[it.cur], it.counts,
-                     depth_slot, d);
+                     depth_slot, d.get());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(it.h_counts, it.counts, sizeof(int) * (c->cap + 2), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(it.h_counts.get(), it.counts, sizeof(int) * (c->cap + 2), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   if ((rc = check_fault(&it, c->stream))) return rc;
-  const int n = it.h_counts[depth_slot];
+  const int n = it.h_counts.get()[depth_slot];
   *npaths = n;
-  HIP_TRY(hipMemcpy(out, d, sizeof(kdpt_path_segment) * (size_t)n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out, d.get(), sizeof(kdpt_path_segment) * (size_t)n, hipMemcpyDeviceToHost));
   return KDPT_OK;
 }
 
@@ -1596,7 +1510,7 @@ int kdpt_count_iteration(kdpt_ctx* c, int iter, unsigned long long* aabb_tri_hit
   Counters h{};
   if (!rc) {
     HIP_TRY(hipMemcpyAsync(&h, c->counters, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(it.h_counts, it.counts, sizeof(int) * (c->cap + 3), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(it.h_counts.get(), it.counts, sizeof(int) * (c->cap + 3), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     segments_from_counts(c);  // stats.segments / seg_per_bounce now describe the counting iteration
     rc = check_fault(&it, c->stream);
@@ -1632,57 +1546,53 @@ int kdpt_wave_profile(kdpt_ctx* c, unsigned long long* out, int n) {
 }
 
 int kdpt_selftest_math(const float* x, int n, float* so, float* co) {
-  float *dx, *ds, *dc;
-  HIP_TRY(hipMalloc((void**)&dx, sizeof(float) * n));
-  HIP_TRY(hipMalloc((void**)&ds, sizeof(float) * n));
-  HIP_TRY(hipMalloc((void**)&dc, sizeof(float) * n));
-  HIP_TRY(hipMemcpy(dx, x, sizeof(float) * n, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_selftest_math, dim3((n + 255) / 256), dim3(256), 0, 0, dx, n, ds, dc);
+  DeviceBuf<float> dx, ds, dc;
+  HIP_TRY(dx.alloc(n));
+  HIP_TRY(ds.alloc(n));
+  HIP_TRY(dc.alloc(n));
+  HIP_TRY(hipMemcpy(dx.get(), x, sizeof(float) * n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_selftest_math, dim3((n + 255) / 256), dim3(256), 0, 0, dx.get(), n, ds.get(), dc.get());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(so, ds, sizeof(float) * n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(co, dc, sizeof(float) * n, hipMemcpyDeviceToHost));
-  (void)hipFree(dx); (void)hipFree(ds); (void)hipFree(dc);
+  HIP_TRY(hipMemcpy(so, ds.get(), sizeof(float) * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(co, dc.get(), sizeof(float) * n, hipMemcpyDeviceToHost));
   return KDPT_OK;
 }
 
 int kdpt_selftest_libm(int fn, const float* x, int n, double* out) {
   if (fn < 0 || fn > 2 || n < 0 || (n && (!x || !out))) return fail(KDPT_ERR_ARG, "kdpt_selftest_libm: bad arguments");
   if (n == 0) return KDPT_OK;
-  float* dx;
-  double* dout;
-  HIP_TRY(hipMalloc((void**)&dx, sizeof(float) * n));
-  HIP_TRY(hipMalloc((void**)&dout, sizeof(double) * n));
-  HIP_TRY(hipMemcpy(dx, x, sizeof(float) * n, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_selftest_libm, dim3((n + 255) / 256), dim3(256), 0, 0, fn, dx, n, dout);
+  DeviceBuf<float> dx;
+  DeviceBuf<double> dout;
+  HIP_TRY(dx.alloc(n));
+  HIP_TRY(dout.alloc(n));
+  HIP_TRY(hipMemcpy(dx.get(), x, sizeof(float) * n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_selftest_libm, dim3((n + 255) / 256), dim3(256), 0, 0, fn, dx.get(), n, dout.get());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost));
-  (void)hipFree(dx); (void)hipFree(dout);
+  HIP_TRY(hipMemcpy(out, dout.get(), sizeof(double) * n, hipMemcpyDeviceToHost));
   return KDPT_OK;
 }
 
 int kdpt_selftest_libm_digest(int fn, uint32_t first, unsigned long long count, unsigned long long* digest) {
   if (fn < 0 || fn > 2 || !digest || count > (1ull << 32) || first + count > (1ull << 32))
     return fail(KDPT_ERR_ARG, "kdpt_selftest_libm_digest: bad arguments");
-  unsigned long long* dacc;
-  HIP_TRY(hipMalloc((void**)&dacc, sizeof(unsigned long long)));
-  HIP_TRY(hipMemset(dacc, 0, sizeof(unsigned long long)));
-  hipLaunchKernelGGL(k_selftest_libm_digest, dim3(4096), dim3(256), 0, 0, fn, first, (uint64_t)count, dacc);
+  DeviceBuf<unsigned long long> dacc;
+  HIP_TRY(dacc.alloc(1));
+  HIP_TRY(hipMemset(dacc.get(), 0, sizeof(unsigned long long)));
+  hipLaunchKernelGGL(k_selftest_libm_digest, dim3(4096), dim3(256), 0, 0, fn, first, (uint64_t)count, dacc.get());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(digest, dacc, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  (void)hipFree(dacc);
+  HIP_TRY(hipMemcpy(digest, dacc.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return KDPT_OK;
 }
 
 int kdpt_selftest_rng(const int* iid, int n, int k, float* u) {
-  int* di;
-  float* du;
-  HIP_TRY(hipMalloc((void**)&di, sizeof(int) * 3 * n));
-  HIP_TRY(hipMalloc((void**)&du, sizeof(float) * n));
-  HIP_TRY(hipMemcpy(di, iid, sizeof(int) * 3 * n, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_selftest_rng, dim3((n + 255) / 256), dim3(256), 0, 0, di, n, k, du);
+  DeviceBuf<int> di;
+  DeviceBuf<float> du;
+  HIP_TRY(di.alloc(3 * (size_t)n));
+  HIP_TRY(du.alloc(n));
+  HIP_TRY(hipMemcpy(di.get(), iid, sizeof(int) * 3 * n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_selftest_rng, dim3((n + 255) / 256), dim3(256), 0, 0, di.get(), n, k, du.get());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(u, du, sizeof(float) * n, hipMemcpyDeviceToHost));
-  (void)hipFree(di); (void)hipFree(du);
+  HIP_TRY(hipMemcpy(u, du.get(), sizeof(float) * n, hipMemcpyDeviceToHost));
   return KDPT_OK;
 }
 
@@ -1691,49 +1601,41 @@ int kdpt_selftest_rng_draws(int mode, const uint32_t* in, int n, int k, float* o
     return fail(KDPT_ERR_ARG, "bad rng selftest arguments");
   if (!n || !k) return KDPT_OK;
   const size_t nin = (size_t)n * (mode == 0 ? 3 : 1), nout = (size_t)n * k;
-  uint32_t* di;
-  float* dout;
-  HIP_TRY(hipMalloc((void**)&di, sizeof(uint32_t) * nin));
-  if (const hipError_t e = hipMalloc((void**)&dout, sizeof(float) * nout)) {
-    (void)hipFree(di);
-    return hip_fail("rng selftest: hipMalloc", e);
-  }
-  hipError_t e = hipMemcpy(di, in, sizeof(uint32_t) * nin, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_selftest_rng_draws, dim3((n + 255) / 256), dim3(256), 0, 0, mode, di, n, k, dout);
-    if ((e = hipGetLastError()) == hipSuccess) e = hipMemcpy(out, dout, sizeof(float) * nout, hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(di);
-  (void)hipFree(dout);
-  return e == hipSuccess ? KDPT_OK : hip_fail("rng selftest", e);
+  DeviceBuf<uint32_t> di;
+  DeviceBuf<float> dout;
+  HIP_TRY(di.alloc(nin));
+  HIP_TRY(dout.alloc(nout));
+  HIP_TRY(hipMemcpy(di.get(), in, sizeof(uint32_t) * nin, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_selftest_rng_draws, dim3((n + 255) / 256), dim3(256), 0, 0, mode, di.get(), n, k, dout.get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, dout.get(), sizeof(float) * nout, hipMemcpyDeviceToHost));
+  return KDPT_OK;
 }
 
 int kdpt_selftest_glm(int fn, const float* in, int n, float* out) {
   const int ni = glm_kat_inputs(fn), no = glm_kat_outputs(fn);
   if (!ni || n < 0 || (n && (!in || !out))) return fail(KDPT_ERR_ARG, "bad glm selftest arguments");
   if (!n) return KDPT_OK;
-  float *din, *dout;
-  HIP_TRY(hipMalloc((void**)&din, sizeof(float) * ni * (size_t)n));
-  HIP_TRY(hipMalloc((void**)&dout, sizeof(float) * no * (size_t)n));
-  HIP_TRY(hipMemcpy(din, in, sizeof(float) * ni * (size_t)n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dout, out, sizeof(float) * no * (size_t)n, hipMemcpyHostToDevice));  // sentinels
-  hipLaunchKernelGGL(k_selftest_glm, dim3((n + 255) / 256), dim3(256), 0, 0, fn, din, n, dout);
+  DeviceBuf<float> din, dout;
+  HIP_TRY(din.alloc(ni * (size_t)n));
+  HIP_TRY(dout.alloc(no * (size_t)n));
+  HIP_TRY(hipMemcpy(din.get(), in, sizeof(float) * ni * (size_t)n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dout.get(), out, sizeof(float) * no * (size_t)n, hipMemcpyHostToDevice));  // sentinels
+  hipLaunchKernelGGL(k_selftest_glm, dim3((n + 255) / 256), dim3(256), 0, 0, fn, din.get(), n, dout.get());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, dout, sizeof(float) * no * (size_t)n, hipMemcpyDeviceToHost));
-  (void)hipFree(din); (void)hipFree(dout);
+  HIP_TRY(hipMemcpy(out, dout.get(), sizeof(float) * no * (size_t)n, hipMemcpyDeviceToHost));
   return KDPT_OK;
 }
 
 int kdpt_selftest_fresnel(const float* cs, int n, float ior, float* f) {
-  float *dc, *df;
-  HIP_TRY(hipMalloc((void**)&dc, sizeof(float) * n));
-  HIP_TRY(hipMalloc((void**)&df, sizeof(float) * n));
-  HIP_TRY(hipMemcpy(dc, cs, sizeof(float) * n, hipMemcpyHostToDevice));
+  DeviceBuf<float> dc, df;
+  HIP_TRY(dc.alloc(n));
+  HIP_TRY(df.alloc(n));
+  HIP_TRY(hipMemcpy(dc.get(), cs, sizeof(float) * n, hipMemcpyHostToDevice));
   float rr = (1.0f - ior) / (1.0f + ior);
-  hipLaunchKernelGGL(k_selftest_fresnel, dim3((n + 255) / 256), dim3(256), 0, 0, dc, n, rr * rr, df);
+  hipLaunchKernelGGL(k_selftest_fresnel, dim3((n + 255) / 256), dim3(256), 0, 0, dc.get(), n, rr * rr, df.get());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(f, df, sizeof(float) * n, hipMemcpyDeviceToHost));
-  (void)hipFree(dc); (void)hipFree(df);
+  HIP_TRY(hipMemcpy(f, df.get(), sizeof(float) * n, hipMemcpyDeviceToHost));
   return KDPT_OK;
 }
 
@@ -1828,17 +1730,17 @@ int brute_stage(const Batch& B, int depth) {
   const BruteKernel kernel = brute_kernel(c->opt.use_bbox != 0, B.count);
   for (int b = 0; b < B.nb; b++) {
     IterState* it = B.its[b];
-    const BruteArgs ba{scene_of(c, it), it->buf[it->cur], it->counts, depth, it->hits, c->shapes, c->num_shapes,
-                       c->chunk_lo, c->chunk_hi, c->cull_scene ? 0.0f : c->S.cl_margin, c->counters,
+    const BruteArgs ba{scene_of(c, it), it->buf[it->cur], it->counts, depth, it->hits, c->bf.shapes, c->bf.num_shapes,
+                       c->bf.chunk_lo, c->bf.chunk_hi, c->cull_scene ? 0.0f : c->S.cl_margin, c->counters,
                        B.its[0]->trace_t};
     hipLaunchKernelGGL(kernel, dim3(c->ntiles), dim3(TILE), 0, B.st, ba);
     HIP_TRY(hipGetLastError());
     if (c->sync_debug) {
       BruteShape h0;
       HIP_TRY(hipStreamSynchronize(B.st));  // (the null-stream copy below does not order after st)
-      HIP_TRY(hipMemcpy(&h0, c->shapes, sizeof h0, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(&h0, c->bf.shapes, sizeof h0, hipMemcpyDeviceToHost));
       fprintf(stderr, "[kdpt] brute depth %d use_bbox %d shapes %d lo %g %g %g hi %g %g %g n %d mat %d\n", depth,
-              c->opt.use_bbox, c->num_shapes, h0.lo.x, h0.lo.y, h0.lo.z, h0.hi.x, h0.hi.y, h0.hi.z, fbits(h0.lo.w),
+              c->opt.use_bbox, c->bf.num_shapes, h0.lo.x, h0.lo.y, h0.lo.z, h0.hi.x, h0.hi.y, h0.hi.z, fbits(h0.lo.w),
               fbits(h0.hi.w));
     }
   }
@@ -1962,7 +1864,7 @@ int shade_stage(const Batch& B, int depth, bool prep_next) {
 // them, then each one's shading and compaction.  The iterations stay independent: only the intersect launch is
 // shared.
 int launch_batch(kdpt_ctx* c, IterState* const* its, const int* iters, int nb, hipStream_t st, int trace_grid,
-                 int stop_depth, bool count, std::vector<hipEvent_t>* bev, const RaySource* rays) {
+                 int stop_depth, bool count, std::vector<Event>* bev, const RaySource* rays) {
   if (c->shade_oob) return refuse_shading();
   const bool kd = !c->brute && !c->viz;
   Batch B{c, its, iters, nb, st, trace_grid, count, scene_of(c, its[0]), c->gen_geoms && kd, c->opt.compaction != 0,
@@ -1982,7 +1884,7 @@ int launch_batch(kdpt_ctx* c, IterState* const* its, const int* iters, int nb, h
   bool prep_ready = false;  // this bounce's intersect-stage first part came with the previous bounce's shading
   for (int depth = 0; depth < c->cap; depth++) {
     const bool prep_next = B.compact && depth + 1 < c->cap && kd;
-    if (timed) HIP_TRY(hipEventRecord((*bev)[2 * depth], st));
+    if (timed) HIP_TRY(hipEventRecord((*bev)[2 * depth].get(), st));
     if ((rc = intersect_stage(B, depth, prep_ready))) return rc;
     if (c->sync_debug) {
       fprintf(stderr, "[kdpt] trace depth %d launched (grid %d, mode %d, lds %zu, batch %d)\n", depth,
@@ -1990,7 +1892,7 @@ int launch_batch(kdpt_ctx* c, IterState* const* its, const int* iters, int nb, h
       HIP_TRY(hipStreamSynchronize(st));
       fprintf(stderr, "[kdpt] trace depth %d done\n", depth);
     }
-    if (timed) HIP_TRY(hipEventRecord((*bev)[2 * depth + 1], st));
+    if (timed) HIP_TRY(hipEventRecord((*bev)[2 * depth + 1].get(), st));
     if ((rc = shade_stage(B, depth, prep_next))) return rc;
     if (c->sync_debug) {
       HIP_TRY(hipStreamSynchronize(st));
@@ -2026,10 +1928,10 @@ int accumulate_iteration(kdpt_ctx* c, int iter) {
   int rc = launch_iteration(c, iter, -1, false);
   if (rc) return rc;
   c->accumulated = true;
-  if (!c->moments) return KDPT_OK;
-  const float* partial = c->mom_partial;
+  if (!c->mom.on) return KDPT_OK;
+  const float* partial = c->mom.partial.get();
   if ((rc = launch_accumulate(c, c->image, &partial, 1, c->stream))) return rc;
-  c->mom_samples++;
+  c->mom.samples++;
   return KDPT_OK;
 }
 
@@ -2114,40 +2016,34 @@ __global__ void k_spin(unsigned long long ticks) {
 }
 
 int reduce_spin(kdpt_ctx* c, hipStream_t st) {
-  if (!(c->reduce_spin_us > 0)) return KDPT_OK;
-  const unsigned long long ticks = (unsigned long long)(c->reduce_spin_us * c->wall_khz / 1000.0);
+  if (!(c->frames.reduce_spin_us > 0)) return KDPT_OK;
+  const unsigned long long ticks = (unsigned long long)(c->frames.reduce_spin_us * c->wall_khz / 1000.0);
   hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, st, ticks);
   HIP_TRY(hipGetLastError());
   return KDPT_OK;
 }
 
 void release_comm(kdpt_ctx* c) {
-  const Rccl* R = c->comm && c->owns_comm ? rccl() : nullptr;
-  if (R) (void)R->commDestroy((ncclComm_t)c->comm);
-  c->comm = nullptr;
-  c->owns_comm = false;
-}
-
-void unregister_host(kdpt_ctx* c) {
-  for (void* p : c->host_reg) (void)hipHostUnregister(p);
-  c->host_reg.clear();
+  const Rccl* R = c->frames.comm && c->frames.owns_comm ? rccl() : nullptr;
+  if (R) (void)R->commDestroy((ncclComm_t)c->frames.comm);
+  c->frames.comm = nullptr;
+  c->frames.owns_comm = false;
 }
 
 int frame_buffers(kdpt_ctx* c) {
   const size_t n3 = 3 * (size_t)c->npix;
-  if (!c->reduce_stream) {
-    int rc = create_stream(c, &c->reduce_stream);
+  if (!c->frames.reduce_stream) {
+    int rc = create_stream(c, &c->frames.reduce_stream);
     if (rc) return rc;
   }
   for (int k = 0; k < 2; k++) {
-    if (!c->frame_buf[k]) {
-      int rc = dalloc(c, &c->frame_buf[k], n3);
-      if (rc) return rc;
-      HIP_TRY(hipEventCreateWithFlags(&c->frame_ev[k], hipEventDisableTiming));
-      HIP_TRY(hipEventRecord(c->frame_ev[k], c->stream));
+    if (!c->frames.buf[k]) {
+      HIP_TRY(c->frames.buf[k].alloc(n3));
+      HIP_TRY(c->frames.ev[k].create_untimed());
+      HIP_TRY(hipEventRecord(c->frames.ev[k], c->stream));
     }
   }
-  if (!c->frame_sum && c->rank == 0) return dalloc(c, &c->frame_sum, n3);
+  if (!c->frames.sum && c->frames.rank == 0) HIP_TRY(c->frames.sum.alloc(n3));
   return KDPT_OK;
 }
 
@@ -2159,8 +2055,7 @@ void pin_host_out(kdpt_ctx* c, void* p, size_t bytes) {
   hipPointerAttribute_t a;
   if (hipPointerGetAttributes(&a, p) == hipSuccess && a.type != hipMemoryTypeUnregistered) return;
   (void)hipGetLastError();
-  if (hipHostRegister(p, bytes, hipHostRegisterDefault) == hipSuccess) c->host_reg.push_back(p);
-  else (void)hipGetLastError();
+  if (c->frames.host_reg.add(p, bytes) != hipSuccess) (void)hipGetLastError();
 }
 
 // Iterations of frame f for rank r of n: first, stride n, count.
@@ -2170,19 +2065,19 @@ void frame_share(int f, int spp, int n, int r, int* first, int* count) {
 }
 
 // Queue frame f's share of this rank into frame_buf[f & 1] (zeroed first, after its previous reduce), and make
-// the reduce stream wait for it: the share's last add (c->acc_last), or, for a rank with no iterations in the
+// the reduce stream wait for it: the share's last add (c->pipe.acc_last), or, for a rank with no iterations in the
 // frame, the zeroing itself, done on the reduce stream (which already follows the previous reduce).
 int enqueue_frame(kdpt_ctx* c, int f, int spp, int pipeline, int batch) {
   int rc = frame_buffers(c);
   if (rc) return rc;
-  float* fb = c->frame_buf[f & 1];
+  float* fb = c->frames.buf[f & 1].get();
   int first, count;
-  frame_share(f, spp, c->nranks, c->rank, &first, &count);
+  frame_share(f, spp, c->frames.nranks, c->frames.rank, &first, &count);
   if (count > 0) {
-    if ((rc = enqueue_iterations(c, first, count, c->nranks, pipeline, batch, fb, c->frame_ev[f & 1]))) return rc;
-    HIP_TRY(hipStreamWaitEvent(c->reduce_stream, c->acc_last, 0));
+    if ((rc = enqueue_iterations(c, first, count, c->frames.nranks, pipeline, batch, fb, c->frames.ev[f & 1]))) return rc;
+    HIP_TRY(hipStreamWaitEvent(c->frames.reduce_stream, c->pipe.acc_last, 0));
   } else {
-    HIP_TRY(hipMemsetAsync(fb, 0, sizeof(float) * 3 * (size_t)c->npix, c->reduce_stream));
+    HIP_TRY(hipMemsetAsync(fb, 0, sizeof(float) * 3 * (size_t)c->npix, c->frames.reduce_stream));
   }
   return KDPT_OK;
 }
@@ -2190,22 +2085,28 @@ int enqueue_frame(kdpt_ctx* c, int f, int spp, int pipeline, int batch) {
 // Rank 0, after its frame image is in `sum`: add it into the context's image and copy it out.
 int finish_frame(kdpt_ctx* c, const float* sum, float* out, int k, hipStream_t st) {
   const int n3 = 3 * c->npix;
-  PartialImages parts{};
-  parts.p[0] = sum;
-  parts.nb = 1;
-  hipLaunchKernelGGL(k_accumulate_batch, dim3((n3 + 255) / 256), dim3(256), 0, st, c->image, parts, n3);
+  hipLaunchKernelGGL(k_accumulate_batch, dim3((n3 + 255) / 256), dim3(256), 0, st, c->image,
+                     fill_parts<PartialImages>(&sum, 1), n3);
   HIP_TRY(hipGetLastError());
   c->accumulated = true;
   if (out) HIP_TRY(hipMemcpyAsync(out + (size_t)k * n3, sum, sizeof(float) * n3, hipMemcpyDefault, st));
   return KDPT_OK;
 }
 
-int check_frames_args(kdpt_ctx* c, int first_frame, int frames, int spp) {
-  if (!c || first_frame < 0 || frames < 0 || spp < 1) return fail(KDPT_ERR_ARG, "bad arguments");
+}  // namespace
+
+// Everything the context owns goes with `delete c`, in reverse order of kdpt_ctx's members, once the streams are
+// drained (a kdpt_render_frames that failed partway may have left a reduce queued) and the communicator released.
+int kdpt_destroy(kdpt_ctx* c) {
+  if (!c) return KDPT_OK;
+  (void)hipSetDevice(c->device);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  c->pipe.drop_groups();  // (each group's stream drained first)
+  if (c->frames.reduce_stream) (void)hipStreamSynchronize(c->frames.reduce_stream);
+  release_comm(c);
+  delete c;
   return KDPT_OK;
 }
-
-}  // namespace
 
 int kdpt_comm_library(char* path, int len) {
   if (!path || len < 1) return fail(KDPT_ERR_ARG, "bad arguments");
@@ -2236,9 +2137,9 @@ int kdpt_comm_init(kdpt_ctx* c, int nranks, int rank, const unsigned char* id) {
   if (rc) return rc;
   release_comm(c);
   const Rccl* R = rccl();
-  c->nranks = nranks;
-  c->rank = rank;
-  c->external_reduce = nranks > 1 && !id;
+  c->frames.nranks = nranks;
+  c->frames.rank = rank;
+  c->frames.external_reduce = nranks > 1 && !id;
   // (one rank with an id gets a communicator too: kdpt_render_frames then runs the same ncclReduce per frame
   // as on N GPUs, so one GPU exercises the multi-GPU path end to end)
   if (id) {
@@ -2247,46 +2148,46 @@ int kdpt_comm_init(kdpt_ctx* c, int nranks, int rank, const unsigned char* id) {
     memcpy(&u, id, sizeof u);
     ncclComm_t comm;
     RCCL_TRY(R, R->commInitRank(&comm, nranks, u, rank));
-    c->comm = comm;
-    c->owns_comm = true;
+    c->frames.comm = comm;
+    c->frames.owns_comm = true;
   }
   return KDPT_OK;
 }
 
 int kdpt_render_frames(kdpt_ctx* c, int first_frame, int frames, int spp, int pipeline, int batch, float* out) {
-  int rc = check_frames_args(c, first_frame, frames, spp);
-  if (rc) return rc;
-  if (c->moments)
+  if (!c || first_frame < 0 || frames < 0 || spp < 1) return fail(KDPT_ERR_ARG, "bad arguments");
+  int rc;
+  if (c->mom.on)
     return fail(KDPT_ERR_UNSUPPORTED,
                 "kdpt_render_frames: the context keeps second moments (kdpt_set_moments), and frames reach the "
                 "image through a cross-rank reduce that does not carry them; turn moments off first");
   HIP_TRY(hipSetDevice(c->device));
-  const Rccl* R = c->comm ? rccl() : nullptr;
-  if (c->nranks > 1 && !R && !c->external_reduce) return fail(KDPT_ERR_ARG, "kdpt_comm_init first");
+  const Rccl* R = c->frames.comm ? rccl() : nullptr;
+  if (c->frames.nranks > 1 && !R && !c->frames.external_reduce) return fail(KDPT_ERR_ARG, "kdpt_comm_init first");
   const size_t n3 = 3 * (size_t)c->npix;
-  if (c->rank == 0 || c->external_reduce) pin_host_out(c, out, sizeof(float) * n3 * (size_t)frames);
+  if (c->frames.rank == 0 || c->frames.external_reduce) pin_host_out(c, out, sizeof(float) * n3 * (size_t)frames);
   for (int k = 0; k < frames; k++) {
     const int f = first_frame + k;
     if ((rc = enqueue_frame(c, f, spp, pipeline, batch))) return rc;
-    float* fb = c->frame_buf[f & 1];
+    float* fb = c->frames.buf[f & 1].get();
     // the frame's reduce and image add run on the reduce stream once its adds are done (enqueue_frame), while
     // the batch streams go on with the next frame's (other buffer)
-    const hipStream_t rs = c->reduce_stream;
+    const hipStream_t rs = c->frames.reduce_stream;
     if ((rc = reduce_spin(c, rs))) return rc;
     const float* sum = fb;
-    if (c->external_reduce) {  // the caller reduces: every rank's share goes out as it is
+    if (c->frames.external_reduce) {  // the caller reduces: every rank's share goes out as it is
       if (out) HIP_TRY(hipMemcpyAsync(out + (size_t)k * n3, fb, sizeof(float) * n3, hipMemcpyDefault, rs));
     } else {
       if (R) {
-        RCCL_TRY(R, R->reduce(fb, c->rank == 0 ? c->frame_sum : nullptr, n3, ncclFloat32, ncclSum, 0,
-                              (ncclComm_t)c->comm, rs));
-        sum = c->frame_sum;
+        RCCL_TRY(R, R->reduce(fb, c->frames.rank == 0 ? c->frames.sum.get() : nullptr, n3, ncclFloat32, ncclSum, 0,
+                              (ncclComm_t)c->frames.comm, rs));
+        sum = c->frames.sum.get();
       }
-      if (c->rank == 0 && (rc = finish_frame(c, sum, out, k, rs))) return rc;
+      if (c->frames.rank == 0 && (rc = finish_frame(c, sum, out, k, rs))) return rc;
     }
-    HIP_TRY(hipEventRecord(c->frame_ev[f & 1], rs));
+    HIP_TRY(hipEventRecord(c->frames.ev[f & 1], rs));
     // (entry points that read or write the image, and adds into it, follow the last reduce: join_accum)
-    c->img_last = c->frame_ev[f & 1];
+    c->pipe.img_last = c->frames.ev[f & 1];
   }
   return KDPT_OK;
 }
@@ -2300,50 +2201,52 @@ int kdpt_render_sharded(const kdpt_scene* scene, const kdpt_options* opt, int nd
   if (opt) o = *opt;
   else kdpt_default_options(&o);
   o.external_image = nullptr;
-  std::vector<kdpt_ctx*> cs(ndev, nullptr);
-  // every event this call records across devices (destroyed once the contexts' streams are drained)
-  std::vector<std::pair<int, hipEvent_t>> xev;
-  auto cleanup = [&](int rc) {
-    for (auto c : cs)
-      if (c) kdpt_destroy(c);  // (drains its streams, releases its communicator)
-    for (auto& de : xev) {
-      (void)hipSetDevice(de.first);
-      (void)hipEventDestroy(de.second);
+  // Owning locals, released at every return last first: the contexts (kdpt_destroy drains a context's streams),
+  // then the copy reduce's staged frames, then every event this call records across devices, each on its device.
+  struct XEvents {
+    std::vector<std::pair<int, Event>> v;
+    ~XEvents() {
+      for (auto& de : v)
+        if (hipSetDevice(de.first) == hipSuccess) de.second.reset();
     }
-    return rc;
-  };
+  } xev;
+  std::vector<DeviceBuf<float>> staged(ndev);  // copy reduce: the other ranks' frames on device 0
+  std::vector<std::unique_ptr<kdpt_ctx, int (*)(kdpt_ctx*)>> cs;
   int rc;
   for (int i = 0; i < ndev; i++) {
-    if ((rc = kdpt_create(scene, &o, devices[i], &cs[i]))) return cleanup(rc);
-    cs[i]->nranks = ndev;
-    cs[i]->rank = i;
+    kdpt_ctx* ci = nullptr;
+    if ((rc = kdpt_create(scene, &o, devices[i], &ci))) return rc;
+    cs.emplace_back(ci, kdpt_destroy);
+    cs[i]->frames.nranks = ndev;
+    cs[i]->frames.rank = i;
   }
   const Rccl* R = nullptr;
   if (reduce == KDPT_REDUCE_RCCL) {
     R = rccl();
-    if (!R) return cleanup(fail(KDPT_ERR_UNSUPPORTED, "librccl.so.1 not found"));
+    if (!R) return fail(KDPT_ERR_UNSUPPORTED, "librccl.so.1 not found");
     std::vector<ncclComm_t> comms(ndev);
     const ncclResult_t e = R->commInitAll(comms.data(), ndev, devices);
-    if (e != ncclSuccess) return cleanup(fail(KDPT_ERR_HIP, std::string("rccl: ") + R->errorString(e)));
+    if (e != ncclSuccess) return fail(KDPT_ERR_HIP, std::string("rccl: ") + R->errorString(e));
     for (int i = 0; i < ndev; i++) {
-      cs[i]->comm = comms[i];
-      cs[i]->owns_comm = true;
+      cs[i]->frames.comm = comms[i];
+      cs[i]->frames.owns_comm = true;
     }
   }
-  kdpt_ctx* c0 = cs[0];
+  kdpt_ctx* c0 = cs[0].get();
   const int n3 = 3 * c0->npix;
-  std::vector<float*> staged(ndev, nullptr);  // copy-reduce: the other ranks' frames on device 0
   if (reduce == KDPT_REDUCE_COPY)
     for (int i = 1; i < ndev; i++)
-      if ((rc = dalloc(c0, &staged[i], (size_t)n3))) return cleanup(rc);
+      if (const hipError_t e = staged[i].alloc((size_t)n3)) return hip_fail("hipMalloc", e);
   // a pageable host `out` pinned for the call (released by the final kdpt_synchronize of c0)
   pin_host_out(c0, out, sizeof(float) * (size_t)n3 * (size_t)frames);
   hipError_t he;  // the HIP status behind a failing step
   auto xevent = [&](int dev, hipStream_t st, hipEvent_t* e) {
-    if ((he = hipSetDevice(dev)) != hipSuccess || (he = hipEventCreateWithFlags(e, hipEventDisableTiming)) != hipSuccess ||
-        (he = hipEventRecord(*e, st)) != hipSuccess)
+    Event ev;
+    if ((he = hipSetDevice(dev)) != hipSuccess || (he = ev.create_untimed()) != hipSuccess ||
+        (he = hipEventRecord(ev, st)) != hipSuccess)
       return false;
-    xev.push_back({dev, *e});
+    *e = ev;
+    xev.v.emplace_back(dev, std::move(ev));
     return true;
   };
   for (int k = 0; k < frames; k++) {
@@ -2352,60 +2255,61 @@ int kdpt_render_sharded(const kdpt_scene* scene, const kdpt_options* opt, int nd
     // kdpt_render_frames), so frame f + 1's adds never queue behind frame f's reduce
     std::vector<hipEvent_t> share_done(ndev, nullptr);  // each rank's last add of the frame (copy reduce)
     for (int i = 0; i < ndev; i++) {
-      kdpt_ctx* ci = cs[i];
-      if ((he = hipSetDevice(ci->device)) != hipSuccess) return cleanup(hip_fail("hipSetDevice", he));
-      if ((rc = enqueue_frame(ci, f, spp, pipeline, batch))) return cleanup(rc);
-      if ((rc = reduce_spin(ci, ci->reduce_stream))) return cleanup(rc);
+      kdpt_ctx* ci = cs[i].get();
+      if ((he = hipSetDevice(ci->device)) != hipSuccess) return hip_fail("hipSetDevice", he);
+      if ((rc = enqueue_frame(ci, f, spp, pipeline, batch))) return rc;
+      if ((rc = reduce_spin(ci, ci->frames.reduce_stream))) return rc;
       // (recorded on the rank's reduce stream, which already waits for the share)
-      if (!xevent(ci->device, ci->reduce_stream, &share_done[i])) return cleanup(hip_fail("frame events", he));
+      if (!xevent(ci->device, ci->frames.reduce_stream, &share_done[i])) return hip_fail("frame events", he);
     }
-    if ((he = hipSetDevice(c0->device)) != hipSuccess) return cleanup(hip_fail("hipSetDevice", he));
-    if ((rc = frame_buffers(c0))) return cleanup(rc);
+    if ((he = hipSetDevice(c0->device)) != hipSuccess) return hip_fail("hipSetDevice", he);
+    if ((rc = frame_buffers(c0))) return rc;
     if (reduce == KDPT_REDUCE_RCCL) {
       R->groupStart();
       ncclResult_t e = ncclSuccess;
       for (int i = 0; i < ndev && e == ncclSuccess; i++)
-        e = R->reduce(cs[i]->frame_buf[f & 1], i == 0 ? c0->frame_sum : nullptr, (size_t)n3, ncclFloat32, ncclSum,
-                      0, (ncclComm_t)cs[i]->comm, cs[i]->reduce_stream);
+        e = R->reduce(cs[i]->frames.buf[f & 1].get(), i == 0 ? c0->frames.sum.get() : nullptr, (size_t)n3, ncclFloat32,
+                      ncclSum, 0, (ncclComm_t)cs[i]->frames.comm, cs[i]->frames.reduce_stream);
       const ncclResult_t e2 = R->groupEnd();
       if (e != ncclSuccess || e2 != ncclSuccess)
-        return cleanup(fail(KDPT_ERR_HIP, std::string("rccl: ") + R->errorString(e != ncclSuccess ? e : e2)));
+        return fail(KDPT_ERR_HIP, std::string("rccl: ") + R->errorString(e != ncclSuccess ? e : e2));
     } else {
       // device 0's reduce stream waits for every rank's share and copies the others' over (peer copies: xGMI
       // between GPUs), then adds them in rank order
       FrameParts parts{};
       parts.n = ndev;
-      parts.p[0] = c0->frame_buf[f & 1];
+      parts.p[0] = c0->frames.buf[f & 1].get();
       for (int i = 1; i < ndev; i++) {
-        kdpt_ctx* ci = cs[i];
+        kdpt_ctx* ci = cs[i].get();
         if ((he = hipSetDevice(c0->device)) != hipSuccess ||
-            (he = hipStreamWaitEvent(c0->reduce_stream, share_done[i], 0)) != hipSuccess ||
-            (he = hipMemcpyPeerAsync(staged[i], c0->device, ci->frame_buf[f & 1], ci->device, sizeof(float) * (size_t)n3,
-                                     c0->reduce_stream)) != hipSuccess)
-          return cleanup(hip_fail("copy reduce: peer copy", he));
-        parts.p[i] = staged[i];
+            (he = hipStreamWaitEvent(c0->frames.reduce_stream, share_done[i], 0)) != hipSuccess ||
+            (he = hipMemcpyPeerAsync(staged[i].get(), c0->device, ci->frames.buf[f & 1].get(), ci->device,
+                                     sizeof(float) * (size_t)n3, c0->frames.reduce_stream)) != hipSuccess)
+          return hip_fail("copy reduce: peer copy", he);
+        parts.p[i] = staged[i].get();
       }
-      hipLaunchKernelGGL(k_sum_frames, dim3((n3 + 255) / 256), dim3(256), 0, c0->reduce_stream, c0->frame_sum, parts, n3);
-      if ((he = hipGetLastError()) != hipSuccess) return cleanup(hip_fail("k_sum_frames", he));
+      hipLaunchKernelGGL(k_sum_frames, dim3((n3 + 255) / 256), dim3(256), 0, c0->frames.reduce_stream,
+                         c0->frames.sum.get(), parts, n3);
+      if ((he = hipGetLastError()) != hipSuccess) return hip_fail("k_sum_frames", he);
       // the other ranks' frame_buf[f & 1] may be reused (frame f + 2) once these copies are done
       hipEvent_t done;
-      if (!xevent(c0->device, c0->reduce_stream, &done)) return cleanup(hip_fail("copy reduce: done event", he));
+      if (!xevent(c0->device, c0->frames.reduce_stream, &done)) return hip_fail("copy reduce: done event", he);
       for (int i = 1; i < ndev; i++)
         if ((he = hipSetDevice(cs[i]->device)) != hipSuccess ||
-            (he = hipStreamWaitEvent(cs[i]->reduce_stream, done, 0)) != hipSuccess)
-          return cleanup(hip_fail("copy reduce: wait for the done event", he));
+            (he = hipStreamWaitEvent(cs[i]->frames.reduce_stream, done, 0)) != hipSuccess)
+          return hip_fail("copy reduce: wait for the done event", he);
     }
-    if ((he = hipSetDevice(c0->device)) != hipSuccess) return cleanup(hip_fail("hipSetDevice", he));
-    if ((rc = finish_frame(c0, c0->frame_sum, out, k, c0->reduce_stream))) return cleanup(rc);
+    if ((he = hipSetDevice(c0->device)) != hipSuccess) return hip_fail("hipSetDevice", he);
+    if ((rc = finish_frame(c0, c0->frames.sum.get(), out, k, c0->frames.reduce_stream))) return rc;
     for (int i = 0; i < ndev; i++) {
       if ((he = hipSetDevice(cs[i]->device)) != hipSuccess ||
-          (he = hipEventRecord(cs[i]->frame_ev[f & 1], cs[i]->reduce_stream)) != hipSuccess)
-        return cleanup(hip_fail("hipEventRecord", he));
+          (he = hipEventRecord(cs[i]->frames.ev[f & 1], cs[i]->frames.reduce_stream)) != hipSuccess)
+        return hip_fail("hipEventRecord", he);
     }
   }
   for (int i = 0; i < ndev; i++)
-    if ((rc = kdpt_synchronize(cs[i]))) return cleanup(rc);
-  return cleanup(KDPT_OK);
+    if ((rc = kdpt_synchronize(cs[i].get()))) return rc;
+  return KDPT_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -2413,51 +2317,42 @@ int kdpt_render_sharded(const kdpt_scene* scene, const kdpt_options* opt, int nd
 // ---------------------------------------------------------------------------
 namespace {
 
-void free_cast_buffers(kdpt_ctx* c) {
-  void* const bufs[] = {c->cast_in, c->cast_out, c->cast_cray, c->cast_cand, c->cast_hits, c->cast_cnt, c->cast_tt};
-  for (void* p : bufs)
-    if (p) (void)hipFree(p);
-  c->cast_in = nullptr;
-  c->cast_out = nullptr;
-  c->cast_cray = nullptr;
-  c->cast_cand = nullptr;
-  c->cast_hits = nullptr;
-  c->cast_cnt = nullptr;
-  c->cast_tt = nullptr;
-  c->cast_alloc = 0;
-}
-
-// The query's buffers for chunks of c->cast_chunk rays (nothing is queued on the context: the caller has
+// The query's buffers for chunks of c->cast.chunk rays (nothing is queued on the context: the caller has
 // synchronised, so the old ones can go).
 int cast_buffers(kdpt_ctx* c) {
-  if (c->cast_alloc == c->cast_chunk) return KDPT_OK;
-  free_cast_buffers(c);
-  const size_t m = (size_t)c->cast_chunk;
-  if (hipMalloc((void**)&c->cast_in, sizeof(float) * 6 * m) != hipSuccess ||
-      hipMalloc((void**)&c->cast_out, sizeof(kdpt_ray_hit) * m) != hipSuccess ||
-      hipMalloc((void**)&c->cast_cray, sizeof(float4) * 2 * m) != hipSuccess ||
-      hipMalloc((void**)&c->cast_cand, sizeof(int) * m) != hipSuccess ||
-      hipMalloc((void**)&c->cast_hits, sizeof(int2) * m) != hipSuccess ||
-      hipMalloc((void**)&c->cast_cnt, sizeof(int) * 2) != hipSuccess ||
-      hipMalloc((void**)&c->cast_tt, sizeof(unsigned long long) * 3) != hipSuccess) {
+  CastQuery::Buffers& b = c->cast.b;
+  if (b.alloc == c->cast.chunk) return KDPT_OK;
+  b = {};
+  const size_t m = (size_t)c->cast.chunk;
+  if (b.in.alloc(6 * m) != hipSuccess || b.out.alloc(m) != hipSuccess || b.cray.alloc(2 * m) != hipSuccess ||
+      b.cand.alloc(m) != hipSuccess || b.hits.alloc(m) != hipSuccess || b.cnt.alloc(2) != hipSuccess ||
+      b.tt.alloc(3) != hipSuccess) {
     (void)hipGetLastError();
-    free_cast_buffers(c);
+    b = {};
     return fail(KDPT_ERR_HIP, "kdpt_cast_rays: cannot allocate the buffers of a " + std::to_string(m) +
                                   "-ray chunk (knob cast_chunk)");
   }
-  for (auto& e : c->cast_ev)
-    if (!e) HIP_TRY(hipEventCreate(&e));
-  c->cast_alloc = c->cast_chunk;
+  for (Event& e : c->cast.ev)
+    if (!e) HIP_TRY(e.create());
+  b.alloc = c->cast.chunk;
   return KDPT_OK;
 }
 
-// Is p memory of the context's device (as kdpt_write_pbo tells its pbo apart)?
-bool on_context_device(const kdpt_ctx* c, const void* p) {
-  hipPointerAttribute_t attr{};
-  const bool dev = hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeDevice &&
-                   attr.device == c->device;
-  (void)hipGetLastError();  // a plain host pointer is an error for hipPointerGetAttributes on some runtimes
-  return dev;
+// A caller's array on its way to the kernels and back.  Memory of the context's device (dev: on_context_device) is
+// read and written where it is; anything else goes through a staging buffer of the context's and a copy on st.
+template <typename T>
+int stage_in(bool dev, const T** src, size_t n, T* stage, hipStream_t st) {
+  if (dev) return KDPT_OK;
+  HIP_TRY(hipMemcpyAsync(stage, *src, n * sizeof(T), hipMemcpyHostToDevice, st));
+  *src = stage;
+  return KDPT_OK;
+}
+// An output: the n elements the kernels left at `from` to the caller's dst (nothing to do when they wrote dst).
+template <typename T>
+int stage_out(bool dev, T* dst, const T* from, size_t n, hipStream_t st) {
+  if (from == dst) return KDPT_OK;
+  HIP_TRY(hipMemcpyAsync(dst, from, n * sizeof(T), dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  return KDPT_OK;
 }
 
 }  // namespace
@@ -2480,63 +2375,56 @@ int kdpt_cast_rays(kdpt_ctx* c, const float* origins, const float* directions, l
   const hipStream_t st = c->stream;
   const bool o_dev = on_context_device(c, origins), d_dev = on_context_device(c, directions),
              out_dev = on_context_device(c, out);
-  const int chunk = c->cast_alloc;
-  HIP_TRY(hipMemsetAsync(c->cast_cnt, 0, sizeof(int) * 2, st));
-  HIP_TRY(hipMemsetAsync(c->cast_tt, 0, sizeof(unsigned long long) * 3, st));
-  HIP_TRY(hipEventRecord(c->cast_ev[0], st));
+  const CastQuery::Buffers& cb = c->cast.b;
+  const int chunk = cb.alloc;
+  HIP_TRY(hipMemsetAsync(cb.cnt.get(), 0, sizeof(int) * 2, st));
+  HIP_TRY(hipMemsetAsync(cb.tt.get(), 0, sizeof(unsigned long long) * 3, st));
+  HIP_TRY(hipEventRecord(c->cast.ev[0], st));
   CastArgs a;
   a.S = c->S;
   a.normalize = (flags & KDPT_CAST_NORMALIZE) ? 1 : 0;
-  a.cray = c->cast_cray;
-  a.hits = c->cast_hits;
-  a.cand = c->cast_cand;
-  a.cnt = c->cast_cnt;
-  a.tt = c->cast_tt;
+  a.cray = cb.cray.get();
+  a.hits = cb.hits.get();
+  a.cand = cb.cand.get();
+  a.cnt = cb.cnt.get();
+  a.tt = cb.tt.get();
   // (one "iteration" at bounce 0: the query's own queue, its length in cast_cnt[1], the chunk counter in [0])
-  const TraceArgs t{c->S, c->cast_cand, c->cast_cray, c->cast_cnt + 1, c->cast_hits, nullptr, 0, c->cast_cnt, 0,
-                    c->counters, c->cast_tt};
+  const TraceArgs t{c->S, a.cand, a.cray, a.cnt + 1, a.hits, nullptr, 0, a.cnt, 0, c->counters, a.tt};
   void (*const resolve)(CastArgs) = hybrid_shading(c) ? k_cast_resolve<true> : k_cast_resolve<false>;
   for (long long off = 0; off < n; off += chunk) {
     const int m = (int)std::min<long long>(chunk, n - off);
     a.n = m;
     a.o = origins + 3 * off;
     a.d = directions + 3 * off;
-    if (!o_dev) {
-      HIP_TRY(hipMemcpyAsync(c->cast_in, a.o, sizeof(float) * 3 * (size_t)m, hipMemcpyHostToDevice, st));
-      a.o = c->cast_in;
-    }
-    if (!d_dev) {
-      HIP_TRY(hipMemcpyAsync(c->cast_in + 3 * (size_t)chunk, a.d, sizeof(float) * 3 * (size_t)m,
-                             hipMemcpyHostToDevice, st));
-      a.d = c->cast_in + 3 * (size_t)chunk;
-    }
-    a.out = out_dev ? out + off : c->cast_out;
+    if ((rc = stage_in(o_dev, &a.o, 3 * (size_t)m, cb.in.get(), st)) ||
+        (rc = stage_in(d_dev, &a.d, 3 * (size_t)m, cb.in.get() + 3 * (size_t)chunk, st)))
+      return rc;
+    a.out = out_dev ? out + off : cb.out.get();
     hipLaunchKernelGGL(k_cast_prep, dim3((m + GEN_BLOCK - 1) / GEN_BLOCK), dim3(GEN_BLOCK), 0, st, a);
     HIP_TRY(hipGetLastError());
     launch_trace(c, t, false, c->trace_grid, st);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(resolve, dim3((m + 255) / 256), dim3(256), 0, st, a);
     HIP_TRY(hipGetLastError());
-    if (!out_dev)
-      HIP_TRY(hipMemcpyAsync(out + off, c->cast_out, sizeof(kdpt_ray_hit) * (size_t)m, hipMemcpyDeviceToHost, st));
+    if ((rc = stage_out(out_dev, out + off, a.out, (size_t)m, st))) return rc;
   }
-  HIP_TRY(hipEventRecord(c->cast_ev[1], st));
+  HIP_TRY(hipEventRecord(c->cast.ev[1], st));
   unsigned long long traced = 0;
-  HIP_TRY(hipMemcpyAsync(&traced, c->cast_tt + 2, sizeof traced, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&traced, a.tt + 2, sizeof traced, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   float ms = 0;
-  HIP_TRY(hipEventElapsedTime(&ms, c->cast_ev[0], c->cast_ev[1]));
-  c->cast_ms = ms;
-  c->cast_rays += n;
-  c->cast_traced += (long long)traced;
+  HIP_TRY(hipEventElapsedTime(&ms, c->cast.ev[0], c->cast.ev[1]));
+  c->cast.ms = ms;
+  c->cast.rays += n;
+  c->cast.traced += (long long)traced;
   return check_fault(&c->solo, c->stream);
 }
 
 int kdpt_cast_stats(kdpt_ctx* c, long long* rays, long long* traced, double* device_ms) {
   if (!c) return fail(KDPT_ERR_ARG, "kdpt_cast_stats: null ctx");
-  if (rays) *rays = c->cast_rays;
-  if (traced) *traced = c->cast_traced;
-  if (device_ms) *device_ms = c->cast_ms;
+  if (rays) *rays = c->cast.rays;
+  if (traced) *traced = c->cast.traced;
+  if (device_ms) *device_ms = c->cast.ms;
   return KDPT_OK;
 }
 
@@ -2549,20 +2437,18 @@ namespace {
 
 // The query's iteration state and buffers, made on first use (the caller has synchronised the context).
 int query_state(kdpt_ctx* c) {
-  if (c->query_ready) return KDPT_OK;
-  int rc;
-  if (!c->query.counts && (rc = alloc_iter(c, &c->query, c->stream, false))) {
-    free_iter(&c->query);
-    return rc;
+  RayQuery& q = c->query;
+  if (!q.state) {  // (a failed alloc_iter drops the half-made state: the next call starts again)
+    std::unique_ptr<IterState> it(new IterState());
+    if (int rc = alloc_iter(c, it.get(), c->stream, false)) return rc;
+    q.state = std::move(it);
   }
   const size_t npix = (size_t)c->npix;
-  if ((!c->query_image && (rc = dalloc(c, &c->query_image, 3 * npix))) ||
-      (!c->query_stage && (rc = dalloc(c, &c->query_stage, 6 * npix))) ||
-      (!c->query_totals && (rc = dalloc(c, &c->query_totals, 4))))
-    return rc;
-  c->query.image = c->query_image;
-  c->query.total_segments = c->query_totals;
-  c->query_ready = true;
+  if (!q.image) HIP_TRY(q.image.alloc(3 * npix));
+  if (!q.stage) HIP_TRY(q.stage.alloc(6 * npix));
+  if (!q.totals) HIP_TRY(q.totals.alloc(4));
+  q.state->image = q.image.get();
+  q.state->total_segments = q.totals.get();
   return KDPT_OK;
 }
 
@@ -2593,7 +2479,7 @@ int kdpt_camera_rays(kdpt_ctx* c, int iter, float* origins, float* directions) {
   int rc = kdpt_synchronize(c);  // everything queued on the context first
   if (rc || (rc = query_state(c))) return rc;
   const hipStream_t st = c->stream;
-  IterState& q = c->query;
+  IterState& q = *c->query.state;
   q.cur = 0;
   GenBatch gb = gen_batch(c);
   gb.it[0] = q.gen_iter(c->opt.cacherays ? 1 : iter);
@@ -2606,9 +2492,9 @@ int kdpt_camera_rays(kdpt_ctx* c, int iter, float* origins, float* directions) {
   const float4* const srcs[2] = {q.buf[0].p0, q.buf[0].p1};
   for (int k = 0; k < 2; k++) {
     const bool dev = on_context_device(c, outs[k]);
-    float* const packed = dev ? outs[k] : c->query_stage + 3 * npix * k;
+    float* const packed = dev ? outs[k] : c->query.stage.get() + 3 * npix * k;
     HIP_TRY(hipMemcpy2DAsync(packed, row, srcs[k], sizeof(float4), row, npix, hipMemcpyDeviceToDevice, st));
-    if (!dev) HIP_TRY(hipMemcpyAsync(outs[k], packed, row * npix, hipMemcpyDeviceToHost, st));
+    if ((rc = stage_out(dev, outs[k], packed, 3 * npix, st))) return rc;
   }
   HIP_TRY(hipStreamSynchronize(st));
   return KDPT_OK;
@@ -2640,54 +2526,48 @@ int trace_rays_query(kdpt_ctx* c, const float* origins, const float* directions,
   int rc = kdpt_synchronize(c);  // everything queued on the context first
   if (rc || (rc = query_state(c))) return rc;
   const hipStream_t st = c->stream;
-  IterState* q = &c->query;
+  RayQuery& Q = c->query;
+  IterState* q = Q.state.get();
   const size_t m = (size_t)n, npix = (size_t)c->npix;
-  if (moments && ((!c->query_partial && (rc = dalloc(c, &c->query_partial, 3 * npix))) ||
-                  (!c->query_sumsq && (rc = dalloc(c, &c->query_sumsq, 3 * npix)))))
+  if (moments) {
+    if (!Q.partial) HIP_TRY(Q.partial.alloc(3 * npix));
+    if (!Q.sumsq) HIP_TRY(Q.sumsq.alloc(3 * npix));
+  }
+  float* const image = Q.image.get();
+  const float* const partial = Q.partial.get();
+  q->image = moments ? Q.partial.get() : image;  // where this call's gathers add
+  RaySource src{{origins, directions, (int)n, (flags & KDPT_CAST_NORMALIZE) ? 1 : 0}, Q.totals.get() + 1};
+  if ((rc = stage_in(on_context_device(c, origins), &src.rays.o, 3 * m, Q.stage.get(), st)) ||
+      (rc = stage_in(on_context_device(c, directions), &src.rays.d, 3 * m, Q.stage.get() + 3 * npix, st)))
     return rc;
-  q->image = moments ? c->query_partial : c->query_image;  // where this call's gathers add
-  RaySource src{{origins, directions, (int)n, (flags & KDPT_CAST_NORMALIZE) ? 1 : 0}, c->query_totals + 1};
-  if (!on_context_device(c, origins)) {
-    HIP_TRY(hipMemcpyAsync(c->query_stage, origins, sizeof(float) * 3 * m, hipMemcpyHostToDevice, st));
-    src.rays.o = c->query_stage;
-  }
-  if (!on_context_device(c, directions)) {
-    HIP_TRY(hipMemcpyAsync(c->query_stage + 3 * npix, directions, sizeof(float) * 3 * m, hipMemcpyHostToDevice, st));
-    src.rays.d = c->query_stage + 3 * npix;
-  }
   HIP_TRY(hipEventRecord(q->ev0, st));
   // pixel i of the query's image is ray i: the gathers add into it in iteration order, from zero
-  HIP_TRY(hipMemsetAsync(c->query_image, 0, sizeof(float) * 3 * m, st));
-  HIP_TRY(hipMemsetAsync(c->query_totals, 0, sizeof(unsigned long long) * 4, st));
-  if (moments) HIP_TRY(hipMemsetAsync(c->query_sumsq, 0, sizeof(float) * 3 * m, st));
+  HIP_TRY(hipMemsetAsync(image, 0, sizeof(float) * 3 * m, st));
+  HIP_TRY(hipMemsetAsync(Q.totals.get(), 0, sizeof(unsigned long long) * 4, st));
+  if (moments) HIP_TRY(hipMemsetAsync(Q.sumsq.get(), 0, sizeof(float) * 3 * m, st));
   for (int k = 0; k < count; k++) {
     const int iter = first_iter + k;
-    if (moments) HIP_TRY(hipMemsetAsync(c->query_partial, 0, sizeof(float) * 3 * m, st));
+    if (moments) HIP_TRY(hipMemsetAsync(Q.partial.get(), 0, sizeof(float) * 3 * m, st));
     if ((rc = launch_batch(c, &q, &iter, 1, st, c->trace_grid, -1, false, nullptr, &src))) return rc;
     if (moments) {
       const int m3 = 3 * (int)n;
-      MomentParts parts{};
-      parts.p[0] = c->query_partial;
-      parts.nb = 1;
-      hipLaunchKernelGGL(k_accumulate_moments, dim3((m3 + 255) / 256), dim3(256), 0, st, c->query_image,
-                         c->query_sumsq, parts, m3);
+      hipLaunchKernelGGL(k_accumulate_moments, dim3((m3 + 255) / 256), dim3(256), 0, st, image, Q.sumsq.get(),
+                         fill_parts<MomentParts>(&partial, 1), m3);
       HIP_TRY(hipGetLastError());
     }
   }
-  HIP_TRY(hipMemcpyAsync(radiance, c->query_image, sizeof(float) * 3 * m,
-                         on_context_device(c, radiance) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-  if (moments)
-    HIP_TRY(hipMemcpyAsync(sumsq, c->query_sumsq, sizeof(float) * 3 * m,
-                           on_context_device(c, sumsq) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  if ((rc = stage_out(on_context_device(c, radiance), radiance, image, 3 * m, st))) return rc;
+  if (moments && (rc = stage_out(on_context_device(c, sumsq), sumsq, Q.sumsq.get(), 3 * m, st)))
+    return rc;
   HIP_TRY(hipEventRecord(q->ev1, st));
   unsigned long long totals[4] = {0, 0, 0, 0};
-  HIP_TRY(hipMemcpyAsync(totals, c->query_totals, sizeof totals, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(totals, Q.totals.get(), sizeof totals, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   float ms = 0;
   HIP_TRY(hipEventElapsedTime(&ms, q->ev0, q->ev1));
-  c->query_ms = ms;
-  c->query_segments = (long long)totals[0];
-  c->query_traced = (long long)totals[3];
+  c->query.ms = ms;
+  c->query.segments = (long long)totals[0];
+  c->query.traced = (long long)totals[3];
   return check_fault(q, st);
 }
 
@@ -2707,9 +2587,9 @@ int kdpt_trace_rays_moments(kdpt_ctx* c, const float* origins, const float* dire
 
 int kdpt_trace_rays_stats(kdpt_ctx* c, long long* segments, long long* traced, double* device_ms) {
   if (!c) return fail(KDPT_ERR_ARG, "kdpt_trace_rays_stats: null ctx");
-  if (segments) *segments = c->query_segments;
-  if (traced) *traced = c->query_traced;
-  if (device_ms) *device_ms = c->query_ms;
+  if (segments) *segments = c->query.segments;
+  if (traced) *traced = c->query.traced;
+  if (device_ms) *device_ms = c->query.ms;
   return KDPT_OK;
 }
 
@@ -2723,14 +2603,8 @@ namespace {
 
 // The buffers of kdpt_set_moments go, and the solo state gathers straight into the image again.  (The caller has
 // drained the context's streams.)
-void free_moments(kdpt_ctx* c) {
-  void* const bufs[] = {c->mom_sumsq, c->mom_partial, c->noise_stage, c->noise_parts};
-  for (void* p : bufs)
-    if (p) (void)hipFree(p);
-  c->mom_sumsq = c->mom_partial = c->noise_stage = nullptr;
-  c->noise_parts = nullptr;
-  c->mom_samples = 0;
-  c->moments = false;
+void drop_moments(kdpt_ctx* c) {
+  c->mom = {};
   if (c->solo.zero_partial) {
     c->solo.image = c->image;
     c->solo.zero_partial = false;
@@ -2747,9 +2621,9 @@ int noise_blocks(const kdpt_ctx* c) {
 int check_noise_args(const kdpt_ctx* c, float floor, const std::string& who) {
   if (!c) return fail(KDPT_ERR_ARG, who + ": null ctx");
   if (!(std::isfinite(floor) && floor > 0.0f)) return fail(KDPT_ERR_ARG, who + ": floor must be finite and > 0");
-  if (!c->moments) return fail(KDPT_ERR_UNSUPPORTED, who + ": moments are off (kdpt_set_moments)");
-  if (c->mom_samples < 2)
-    return fail(KDPT_ERR_ARG, who + ": " + std::to_string(c->mom_samples) +
+  if (!c->mom.on) return fail(KDPT_ERR_UNSUPPORTED, who + ": moments are off (kdpt_set_moments)");
+  if (c->mom.samples < 2)
+    return fail(KDPT_ERR_ARG, who + ": " + std::to_string(c->mom.samples) +
                                   " iteration(s) accumulated, a variance needs at least 2");
   return KDPT_OK;
 }
@@ -2759,7 +2633,7 @@ int check_noise_args(const kdpt_ctx* c, float floor, const std::string& who) {
 int kdpt_set_moments(kdpt_ctx* c, int enable) {
   if (!c) return fail(KDPT_ERR_ARG, "kdpt_set_moments: null ctx");
   const bool on = enable != 0;
-  if (on == c->moments) return KDPT_OK;
+  if (on == c->mom.on) return KDPT_OK;
   if (on && (c->stats.iterations != 0 || c->accumulated))
     return fail(KDPT_ERR_UNSUPPORTED,
                 "kdpt_set_moments: iterations have been accumulated into the image since the last kdpt_reset; "
@@ -2767,37 +2641,36 @@ int kdpt_set_moments(kdpt_ctx* c, int enable) {
   int rc = kdpt_synchronize(c);  // everything queued on the context first (the solo state changes its target)
   if (rc) return rc;
   if (!on) {
-    free_moments(c);
+    drop_moments(c);
     return KDPT_OK;
   }
   const size_t n3 = 3 * (size_t)c->npix;
   hipError_t e;
-  if ((e = hipMalloc((void**)&c->mom_sumsq, sizeof(float) * n3)) != hipSuccess ||
-      (e = hipMalloc((void**)&c->mom_partial, sizeof(float) * n3)) != hipSuccess ||
-      (e = hipMalloc((void**)&c->noise_stage, sizeof(float) * (size_t)c->npix)) != hipSuccess ||
-      (e = hipMalloc((void**)&c->noise_parts, sizeof(NoisePartial) * ((size_t)noise_blocks(c) + 1))) != hipSuccess ||
-      (e = hipMemsetAsync(c->mom_sumsq, 0, sizeof(float) * n3, c->stream)) != hipSuccess ||
+  if ((e = c->mom.sumsq.alloc(n3)) != hipSuccess || (e = c->mom.partial.alloc(n3)) != hipSuccess ||
+      (e = c->mom.noise_stage.alloc((size_t)c->npix)) != hipSuccess ||
+      (e = c->mom.noise_parts.alloc((size_t)noise_blocks(c) + 1)) != hipSuccess ||
+      (e = hipMemsetAsync(c->mom.sumsq.get(), 0, sizeof(float) * n3, c->stream)) != hipSuccess ||
       (e = hipStreamSynchronize(c->stream)) != hipSuccess) {
-    free_moments(c);
+    drop_moments(c);
     return hip_fail("kdpt_set_moments", e);
   }
-  c->solo.image = c->mom_partial;
+  c->solo.image = c->mom.partial.get();
   c->solo.zero_partial = true;  // the camera kernel clears it, as it clears a pipeline state's
-  c->mom_samples = 0;
-  c->moments = true;
+  c->mom.samples = 0;
+  c->mom.on = true;
   return KDPT_OK;
 }
 
 int kdpt_read_moments(kdpt_ctx* c, float* sumsq, long long* samples) {
   if (!c) return fail(KDPT_ERR_ARG, "kdpt_read_moments: null ctx");
-  if (!c->moments) return fail(KDPT_ERR_UNSUPPORTED, "kdpt_read_moments: moments are off (kdpt_set_moments)");
+  if (!c->mom.on) return fail(KDPT_ERR_UNSUPPORTED, "kdpt_read_moments: moments are off (kdpt_set_moments)");
   HIP_TRY(hipSetDevice(c->device));
   int rc = join_accum(c);
   if (rc) return rc;
   if (sumsq)
-    HIP_TRY(hipMemcpyAsync(sumsq, c->mom_sumsq, sizeof(float) * 3 * (size_t)c->npix, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(sumsq, c->mom.sumsq.get(), sizeof(float) * 3 * (size_t)c->npix, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (samples) *samples = c->mom_samples;
+  if (samples) *samples = c->mom.samples;
   return KDPT_OK;
 }
 
@@ -2808,11 +2681,11 @@ int kdpt_noise_map(kdpt_ctx* c, float floor, float* noise) {
   HIP_TRY(hipSetDevice(c->device));
   if ((rc = join_accum(c))) return rc;
   const bool dev = on_context_device(c, noise);
-  float* const d = dev ? noise : c->noise_stage;
-  hipLaunchKernelGGL(k_noise_map, dim3((c->npix + 255) / 256), dim3(256), 0, c->stream, c->image, c->mom_sumsq,
-                     c->npix, c->mom_samples, floor, d);
+  float* const d = dev ? noise : c->mom.noise_stage.get();
+  hipLaunchKernelGGL(k_noise_map, dim3((c->npix + 255) / 256), dim3(256), 0, c->stream, c->image, c->mom.sumsq.get(),
+                     c->npix, c->mom.samples, floor, d);
   HIP_TRY(hipGetLastError());
-  if (!dev) HIP_TRY(hipMemcpyAsync(noise, d, sizeof(float) * (size_t)c->npix, hipMemcpyDeviceToHost, c->stream));
+  if ((rc = stage_out(dev, noise, d, (size_t)c->npix, c->stream))) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
   return KDPT_OK;
 }
@@ -2825,17 +2698,18 @@ int kdpt_noise_estimate(kdpt_ctx* c, float floor, float threshold, kdpt_noise* o
   HIP_TRY(hipSetDevice(c->device));
   if ((rc = join_accum(c))) return rc;
   const int nb = noise_blocks(c);
-  hipLaunchKernelGGL(k_noise_partials, dim3(nb), dim3(NOISE_BLOCK), 0, c->stream, c->image, c->mom_sumsq, c->npix,
-                     c->mom_samples, floor, threshold, c->noise_parts);
+  NoisePartial* const parts = c->mom.noise_parts.get();
+  hipLaunchKernelGGL(k_noise_partials, dim3(nb), dim3(NOISE_BLOCK), 0, c->stream, c->image, c->mom.sumsq.get(), c->npix,
+                     c->mom.samples, floor, threshold, parts);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_noise_final, dim3(1), dim3(NOISE_BLOCK), 0, c->stream, c->noise_parts, nb, c->noise_parts + nb);
+  hipLaunchKernelGGL(k_noise_final, dim3(1), dim3(NOISE_BLOCK), 0, c->stream, parts, nb, parts + nb);
   HIP_TRY(hipGetLastError());
   NoisePartial r{};
-  HIP_TRY(hipMemcpyAsync(&r, c->noise_parts + nb, sizeof r, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(&r, parts + nb, sizeof r, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   const long long finite = (long long)c->npix - r.nonfinite;
   memset(out, 0, sizeof *out);
-  out->samples = c->mom_samples;
+  out->samples = c->mom.samples;
   out->pixels = c->npix;
   out->above = r.above;
   out->nonfinite = r.nonfinite;

@@ -13,6 +13,8 @@ restatement under ASan/UBSan; the product's host code parses untrusted OBJ/MTL/s
 - tests/native/scene_prep_host.cpp: kdpt_create's scene validation and packing (csrc/kdpt_scene_prep.h), the
   code that reads nodes[ch].parentID, obj_polysidxflat[j] and the like from caller memory -- every option set
   on the edge OBJs, and every refusal provoked by one mutation of a private, exactly sized copy of the scene.
+- tests/native/owned_host.cpp: the owners of the library's HIP resources (csrc/kdpt_owned.h) against a counting
+  stub of the HIP entry points -- every creation released exactly once, nothing twice, nothing left (the leak check).
 """
 import json
 import os
@@ -179,3 +181,16 @@ def test_scene_prep_clean_under_sanitizers(scene_prep_host, files, name):
 def test_scene_prep_reference_mesh_clean_under_sanitizers(scene_prep_host):
     r = _run_prep(scene_prep_host, f"{REFERENCE}/scenes/cornell.txt", f"{REFERENCE}/scenes/sphere_low_1.obj")
     assert not r["skipped"] and set(r["ran"]) == MUTATIONS
+
+
+def test_owned_handles_clean_under_sanitizers():
+    exe = os.path.join(ROOT, "build", "owned_host")
+    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    tmp = f"{exe}.{os.getpid()}"
+    subprocess.run(["g++", *SAN, "-std=c++17", os.path.join(TESTS, "native", "owned_host.cpp"), "-o", tmp], check=True)
+    os.replace(tmp, exe)
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=ENV)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    assert "runtime error" not in p.stderr and "Sanitizer" not in p.stderr, p.stderr[-4000:]
+    r = json.loads(p.stdout.strip().splitlines()[-1])
+    assert r["failures"] == 0 and r["created"] == r["released"] > 0
