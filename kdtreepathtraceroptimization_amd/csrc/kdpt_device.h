@@ -264,6 +264,34 @@ KDPT_HD float boxIntersectionTest(const DevGeom& box, const Ray& r, f3& ip, f3& 
   return -1;
 }
 
+// "boxIntersectionTest(box, {o, d}) returns -1", proven from that test's own first steps: true only when it
+// does, false when this cannot tell (the exact test then decides as ever).
+//
+// qo is the exact test's q.origin: the same mulMV of the same operands, so the same bits.  Its q.direction is
+// qu scaled by f = 1 / sqrtf(dot(qu, qu)) (glm's normalize).  With l2 = dot(qu, qu) finite and > 0, f is finite
+// and > 0 (sqrtf(l2) lies in [2^-75, 2^64]; float denormals are kept on both targets), so qd_k = qu_k * f has
+// the sign of qu_k: a product that underflows becomes a zero of that sign, one that overflows an infinity of
+// that sign, and with qu_k != 0 and f > 0 it is never NaN.
+// Take an axis k with qo_k > 0.5 and qu_k > 0.  Both numerators, -0.5 - qo_k and 0.5 - qo_k, are < 0 (the
+// second because qo_k != 0.5 and a difference of two distinct floats of this size is not zero), and the divisor
+// qd_k is +0, positive or +inf: t1 and t2 are each -inf, negative or -0, never NaN and never > 0.  So
+// tb = glm_max(t1, t2) <= -0, `tb < tmax` holds against the initial 1e38 or tmax is already below it: after
+// axis k tmax <= -0, the other axes can only lower it (a NaN tb fails `tb < tmax` and leaves it), and the
+// final `tmax > 0` fails: -1.  The mirrored case, qo_k < -0.5 and qu_k < 0: both numerators > 0, the divisor
+// -0, negative or -inf, the same quotients.
+// The comparisons are strict, so a NaN coordinate, a numerator of 0 (qo_k = +-0.5) and a zero component of
+// the direction all abstain, as does an l2 that is 0, infinite or NaN (f would be inf, 0 or NaN, and 0 * inf
+// a NaN divisor).  Nothing here depends on the geom's bounds, so it holds for any origin.
+KDPT_HD bool box_provably_missed(const DevGeom& box, f3 o, f3 d) {
+  const f3 qo = mulMV(box.inverseTransform, f4{o.x, o.y, o.z, 1.0f});
+  const f3 qu = mulMV(box.inverseTransform, f4{d.x, d.y, d.z, 0.0f});
+  const float l2 = dot(qu, qu);
+  const bool leaves = (qo.x > 0.5f && qu.x > 0.0f) || (qo.x < -0.5f && qu.x < 0.0f) ||
+                      (qo.y > 0.5f && qu.y > 0.0f) || (qo.y < -0.5f && qu.y < 0.0f) ||
+                      (qo.z > 0.5f && qu.z > 0.0f) || (qo.z < -0.5f && qu.z < 0.0f);
+  return leaves && l2 > 0.0f && l2 < FLT_INFV;
+}
+
 // src/intersections.h:161-203
 KDPT_HD float sphereIntersectionTest(const DevGeom& sphere, const Ray& r, f3& ip, f3& nrm) {
   float radius = .5f;
@@ -337,6 +365,14 @@ KDPT_HD bool geoms_hold_for(const DevScene& S, f3 o) {
   return fmaxf(fmaxf(fabsf(o.x - S.gc.x) - S.gh.x, fabsf(o.y - S.gc.y) - S.gh.y), fabsf(o.z - S.gc.z) - S.gh.z) <= 0.0f;
 }
 constexpr int ORDERED_GEOMS = 8;  // scenes with at most this many analytic geoms test them nearest-first
+// prep_ray's two test-only switches, both for the host harness tests/native/geom_pretest_diff.cpp and for A/B
+// builds (tools/build_variant.sh); the product defines neither:
+//   KDPT_PREP_EVENT(kind, geom)  what the nearest-first branch does to one geom: 0 an exact test, 1 the pre-test
+//                                rules it out, 2 the pre-test abstains.  Empty here; the harness defines it to count.
+//   KDPT_NO_GEOM_PRETEST         compiles the pre-pass out: the loop as it was before, for the efficacy ratio.
+#ifndef KDPT_PREP_EVENT
+#define KDPT_PREP_EVENT(kind, geom) ((void)0)
+#endif
 KDPT_HDI bool prep_ray(const DevScene& S, bool kd, f3 o, f3 d, float& t_min, int& hit) {
   Ray ray;
   ray.origin = o;
@@ -357,7 +393,7 @@ KDPT_HDI bool prep_ray(const DevScene& S, bool kd, f3 o, f3 d, float& t_min, int
     // typically one or two exact tests per ray instead of one per geom the wave's rays come near.
     // An origin the bounds do not hold for enters every geom at -inf: all are tested, in index order.
     float lo[ORDERED_GEOMS];
-    uint32_t pending = 0;
+    uint32_t pending = 0, inside = 0;
 #pragma unroll
     for (int g = 0; g < ORDERED_GEOMS; g++) {
       lo[g] = FLT_INFV;
@@ -365,8 +401,27 @@ KDPT_HDI bool prep_ray(const DevScene& S, bool kd, f3 o, f3 d, float& t_min, int
         const bool enters = geom_entry_bound(S.geoms[g], o, inv, lo[g]);
         if (!held) lo[g] = -FLT_INFV;
         if (enters || !held) pending |= 1u << g;
+        if ((enters || !held) && lo[g] <= 0.0f) inside |= 1u << g;
       }
     }
+#ifndef KDPT_NO_GEOM_PRETEST
+    // The geoms whose enlarged bounds hold the origin (entry bound <= 0) come first in the loop below whatever
+    // they are: after a bounce that is the box the path has just left, which the ray cannot hit, and the loop's
+    // trip count is the wave's largest.  A box that box_provably_missed rules out is taken off the list here,
+    // for a fraction of an exact test; the loop then starts at the geom the ray may really hit.  Removing a
+    // geom whose exact test returns -1 changes neither the winner nor its t.  One step per lane, for the first
+    // such geom, so that the pre-pass is straight-line code and adds no loop-carried state: at the room's edges
+    // and corners, where two or three walls hold the origin, the others stay on the list as before (DESIGN
+    // section 4 has the measurement).  A wave of rays that start outside every geom's bounds, the camera's,
+    // skips the step.
+    if (inside) {
+      const int g = __builtin_ctz(inside);
+      const DevGeom& G = S.geoms[g];
+      const bool missed = G.type == 1 && box_provably_missed(G, o, d);
+      KDPT_PREP_EVENT(missed ? 1 : 2, g);
+      if (missed) pending &= ~(1u << g);
+    }
+#endif
     while (pending) {
       int gb = 0;
       float lb = FLT_INFV;
@@ -379,6 +434,7 @@ KDPT_HDI bool prep_ray(const DevScene& S, bool kd, f3 o, f3 d, float& t_min, int
       if (lb > t_min) break;  // every remaining geom's exact t exceeds the best
       pending &= ~(1u << gb);
       const DevGeom& G = S.geoms[gb];
+      KDPT_PREP_EVENT(0, gb);
       const float t = G.type == 1 ? boxIntersectionTest(G, ray, tmp_i, tmp_n)
                                   : sphereIntersectionTest(G, ray, tmp_i, tmp_n);
       if (t > 0.0f && (t < t_min || (t == t_min && gb < hit))) {

@@ -1,0 +1,216 @@
+// TEST INFRASTRUCTURE: the analytic-geom stage's box pre-test (kdpt_device.h box_provably_missed and the pre-pass
+// of prep_ray's nearest-first branch), compiled for the host, against the oracle (oracle/liboracle.so).
+//   geom_pretest_diff DESC NAME=RAYS ...
+//   geom_pretest_diff DESC --first-hits RAYS OUT
+// DESC and RAYS are tests/geoms.py write_desc's and write_rays' files (directions as traced); the scene's triangles
+// are left out.  Per RAYS file one JSON line:
+//   mismatches   rays on which prep_ray's winner or the bits of its t differ from orc_trace_ray's (the oracle's
+//                index-order loop over every geom);
+//   false_miss   (ray, box) pairs that box_provably_missed rules out although the oracle's boxIntersectionTest of
+//                that box alone (a one-geom oracle scene) returns t > 0 -- every box of every ray, whatever its
+//                bounds say;
+//   ruled_out    (ray, box) pairs the pre-test rules out, of `boxes` pairs in all;
+//   exact, pre_miss, pre_abstain   what prep_ray did, counted through kdpt_device.h's KDPT_PREP_EVENT hook (defined
+//                here, so in this program alone): exact tests run, pre-tests that ruled a box out / abstained;
+//   left_behind  rays with a box whose enlarged bounds hold the origin and which the oracle's test of that box
+//                alone misses: the rays the pre-pass exists for;
+//   hits, ordered   as geom_diff's.
+// Built with -DKDPT_NO_GEOM_PRETEST the same program runs prep_ray without the pre-pass, for the efficacy ratio.
+// --first-hits: the oracle's record of each ray of RAYS, to OUT: int32 n, then per ray int32 geom (-1: none),
+// int32 the geom's type, float32 point[3], float32 normal[3].
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+static long g_prep_events[3];
+#define KDPT_PREP_EVENT(kind, geom) (g_prep_events[(kind)]++)
+#include "../../kdtreepathtraceroptimization_amd/csrc/kdpt_scene_prep.h"
+extern "C" {
+#include "../../oracle/kdpt_oracle.h"
+}
+
+using namespace kdpt;
+
+static_assert(sizeof(orc_geom) == sizeof(kdpt_geom) && offsetof(orc_geom, transform) == offsetof(kdpt_geom, transform) &&
+              offsetof(orc_geom, invTranspose) == offsetof(kdpt_geom, invTranspose), "geom record layouts");
+static_assert(sizeof(orc_material) == 56, "file record sizes");
+
+static bool read_file(const char* path, std::vector<char>& out) {
+  FILE* f = fopen(path, "rb");
+  if (!f) return false;
+  fseek(f, 0, SEEK_END);
+  const long n = ftell(f);
+  fseek(f, 0, SEEK_SET);
+  out.resize((size_t)n);
+  const bool ok = n == 0 || fread(out.data(), 1, (size_t)n, f) == (size_t)n;
+  fclose(f);
+  return ok;
+}
+
+// tests/soups.py write_desc's file into an orc_scene_desc whose arrays point into `buf` (as geom_diff.cpp)
+static bool parse_desc(const std::vector<char>& buf, orc_scene_desc& d) {
+  size_t at = 0;
+  bool ok = true;
+  auto take = [&](size_t bytes) -> const char* {
+    if (at + bytes > buf.size()) { ok = false; return buf.data(); }
+    const char* p = buf.data() + at;
+    at += bytes;
+    return p;
+  };
+  auto geti = [&]() { int v = 0; memcpy(&v, take(4), ok ? 4 : 0); return v; };
+  memset(&d, 0, sizeof d);
+  d.res[0] = geti(); d.res[1] = geti();
+  memcpy(&d.fovy, take(4), ok ? 4 : 0);
+  d.iterations = geti(); d.traceDepth = geti();
+  memcpy(d.eye, take(12), ok ? 12 : 0); memcpy(d.lookAt, take(12), ok ? 12 : 0); memcpy(d.up, take(12), ok ? 12 : 0);
+  d.num_materials = geti();
+  if (!ok || d.num_materials < 0) return false;
+  d.materials = (const orc_material*)take(sizeof(orc_material) * (size_t)d.num_materials);
+  d.num_geoms = geti();
+  if (!ok || d.num_geoms < 0) return false;
+  d.geom_type = (const int*)take(4 * (size_t)d.num_geoms);
+  d.geom_material = (const int*)take(4 * (size_t)d.num_geoms);
+  d.geom_trs = (const float*)take(36 * (size_t)d.num_geoms);
+  d.ntri = geti();
+  if (!ok || d.ntri < 0) return false;
+  d.verts9 = (const float*)take(36 * (size_t)d.ntri);
+  d.norms9 = (const float*)take(36 * (size_t)d.ntri);
+  d.shape_of_tri = (const int*)take(4 * (size_t)d.ntri);
+  d.num_shapes = geti();
+  if (!ok || d.num_shapes < 0) return false;
+  d.shape_materials = (const orc_material*)take(sizeof(orc_material) * (size_t)d.num_shapes);
+  return ok && at == buf.size();
+}
+
+struct Rays {
+  std::vector<char> buf;
+  int n = 0;
+  const float* O = nullptr;
+  const float* D = nullptr;
+  bool load(const char* path) {
+    if (!read_file(path, buf) || buf.size() < 4) return false;
+    memcpy(&n, buf.data(), 4);
+    if (n < 0 || buf.size() != 4 + 24 * (size_t)n) return false;
+    O = (const float*)(buf.data() + 4);
+    D = O + 3 * (size_t)n;
+    return true;
+  }
+};
+
+int main(int argc, char** argv) {
+  if (argc < 3) return 2;
+  std::vector<char> desc_buf;
+  orc_scene_desc d;
+  if (!read_file(argv[1], desc_buf) || !parse_desc(desc_buf, d)) return 3;
+  d.ntri = 0;  // the analytic geoms alone
+  d.num_shapes = 0;
+  orc_scene s;
+  if (orc_build_scene(&d, &s)) return 3;
+  const int ng = s.num_geoms;
+
+  if (strcmp(argv[2], "--first-hits") == 0) {
+    if (argc != 5) return 2;
+    Rays R;
+    if (!R.load(argv[3])) return 5;
+    FILE* out = fopen(argv[4], "wb");
+    if (!out) return 4;
+    fwrite(&R.n, 4, 1, out);
+    for (long r = 0; r < R.n; r++) {
+      double ref[14];
+      orc_trace_ray(&s, R.O + 3 * r, R.D + 3 * r, 1, ref);
+      const int g = (int)ref[1];
+      const int rec_i[2] = {g, g >= 0 ? s.geoms[g].type : -1};
+      const float rec_f[6] = {(float)ref[2], (float)ref[3], (float)ref[4], (float)ref[5], (float)ref[6], (float)ref[7]};
+      fwrite(rec_i, 4, 2, out);
+      fwrite(rec_f, 4, 6, out);
+    }
+    fclose(out);
+    orc_free_scene(&s);
+    return 0;
+  }
+
+  std::vector<orc_scene> alone((size_t)ng);  // each geom as a scene of its own: the oracle's exact test of it
+  for (int g = 0; g < ng; g++) {
+    orc_scene_desc one = d;
+    one.num_geoms = 1;
+    one.geom_type = d.geom_type + g;
+    one.geom_material = d.geom_material + g;
+    one.geom_trs = d.geom_trs + 9 * (size_t)g;
+    if (orc_build_scene(&one, &alone[(size_t)g])) return 3;
+  }
+  std::vector<DevGeom> geoms((size_t)ng);
+  for (int i = 0; i < ng; i++) {
+    kdpt_geom g;
+    memcpy(&g, &s.geoms[i], sizeof g);
+    geoms[(size_t)i] = prepare_geom(g);
+  }
+  DevScene S{};
+  S.geoms = geoms.data();
+  S.num_geoms = ng;
+  S.num_materials = s.num_materials;
+  geoms_safe_region(geoms.data(), ng, S.gc, S.gh);
+  long total_bad = 0;
+  for (int a = 2; a < argc; a++) {
+    const char* eq = strchr(argv[a], '=');
+    if (!eq) return 2;
+    const std::string name(argv[a], (size_t)(eq - argv[a]));
+    Rays R;
+    if (!R.load(eq + 1)) return 5;
+    long bad = 0, hits = 0, ordered = 0, false_miss = 0, ruled_out = 0, boxes = 0, left_behind = 0;
+    memset(g_prep_events, 0, sizeof g_prep_events);
+    for (long r = 0; r < R.n; r++) {
+      const float* o = R.O + 3 * r;
+      const float* dd = R.D + 3 * r;
+      const f3 fo = mk3(o[0], o[1], o[2]), fd = mk3(dd[0], dd[1], dd[2]);
+      double ref[14];
+      orc_trace_ray(&s, o, dd, 1, ref);
+      float t_min = 0.0f;
+      int hit = -2;
+      (void)prep_ray(S, false, fo, fd, t_min, hit);
+      if (ng <= ORDERED_GEOMS && geoms_hold_for(S, fo) && std::isfinite(1.0f / dd[0]) && std::isfinite(1.0f / dd[1]) &&
+          std::isfinite(1.0f / dd[2]))
+        ordered++;
+      const float want_t = (float)ref[0];
+      const int want = (int)ref[1];
+      if (want >= 0) hits++;
+      if (hit != want || memcmp(&t_min, &want_t, 4) != 0) {
+        if (bad < 5) printf("mismatch %s ray %ld: geom %d/%d t %.9g/%.9g\n", name.c_str(), r, hit, want, t_min, want_t);
+        bad++;
+      }
+      // the pre-test on its own, per (ray, box), against the oracle's test of that box alone
+      bool left = false;
+      for (int g = 0; g < ng; g++) {
+        const DevGeom& G = geoms[(size_t)g];
+        if (G.type != 1) continue;
+        boxes++;
+        const bool missed = box_provably_missed(G, fo, fd);
+        const bool holds = o[0] >= G.wlo[0] && o[0] <= G.whi[0] && o[1] >= G.wlo[1] && o[1] <= G.whi[1] &&
+                           o[2] >= G.wlo[2] && o[2] <= G.whi[2];
+        if (!missed && !holds) continue;
+        double one[14];
+        orc_trace_ray(&alone[(size_t)g], o, dd, 1, one);
+        const bool oracle_hits = (int)one[1] == 0 && (float)one[0] > 0.0f;
+        if (missed) {
+          ruled_out++;
+          if (oracle_hits) {
+            if (false_miss < 5) printf("false miss %s ray %ld geom %d: the oracle's t %.9g\n", name.c_str(), r, g, one[0]);
+            false_miss++;
+          }
+        }
+        if (holds && !oracle_hits) left = true;
+      }
+      if (left) left_behind++;
+    }
+    printf("{\"gen\": \"%s\", \"rays\": %d, \"mismatches\": %ld, \"false_miss\": %ld, \"hits\": %ld, \"ordered\": %ld, "
+           "\"boxes\": %ld, \"ruled_out\": %ld, \"left_behind\": %ld, \"exact\": %ld, \"pre_miss\": %ld, \"pre_abstain\": %ld}\n",
+           name.c_str(), R.n, bad, false_miss, hits, ordered, boxes, ruled_out, left_behind, g_prep_events[0],
+           g_prep_events[1], g_prep_events[2]);
+    total_bad += bad + false_miss;
+  }
+  for (orc_scene& a : alone) orc_free_scene(&a);
+  orc_free_scene(&s);
+  return total_bad ? 1 : 0;
+}
