@@ -534,7 +534,7 @@ int kdpt_selftest_rng(const int *iter_idx_depth, int n, int k, float *u_out);
  * 2 engine(seed) of raw uint32 seeds.  Pinned to rocThrust by tests/golden/ref_pins.json. */
 int kdpt_selftest_rng_draws(int mode, const uint32_t *in, int n, int k, float *out);
 int kdpt_selftest_fresnel(const float *cosines, int n, float ior, float *f_out);
-/* The glm pieces on the path (kdpt_device.h glm_kat, vendored glm 0.9.6.3 restated): fn 0
+/* The glm pieces on the path (kdpt_glm_kat.h glm_kat, vendored glm 0.9.6.3 restated): fn 0
  * intersectRayTriangle (15 floats in -> {passed, bary.xyz}; `out` holds sentinels on entry, kept where
  * glm leaves bary unwritten), 1 normalize (3 -> 3), 2 reflect (6 -> 3), 3 refract (7 -> 3),
  * 4 glm::rotate(quat, vec3) (7 -> 3).  Run on the device. */

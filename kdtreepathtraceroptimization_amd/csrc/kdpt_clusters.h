@@ -17,7 +17,8 @@
 #include <vector>
 
 #include "../../include/kdpt.h"
-#include "kdpt_device.h"
+#include "kdpt_scene.h"
+#include "kdpt_cull.h"
 
 namespace kdpt {
 
@@ -604,7 +605,7 @@ inline int dir_mask_resolution(int ncl, size_t budget = (size_t)640 << 20) {
 
 // The brute-force route's boxes of 64 file-order triangles [64j, 64j + 64): the triangles glm tests,
 // v0, v0 + e1, v0 + e2, exact in double and rounded outward to float (BruteArgs::chunk_lo / chunk_hi), and in
-// chunk_lo[j].w the coefficient the chunk is culled at (kdpt_device.h brute_chunk_may_pass): the rigorous one of
+// chunk_lo[j].w the coefficient the chunk is culled at (kdpt_cull.h brute_chunk_may_pass): the rigorous one of
 // the chunk's own triangles, 8.75 max |e1||e2| + 64 u (1 + max|coord| + max|e|) as cluster_margin (below) forms the
 // scene's, rounded up -- so the chunk cull drops no triangle that passes glm's u/v tests, for any line.  The route
 // has no direction masks, so nothing smaller is exact.  At a coefficient K >= 1 the widened box

@@ -553,7 +553,7 @@ void apply_cull_route(kdpt_ctx* c) {
   c->S.mask_n = c->masks.n;
   c->S.cl_tn = c->masks.tn.get();
 }
-// The masked cull's cells on the device (kdpt_device.h dir_mask_cell, the code the host builder runs): one
+// The masked cull's cells on the device (kdpt_cull.h dir_mask_cell, the code the host builder runs): one
 // workgroup per (cluster, 256 buckets), the cluster's 64 entries staged in LDS (every lane reads the same entry:
 // a broadcast), one mask per lane, written bucket-major.
 __global__ void __launch_bounds__(256) k_build_masks(const double* __restrict__ ent, const float* __restrict__ krig,
@@ -581,7 +581,7 @@ int build_masks(kdpt_ctx* c, int n) {
   const auto t0 = std::chrono::steady_clock::now();
   const ClusterSet& cs = *c->masks.cs;
   const int ncl = (int)cs.info.size(), nb = 6 * n * n;
-  // the intersect kernel indexes the table with 32 bits (kdpt_device.h, S.cl_mask[bucket * num_clusters + c]): a
+  // the intersect kernel indexes the table with 32 bits (kdpt_trace_phase.h, S.cl_mask[bucket * num_clusters + c]): a
   // resolution whose table has 2^32 cells or more is refused here, before anything is freed or allocated
   if (n < 1 || (unsigned long long)nb * (unsigned long long)ncl >= (1ull << 32))
     return fail(KDPT_ERR_ARG, "direction masks: 6 n^2 num_clusters must be below 2^32 (n = " + std::to_string(n) +
@@ -1872,7 +1872,6 @@ int launch_batch(kdpt_ctx* c, IterState* const* its, const int* iters, int nb, h
   B.shade.S = c->S;
   B.shade.softness = c->opt.softness;
   B.shade.enable_sss = c->opt.enable_sss;
-  B.shade.tile_kcounts = nullptr;
   B.shade.ntiles = c->ntiles;
   B.shade.nkeys = c->nkeys;
   B.shade.trace_t = its[0]->trace_t;

@@ -1,6 +1,6 @@
 // kdpt_scene_prep.h -- everything kdpt_create does with a caller's kdpt_scene before it touches a device:
 // whether the (untrusted) scene and options are accepted, and the conversion of the scene into the arrays and
-// numbers the kernels read (DevScene, kdpt_device.h).  Host code only: no HIP runtime header, no HIP call, no
+// numbers the kernels read (DevScene, kdpt_scene.h).  Host code only: no HIP runtime header, no HIP call, no
 // globals.  Included by kdpt_runtime.hip under hipcc, which only uploads what prepare_scene returns, and by the
 // native test programs under g++ (tests/native/scene_prep_host.cpp runs it under ASan + UBSan;
 // asan_host.cpp, traverse_diff.cpp and cull_diff.cpp take the product's wide node and triangle arrays from
@@ -121,7 +121,7 @@ inline void pack_triangles(const kdpt_tri_bare* T, int nt, TriArrays& out) {
   }
 }
 
-// NodesPacked records (kdpt_device.h); false when the tree does not fit the format.
+// NodesPacked records (kdpt_trace_phase.h); false when the tree does not fit the format.
 inline bool pack_nodes(const kdpt_node_bare* N, int nn, const std::vector<int2>& leaf_cl, std::vector<int4>& out) {
   if (nn >= 0xffff) return false;
   out.assign(2 * (size_t)nn, make_int4(0, 0, 0, 0));
@@ -143,7 +143,7 @@ inline bool pack_nodes(const kdpt_node_bare* N, int nn, const std::vector<int2>&
   return true;
 }
 
-// NodesDerived records (kdpt_device.h); false unless every node's box is its parent's with exactly the one
+// NodesDerived records (kdpt_trace_phase.h); false unless every node's box is its parent's with exactly the one
 // coordinate the reference's split replaces (checked bit for bit), both children write the same centre, and
 // the tree fits the 16-bit links.
 inline bool pack_nodes16(const kdpt_node_bare* N, int nn, const std::vector<int2>& leaf_cl, std::vector<int4>& out) {
@@ -216,7 +216,7 @@ inline void choose_clusters(const kdpt_node_bare* nodes, int nn, const kdpt_tri_
 }
 
 // The Chebyshev distance from a geom's enlarged bounds within which a ray origin may rely on them: the largest R
-// of a halving sequence for which the exact test's error, bounded as kdpt_device.h derives it ("The analytic
+// of a halving sequence for which the exact test's error, bounded as kdpt_geoms.h derives it ("The analytic
 // geoms' bounds"), fits the margin; -inf when none does.  m, mi: transform and inverseTransform (column-major);
 // lo, hi: the exact world bounds.
 inline float geom_safe_range(int type, const float* m, const float* mi, const double* lo, const double* hi,
@@ -250,7 +250,7 @@ inline float geom_safe_range(int type, const float* m, const float* mi, const do
     double Dq[3];
     for (int j = 0; j < 3; j++) Dq[j] = gi[j] * reach + std::fabs(e[j]) + 1.0;  // object-space coordinates up to the hit
     // (c): the origin's object-space distance, |inverse (o - centre)| <= |inverse|_F sqrt(3) (R + margin + ext / 2);
-    // radius^2 grows by at most 16 u (D + 1)^2 (kdpt_device.h), the radius 0.5 by no more than that
+    // radius^2 grows by at most 16 u (D + 1)^2 (kdpt_geoms.h), the radius 0.5 by no more than that
     const double D2 = 1.7320508075688772 * (fro * (R + margin + 0.5 * ext) + emax) + 1.0;
     const double radicand = type == 0 ? 16.0 * u * D2 * D2 : 0.0;
     double dq[3];

@@ -1,5 +1,5 @@
 // kernels_gen.h -- the path buffers, camera rays (generateRayFromCamera), the intersect stage's launch records and tree
-// modes and the analytic-geom stage (k_gen_rays_b, k_geoms_b, k_gen_geoms_b; its per-ray part, prep_ray, is in kdpt_device.h).
+// modes and the analytic-geom stage (k_gen_rays_b, k_geoms_b, k_gen_geoms_b; its per-ray part, prep_ray, is in kdpt_geoms.h).
 //
 // A section of kdpt_runtime.hip's translation unit, not a stand-alone header: kdpt_runtime.hip includes it
 // after kdpt_runtime.hip's own head, and the kernels keep that order in the code object.  Device code and launch-argument

@@ -24,7 +24,6 @@ struct ShadeArgs {
   float softness;
   int enable_sss;
   int* tile_counts;  // [ntiles] or key-major [MAX_KEYS][ntiles] when sorting
-  int* tile_kcounts;  // key-major [TRACE_KEYS][ntiles] survivors per trace-order class, or null
   int ntiles;
   int nkeys;
   unsigned long long* total_segments;  // running sum of paths launched into the intersect kernel
@@ -169,8 +168,7 @@ __device__ inline void count_prep(const ShadeArgs& A, bool tested, bool walk) {
   if ((threadIdx.x & 63) == 0 && wm) atomicAdd(&A.count_aabb->cand, (unsigned long long)__popcll(wm));
 }
 
-// Shading in place, then k_scan + k_scatter (the material sort of iteration 2, no compaction, or the
-// trace-order classes).
+// Shading in place, then k_scan + k_scatter (the material sort of iteration 2, or no compaction).
 template <bool HYBRID, bool COMPACT, bool SORT>
 __global__ __launch_bounds__(TILE) void k_shade(ShadeArgs A) {
   const int n = A.counts[A.depth];
@@ -179,13 +177,10 @@ __global__ __launch_bounds__(TILE) void k_shade(ShadeArgs A) {
   const int i = tile * TILE + threadIdx.x;
   if (i == 0) shade_stats(A, n);
   __shared__ int s_hist[MAX_KEYS];
-  __shared__ int s_khist[TRACE_KEYS];
   if (SORT) {
     for (int k = threadIdx.x; k < MAX_KEYS; k += TILE) s_hist[k] = 0;
+    __syncthreads();
   }
-  if (COMPACT && A.tile_kcounts && threadIdx.x < TRACE_KEYS) s_khist[threadIdx.x] = 0;
-  if (SORT || (COMPACT && A.tile_kcounts)) __syncthreads();
-  const DevScene& S = A.S;
   bool alive = false, walk = false, tested = false;
   int key = 0;
   if (i < n) {
@@ -204,12 +199,6 @@ __global__ __launch_bounds__(TILE) void k_shade(ShadeArgs A) {
     tested = o.tested;
     key = o.pm;
     if (COMPACT && A.prep_on && alive) A.prep[i] = make_int2(fbits(o.tm), (o.gh + 1) | (walk ? 0x10000 : 0));
-    if (COMPACT && A.tile_kcounts && alive)
-      atomicAdd(&s_khist[trace_class(S, mk3(o.q0.x, o.q0.y, o.q0.z), mk3(o.q1.x, o.q1.y, o.q1.z))], 1);
-  }
-  if (COMPACT && A.tile_kcounts) {
-    __syncthreads();
-    if (threadIdx.x < TRACE_KEYS) A.tile_kcounts[threadIdx.x * A.ntiles + tile] = s_khist[threadIdx.x];
   }
   if (SORT) {
     if (alive) atomicAdd(&s_hist[key], 1);

@@ -2,7 +2,7 @@
 //   asan_host SCENE.txt OBJ|- NRAYS
 // Parses the scene and OBJ with the product's C++ parsers and builds the KD tree (csrc/scene_host.cpp),
 // encodes a PNG and an HDR of a small image (csrc/image_io.cpp), and walks NRAYS random rays through the
-// compact-state traversal (csrc/kdpt_device.h compiled for the host).  Exits non-zero on a parse error
+// compact-state traversal (csrc/kdpt_traverse.h compiled for the host).  Exits non-zero on a parse error
 // code; the sanitizers abort on any memory or UB finding.  Prints a JSON summary; for a refused input it holds
 // the code and kdpt_last_error()'s message.
 #include <cstdio>
@@ -13,6 +13,7 @@
 
 #include "kdpt.h"
 #include "../../kdtreepathtraceroptimization_amd/csrc/kdpt_scene_prep.h"
+#include "../../kdtreepathtraceroptimization_amd/csrc/kdpt_traverse.h"
 
 using namespace kdpt;
 

@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE: differential test of the intersect kernel's cluster cull (kdpt_device.h
+// TEST INFRASTRUCTURE: differential test of the intersect kernel's cluster cull (kdpt_cull.h
 // cluster_may_pass / cluster_may_pass_slab, the half-precision super-cluster boxes, and the brute-force
 // route's chunk boxes; all compiled here for the host) against glm's float u/v tests (tri_test_v, pinned
 // bit for bit to the reference's glm::intersectRayTriangle, gtx/intersect.inl:37-74).
@@ -20,6 +20,8 @@
 
 #define KDPT_RCP_ULP  // kd_rcp follows kdpt_rcp_ulp (the device reciprocal's 1-ulp error)
 #include "../../kdtreepathtraceroptimization_amd/csrc/kdpt_scene_prep.h"
+#include "../../kdtreepathtraceroptimization_amd/csrc/kdpt_cull.h"
+#include "../../kdtreepathtraceroptimization_amd/csrc/kdpt_traverse.h"
 
 // the masked cull's box coefficient and mask resolution: the product's (cluster_margin, dir_mask_resolution)
 // unless MASK_KF / MASK_N say otherwise
@@ -185,7 +187,7 @@ double bound_ratio(f3 o, f3 d, float4 v0, float4 e1, float4 e2, float bx, float 
   return (double)(std::sqrt(dist2) / bound);
 }
 
-// The product's masked cull (kdpt_device.h trace_phase, one-level route) for a (line, cluster) pair whose line
+// The product's masked cull (kdpt_trace_phase.h cull_one_level) for a (line, cluster) pair whose line
 // missed the cluster's fast-margin box or oriented box: the pair's cell (dir_bucket) and its danger mask, and the
 // mask's triangles that danger_needs_test keeps (those get glm's u/v tests).
 struct MaskTables {
@@ -567,7 +569,7 @@ int main(int argc, char** argv) {
       const bool pass = any_pass(&cs.cv0[inf.x], &cs.ce1[inf.x], &cs.ce2[inf.x], inf.y, &L, &H);
       if (!fast) {
         C.nofast++;
-        continue;  // the wave runs no cull at all (kdpt_device.h trace_phase: fastAABB)
+        continue;  // the wave runs no cull at all (kdpt_trace_phase.h trace_phase: fastAABB)
       }
       const bool box = cluster_may_pass(L, H, of, inv, K);
       if (!box) C.culled_box++;

@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE: differential test of the product's analytic-geom stage (kdpt_device.h prep_ray: the
+// TEST INFRASTRUCTURE: differential test of the product's analytic-geom stage (kdpt_geoms.h prep_ray: the
 // nearest-first loop over geom_entry_bound for at most ORDERED_GEOMS geoms, the index-order loop with the
 // geom_may_hit skip above that, over kdpt_scene_prep.h prepare_geom's bounds; all compiled here for the host)
 // against the oracle's plain index-order loop (orc_trace_ray, oracle/liboracle.so): the winning geom and the
@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../kdtreepathtraceroptimization_amd/csrc/kdpt_scene_prep.h"
+#include "../../kdtreepathtraceroptimization_amd/csrc/kdpt_geoms.h"
 extern "C" {
 #include "../../oracle/kdpt_oracle.h"
 }

@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE: the analytic-geom stage's box pre-test (kdpt_device.h box_provably_missed and the pre-pass
+// TEST INFRASTRUCTURE: the analytic-geom stage's box pre-test (kdpt_geoms.h box_provably_missed and the pre-pass
 // of prep_ray's nearest-first branch), compiled for the host, against the oracle (oracle/liboracle.so).
 //   geom_pretest_diff DESC NAME=RAYS ...
 //   geom_pretest_diff DESC --first-hits RAYS OUT
@@ -10,7 +10,7 @@
 //                that box alone (a one-geom oracle scene) returns t > 0 -- every box of every ray, whatever its
 //                bounds say;
 //   ruled_out    (ray, box) pairs the pre-test rules out, of `boxes` pairs in all;
-//   exact, pre_miss, pre_abstain   what prep_ray did, counted through kdpt_device.h's KDPT_PREP_EVENT hook (defined
+//   exact, pre_miss, pre_abstain   what prep_ray did, counted through kdpt_geoms.h's KDPT_PREP_EVENT hook (defined
 //                here, so in this program alone): exact tests run, pre-tests that ruled a box out / abstained;
 //   left_behind  rays with a box whose enlarged bounds hold the origin and which the oracle's test of that box
 //                alone misses: the rays the pre-pass exists for;
@@ -28,6 +28,7 @@
 static long g_prep_events[3];
 #define KDPT_PREP_EVENT(kind, geom) (g_prep_events[(kind)]++)
 #include "../../kdtreepathtraceroptimization_amd/csrc/kdpt_scene_prep.h"
+#include "../../kdtreepathtraceroptimization_amd/csrc/kdpt_geoms.h"
 extern "C" {
 #include "../../oracle/kdpt_oracle.h"
 }

@@ -1,11 +1,11 @@
-// TEST INFRASTRUCTURE: the product's glm restatements (kdpt_device.h glm_kat, compiled here for the
+// TEST INFRASTRUCTURE: the product's glm restatements (kdpt_glm_kat.h glm_kat, compiled here for the
 // host with the device build's numerics flags) on a known-answer input file.
 //   glm_host FN N IN.f32 OUT.f32   (OUT is read first: fn 0's bary sentinels) -> OUT rewritten
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
-#include "../../kdtreepathtraceroptimization_amd/csrc/kdpt_device.h"
+#include "../../kdtreepathtraceroptimization_amd/csrc/kdpt_glm_kat.h"
 
 int main(int argc, char** argv) {
   if (argc != 5) return 2;

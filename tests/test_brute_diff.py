@@ -1,7 +1,7 @@
 """Host differential of the brute-force intersect route (enable_kd = 0, kernels_brute.h k_brute).
 
 k_brute is the reference's loop over every OBJ triangle with two shortcuts: a lane skips a 64-triangle file-order
-chunk whose box its line misses (kdpt_device.h brute_chunk_may_pass, the box widened by the chunk's own rigorous
+chunk whose box its line misses (kdpt_cull.h brute_chunk_may_pass, the box widened by the chunk's own rigorous
 coefficient), and it rejects a triangle without glm's division when glm's answer is certain (tri_certain_miss).
 tests/native/brute_diff.cpp compiles both for the host, calls kdpt_scene_prep.h prepare_brute on the scene's raw
 OBJ arrays -- so it runs on the kernel's triangles, chunk boxes, coefficients and shapes, in file order -- and checks,

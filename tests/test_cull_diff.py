@@ -1,6 +1,6 @@
 """Host differential test of the intersect kernel's cluster cull ("Cluster cull").
 
-The cull (kdpt_device.h cluster_may_pass / cluster_may_pass_slab, the half-precision super-cluster boxes and the
+The cull (kdpt_cull.h cluster_may_pass / cluster_may_pass_slab, the half-precision super-cluster boxes and the
 brute-force route's chunk boxes, compiled here for the host by tests/native/cull_diff.cpp) may drop a
 (line, cluster) pair only when no triangle of the cluster passes glm's float u/v tests for that line -- with
 any t, since a pass with t < 0 still writes bary.z, which the reference's traversal reads

@@ -1,4 +1,4 @@
-"""Host differential test of the analytic-geom stage: the product's prep_ray (kdpt_device.h: the nearest-first loop
+"""Host differential test of the analytic-geom stage: the product's prep_ray (kdpt_geoms.h: the nearest-first loop
 over geom_entry_bound, the index-order loop with the geom_may_hit skip; kdpt_scene_prep.h prepare_geom's bounds),
 compiled for the host, against the oracle's plain index-order loop on the adversarial scenes and generators of
 tests/geoms.py: the winning geom and the bits of t, 400 000 rays per (scene, generator).  No reference file is read."""

@@ -1,4 +1,4 @@
-"""Host differential test of the analytic-geom stage's box pre-test (kdpt_device.h: box_provably_missed and the
+"""Host differential test of the analytic-geom stage's box pre-test (kdpt_geoms.h: box_provably_missed and the
 pre-pass of prep_ray's nearest-first branch), compiled for the host (tests/native/geom_pretest_diff.cpp), against the
 oracle: prep_ray's winner and the bits of its t against the oracle's index-order loop, and the pre-test's verdict
 per (ray, box) against the oracle's exact test of that box alone -- on every scene and generator of tests/geoms.py

@@ -1,4 +1,4 @@
-"""The analytic-geom stage's box pre-test (kdpt_device.h box_provably_missed, the pre-pass of prep_ray) on the GPU,
+"""The analytic-geom stage's box pre-test (kdpt_geoms.h box_provably_missed, the pre-pass of prep_ray) on the GPU,
 against the CPU oracle, bit for bit: renders of the cornell fixture through every producer that calls prep_ray
 (k_gen_geoms_b at bounce 0, the fused shading's hand-off, iteration 2's k_scatter hand-off), of the adversarial scenes
 of tests/geoms.py (rotated boxes, ties, origins inside a box, refraction), and ray queries with origins where a bounce

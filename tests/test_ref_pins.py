@@ -67,7 +67,7 @@ def test_glm_oracle_and_host_device_source_equal_reference(oracle, glm_host, fn)
     orc = oracle.glm_array(fn, x, K.glm_sentinels(fn, len(x)))
     assert K.sha256(orc) == want, "oracle"
     host = _glm_host(glm_host, fn, x)
-    assert K.sha256(host) == want, "kdpt_device.h glm_kat compiled for the host"
+    assert K.sha256(host) == want, "kdpt_glm_kat.h glm_kat compiled for the host"
 
 
 def test_glm_nan_values_only_where_glm_makes_them():

@@ -2,7 +2,7 @@
 restatement under ASan/UBSan; the product's host code parses untrusted OBJ/MTL/scene text).
 
 - tests/native/asan_host.cpp + the product's csrc/scene_host.cpp + csrc/image_io.cpp + the traversal of
-  csrc/kdpt_device.h compiled for the host, all sanitized, over the edge OBJs of test_host_builder.py,
+  csrc/kdpt_traverse.h compiled for the host, all sanitized, over the edge OBJs of test_host_builder.py,
   malformed OBJ and scene files (missing/short normal lists, out-of-range, zero and negative indices,
   truncated faces, garbage, NaN/inf coordinates, a 200 kB line, a missing mtllib) and, where present,
   the reference's own meshes: each input is either built or refused with an error code and a message

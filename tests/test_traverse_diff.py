@@ -1,5 +1,5 @@
 """Host differential test: the product's compact visited-state KD traversal
-(kdpt_device.h traverseKD, compiled for the host) against the oracle's literal
+(kdpt_traverse.h traverseKD, compiled for the host) against the oracle's literal
 visited-bitmap restatement of traverseKDbareShortHybrid / traverseKDbare
 (src/pathtrace.cu) on random rays: every hit field bit-exact."""
 import json
