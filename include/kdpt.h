@@ -539,6 +539,16 @@ int kdpt_selftest_fresnel(const float *cosines, int n, float ior, float *f_out);
  * glm leaves bary unwritten), 1 normalize (3 -> 3), 2 reflect (6 -> 3), 3 refract (7 -> 3),
  * 4 glm::rotate(quat, vec3) (7 -> 3).  Run on the device. */
 int kdpt_selftest_glm(int fn, const float *in, int n, float *out);
+/* The bounce as units, run on the device, one record of 32-bit words per lane (float unless said otherwise;
+ * csrc/kdpt_bounce_kat.h).  scatter: scatterRay (src/interactions.h:195-358) with engine(seed) -- in: origin 0-2,
+ * direction 3-5, isinside 6 (0 / 1), sdepth 7, intersect 8-10, normal 11-13, hasReflective 14, hasRefractive 15,
+ * indexOfRefraction 16, transmittance 17-19, softness 20, seed 21 (uint32); out: origin 0-2, direction 3-5,
+ * isinside 6, sdepth 7, the engine's next u01 draw 8.  shade: shadeMaterial's body (src/pathtrace.cu:2318-2366)
+ * -- in: t 0, colour 1-3, specular colour 4-6, hasReflective 7, hasRefractive 8, emittance 9, transmittance
+ * 10-12, enable_sss 13 (0 / 1), sdepth 14, path colour 15-17, remainingBounces 18 (int32); out: path colour 0-2,
+ * remainingBounces 3 (int32). */
+int kdpt_selftest_scatter(const float *in, int n, float *out);
+int kdpt_selftest_shade(const float *in, int n, float *out);
 /* The scatter's glibc calls as restated for gfx950 (src/interactions.h:67-83,214): fn 0 acosf(x),
  * 1 sin((double)x), 2 cos((double)x); results as doubles. */
 int kdpt_selftest_libm(int fn, const float *x, int n, double *out);

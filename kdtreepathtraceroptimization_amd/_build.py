@@ -31,7 +31,7 @@ COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "
 DEVICE_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 # the sources whose device code the runtime's kernels are compiled from
 KERNEL_SOURCES = ["kdpt_device.h", "kdpt_scene.h", "kdpt_geoms.h", "kdpt_traverse.h", "kdpt_cull.h", "kdpt_wave.h",
-                  "kdpt_trace_phase.h", "kdpt_scatter.h", "kdpt_glm_kat.h",
+                  "kdpt_trace_phase.h", "kdpt_scatter.h", "kdpt_glm_kat.h", "kdpt_bounce_kat.h",
                   "kdpt_math.h", "kdpt_runtime.hip", "glibc_sincostab.h", "kernels_gen.h",
                   "kernels_trace.h", "kernels_brute.h", "kernels_shade.h", "kernels_image.h", "kernels_cast.h",
                   "kernels_rays.h", "kernels_selftest.h", "kernels_moments.h"]

@@ -16,3 +16,4 @@
 #endif
 #include "kdpt_scatter.h"  // scatterRay, shade
 #include "kdpt_glm_kat.h"  // glm known-answer table
+#include "kdpt_bounce_kat.h"  // scatterRay / shade / geom tests on known-answer records

@@ -1627,6 +1627,32 @@ int kdpt_selftest_glm(int fn, const float* in, int n, float* out) {
   return KDPT_OK;
 }
 
+namespace {
+// one record of `ni` words in, `no` words out per lane
+int kdpt_selftest_records(void (*kernel)(const float*, int, float*), const char* what, int ni, int no, const float* in,
+                     int n, float* out) {
+  if (n < 0 || (n && (!in || !out))) return fail(KDPT_ERR_ARG, what);
+  if (!n) return KDPT_OK;
+  DeviceBuf<float> din, dout;
+  HIP_TRY(din.alloc(ni * (size_t)n));
+  HIP_TRY(dout.alloc(no * (size_t)n));
+  HIP_TRY(hipMemcpy(din.get(), in, sizeof(float) * ni * (size_t)n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(kernel, dim3((n + 255) / 256), dim3(256), 0, 0, din.get(), n, dout.get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, dout.get(), sizeof(float) * no * (size_t)n, hipMemcpyDeviceToHost));
+  return KDPT_OK;
+}
+}  // namespace
+
+int kdpt_selftest_scatter(const float* in, int n, float* out) {
+  return kdpt_selftest_records(k_selftest_scatter, "bad scatter selftest arguments", SCATTER_KAT_IN, SCATTER_KAT_OUT, in,
+                          n, out);
+}
+
+int kdpt_selftest_shade(const float* in, int n, float* out) {
+  return kdpt_selftest_records(k_selftest_shade, "bad shade selftest arguments", SHADE_KAT_IN, SHADE_KAT_OUT, in, n, out);
+}
+
 int kdpt_selftest_fresnel(const float* cs, int n, float ior, float* f) {
   DeviceBuf<float> dc, df;
   HIP_TRY(dc.alloc(n));

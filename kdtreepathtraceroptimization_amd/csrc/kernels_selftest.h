@@ -1,4 +1,4 @@
-// kernels_selftest.h -- the kdpt_selftest_* entry points' kernels (device math, RNG, glm, Fresnel).
+// kernels_selftest.h -- the kdpt_selftest_* entry points' kernels (device math, RNG, glm, Fresnel, the bounce).
 //
 // A section of kdpt_runtime.hip's translation unit, not a stand-alone header: kdpt_runtime.hip includes it
 // after kernels_rays.h, and the kernels keep that order in the code object.  Device code and launch-argument
@@ -56,6 +56,17 @@ __global__ void k_selftest_glm(int fn, const float* in, int n, float* out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   glm_kat(fn, in + (size_t)glm_kat_inputs(fn) * i, out + (size_t)glm_kat_outputs(fn) * i);
+}
+// scatterRay / shade on one record per lane (kdpt_bounce_kat.h)
+__global__ void k_selftest_scatter(const float* in, int n, float* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  scatter_kat(in + (size_t)SCATTER_KAT_IN * i, out + (size_t)SCATTER_KAT_OUT * i);
+}
+__global__ void k_selftest_shade(const float* in, int n, float* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  shade_kat(in + (size_t)SHADE_KAT_IN * i, out + (size_t)SHADE_KAT_OUT * i);
 }
 __global__ void k_selftest_fresnel(const float* c, int n, float R0, float* f) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;

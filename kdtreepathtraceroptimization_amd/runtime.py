@@ -147,6 +147,7 @@ EXPORTS = [
     "kdpt_comm_library", "kdpt_cull_masks", "kdpt_cast_rays", "kdpt_cast_stats",
     "kdpt_set_camera", "kdpt_camera_rays", "kdpt_trace_rays", "kdpt_trace_rays_stats", "kdpt_shade_staged",
     "kdpt_set_moments", "kdpt_read_moments", "kdpt_noise_map", "kdpt_noise_estimate", "kdpt_trace_rays_moments",
+    "kdpt_selftest_scatter", "kdpt_selftest_shade",
 ]
 
 REDUCE_RCCL, REDUCE_COPY = 0, 1  # kdpt_render_sharded's reduce (KDPT_REDUCE_*)
@@ -240,6 +241,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.kdpt_set_options.argtypes = [C.c_void_p, P(Options)]
     if hasattr(lib, "kdpt_selftest_glm"):
         lib.kdpt_selftest_glm.argtypes = [C.c_int, P(C.c_float), C.c_int, P(C.c_float)]
+    if hasattr(lib, "kdpt_selftest_scatter"):  # absent from older builds used in A/B runs
+        lib.kdpt_selftest_scatter.argtypes = [P(C.c_float), C.c_int, P(C.c_float)]
+        lib.kdpt_selftest_shade.argtypes = [P(C.c_float), C.c_int, P(C.c_float)]
     if hasattr(lib, "kdpt_set_tuning"):  # absent from older builds used in A/B runs
         lib.kdpt_set_tuning.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
     if hasattr(lib, "kdpt_cast_rays"):  # absent from older builds used in A/B runs

@@ -502,8 +502,12 @@ static v3 soft_lobe(v3 dir, rng_t *rng) {
     v3 axis = vnormalize(vcross(V3(0.0f, 0.0f, -1.0f), dir));
     return rotateVector(v, axis, angle);
 }
-/* :195-358 */
-static void scatterRay(ray_t *ray, v3 intersect, v3 normal, const orc_material *m, rng_t *rng, float softness) {
+/* :195-358.  leaf (may be NULL; the render passes NULL): which leaf ran, ORC_LEAF_* of kdpt_oracle.h,
+ * + ORC_LEAF_SOFT when the soft lobe ran. */
+#define LEAF(code) do { if (leaf) *leaf = (code); } while (0)
+#define SOFT_LEAF() do { if (leaf) *leaf |= ORC_LEAF_SOFT; } while (0)
+static void scatterRay(ray_t *ray, v3 intersect, v3 normal, const orc_material *m, rng_t *rng, float softness,
+                       int *leaf) {
     if (m->transmittance[0] > 0.0f || m->transmittance[1] > 0.0f || m->transmittance[2] > 0.0f) {
         float randval = u01(rng);
         if (randval < 0.5f && !ray->isinside) {
@@ -514,10 +518,12 @@ static void scatterRay(ray_t *ray, v3 intersect, v3 normal, const orc_material *
             ray->origin = vadd(ray->origin, vscale(ray->direction, 0.0001f));
             ray->sdepth = vdistance(ray->origin, intersect);
             ray->isinside = 1;
+            LEAF(0);
         } else {
             ray->direction = calculateRandomDirectionInHemisphere(normal, rng);
             ray->origin = vadd(intersect, vscale(normal, 0.00001f));
             ray->sdepth = 0.0f;
+            LEAF(1);
         }
     } else if (m->hasRefractive != 0.0f) {
         float randval = u01(rng);
@@ -533,46 +539,56 @@ static void scatterRay(ray_t *ray, v3 intersect, v3 normal, const orc_material *
                 float val = u01(rng);
                 if (val < m->hasReflective) {
                     ray->direction = glm_reflect(ray->direction, normal);
-                    if (softness > 0.0f) ray->direction = soft_lobe(ray->direction, rng);
+                    LEAF(2);
+                    if (softness > 0.0f) { ray->direction = soft_lobe(ray->direction, rng); SOFT_LEAF(); }
                     ray->origin = vadd(intersect, vscale(normal, 0.00001f));
                 } else {
                     ray->direction = calculateRandomDirectionInHemisphere(normal, rng);
                     ray->origin = vadd(intersect, vscale(normal, 0.00001f));
+                    LEAF(3);
                 }
             } else {
                 float val = u01(rng);
                 if (val < m->hasRefractive) {
                     ray->direction = glm_refract(ray->direction, normal, ior);
-                    if (softness > 0.0f) ray->direction = soft_lobe(ray->direction, rng);
+                    LEAF(4);
+                    if (softness > 0.0f) { ray->direction = soft_lobe(ray->direction, rng); SOFT_LEAF(); }
                     ray->origin = vsub(intersect, vscale(normal, 0.001f));
                     ray->isinside = !ray->isinside;
                 } else {
                     ray->direction = calculateRandomDirectionInHemisphere(normal, rng);
                     ray->origin = vadd(intersect, vscale(normal, 0.00001f));
+                    LEAF(5);
                 }
             }
         } else {
             ray->direction = glm_reflect(ray->direction, normal);
             ray->origin = vadd(intersect, vscale(normal, 0.00001f));
             ray->isinside = 0;
+            LEAF(6);
         }
     } else if (m->hasReflective != 0.0f) {
         float randval = u01(rng);
         if (randval < m->hasReflective) {
             ray->direction = glm_reflect(ray->direction, normal);
-            if (softness > 0.0f) ray->direction = soft_lobe(ray->direction, rng);
+            LEAF(7);
+            if (softness > 0.0f) { ray->direction = soft_lobe(ray->direction, rng); SOFT_LEAF(); }
             ray->origin = vadd(intersect, vscale(normal, 0.0001f));
             ray->isinside = 0;
         } else {
             ray->direction = calculateRandomDirectionInHemisphere(normal, rng);
             ray->origin = vadd(intersect, vscale(normal, 0.00001f));
+            LEAF(8);
         }
     } else {
         ray->direction = calculateRandomDirectionInHemisphere(normal, rng);
         ray->origin = vadd(intersect, vscale(normal, 0.00001f));
         ray->isinside = 0;
+        LEAF(9);
     }
 }
+#undef LEAF
+#undef SOFT_LEAF
 
 /* ------------------------------------------------------------------ */
 /* KD traversals (src/pathtrace.cu:881-1020 and 1023-1235)               */
@@ -895,7 +911,7 @@ static void traceOneBounce(const orc_scene *s, const orc_opts *o, int depth, int
                 m = &s->materials[mid];
                 P->materialIdHit = mid;
                 ray_t r2 = path_ray(P);
-                scatterRay(&r2, h.intersect_point, h.normal, m, &rng, o->softness);
+                scatterRay(&r2, h.intersect_point, h.normal, m, &rng, o->softness, NULL);
                 path_set_ray(P, r2);
                 I->t = h.t_min;
                 I->materialId = mid;
@@ -2148,5 +2164,96 @@ void orc_geom_matrices(const float *trs, int n, float *out) {
         memcpy(out + 48 * (size_t)i, &tr, 64);
         memcpy(out + 48 * (size_t)i + 16, &inv, 64);
         memcpy(out + 48 * (size_t)i + 32, &it, 64);
+    }
+}
+
+/* The bounce as array functions (tests/kat_inputs.py has the record layouts; tests/test_bounce_pins.py).
+ * scatterRay on n records of 22 words -> 9 words each and the leaf that ran. */
+void orc_scatter_array(const float *in, int n, float *out, int *leaf) {
+#pragma omp parallel for schedule(static)
+    for (int i = 0; i < n; i++) {
+        const float *a = in + 22 * (size_t)i;
+        float *o = out + 9 * (size_t)i;
+        ray_t r;
+        r.origin = V3(a[0], a[1], a[2]);
+        r.direction = V3(a[3], a[4], a[5]);
+        r.isinside = a[6] != 0.0f;
+        r.sdepth = a[7];
+        orc_material m;
+        memset(&m, 0, sizeof m);
+        m.hasReflective = a[14]; m.hasRefractive = a[15]; m.indexOfRefraction = a[16];
+        m.transmittance[0] = a[17]; m.transmittance[1] = a[18]; m.transmittance[2] = a[19];
+        unsigned int seed;
+        memcpy(&seed, a + 21, 4);
+        rng_t rng = rng_seed(seed);
+        int code = -1;
+        scatterRay(&r, V3(a[8], a[9], a[10]), V3(a[11], a[12], a[13]), &m, &rng, a[20], &code);
+        o[0] = r.origin.x; o[1] = r.origin.y; o[2] = r.origin.z;
+        o[3] = r.direction.x; o[4] = r.direction.y; o[5] = r.direction.z;
+        o[6] = r.isinside ? 1.0f : 0.0f;
+        o[7] = r.sdepth;
+        o[8] = u01(&rng);
+        if (leaf) leaf[i] = code;
+    }
+}
+
+/* shadeMaterial on n records of 19 words, one path and one material each -> colour and remainingBounces. */
+void orc_shade_array(const float *in, int n, float *out) {
+    orc_material *mats = (orc_material *)calloc((size_t)n + 1, sizeof *mats);
+    orc_isect *is = (orc_isect *)calloc((size_t)n + 1, sizeof *is);
+    orc_path *paths = (orc_path *)calloc((size_t)n + 1, sizeof *paths);
+    orc_scene s;
+    memset(&s, 0, sizeof s);
+    s.materials = mats;
+    s.num_materials = n;
+    orc_opts o;
+    orc_default_opts(&o);
+    for (int sss = 0; sss < 2; sss++) { /* the flag is per launch: one pass per value, rows taken by their own */
+        for (int i = 0; i < n; i++) {
+            const float *a = in + 19 * (size_t)i;
+            orc_material *m = &mats[i];
+            memcpy(m->color, a + 1, 12);
+            memcpy(m->spec_color, a + 4, 12);
+            m->hasReflective = a[7]; m->hasRefractive = a[8]; m->emittance = a[9];
+            memcpy(m->transmittance, a + 10, 12);
+            is[i].t = a[0];
+            is[i].materialId = i;
+            paths[i].sdepth = a[14];
+            memcpy(paths[i].color, a + 15, 12);
+            memcpy(&paths[i].remainingBounces, a + 18, 4);
+        }
+        o.enableSss = sss;
+        shadeMaterial(&s, &o, n, is, paths);
+        for (int i = 0; i < n; i++) {
+            if ((in[19 * (size_t)i + 13] != 0.0f) != sss) continue;
+            memcpy(out + 4 * (size_t)i, paths[i].color, 12);
+            memcpy(out + 4 * (size_t)i + 3, &paths[i].remainingBounces, 4);
+        }
+    }
+    free(mats); free(is); free(paths);
+}
+
+/* boxIntersectionTest / sphereIntersectionTest on n records of 55 words -> t, hit point, normal; the
+ * point and the normal keep the caller's words where the test does not write them. */
+void orc_geom_test_array(const float *in, int n, float *out) {
+#pragma omp parallel for schedule(static)
+    for (int i = 0; i < n; i++) {
+        const float *a = in + 55 * (size_t)i;
+        float *o = out + 7 * (size_t)i;
+        orc_geom g;
+        memset(&g, 0, sizeof g);
+        memcpy(&g.type, a, 4);
+        memcpy(g.transform, a + 1, 64);
+        memcpy(g.inverseTransform, a + 17, 64);
+        memcpy(g.invTranspose, a + 33, 64);
+        ray_t r;
+        r.origin = V3(a[49], a[50], a[51]);
+        r.direction = V3(a[52], a[53], a[54]);
+        r.isinside = 0; r.sdepth = 0.0f;
+        v3 ip = V3(o[1], o[2], o[3]), nrm = V3(o[4], o[5], o[6]);
+        int outside = 0;
+        o[0] = g.type == 1 ? boxIntersectionTest(&g, r, &ip, &nrm, &outside)
+                           : sphereIntersectionTest(&g, r, &ip, &nrm, &outside);
+        o[1] = ip.x; o[2] = ip.y; o[3] = ip.z; o[4] = nrm.x; o[5] = nrm.y; o[6] = nrm.z;
     }
 }

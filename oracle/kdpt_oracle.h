@@ -258,6 +258,23 @@ void orc_geom_matrices(const float *trs, int n, float *out);
 /* getFresnelVal with dot(N,-I) == cosines[i] */
 void orc_fresnel_array(const float *cosines, int n, float ior, float *f);
 
+/* The bounce as units, on rows of 32-bit words (tests/kat_inputs.py SCATTER_IN / SHADE_IN / GEOM_TEST_IN):
+ * scatterRay (src/interactions.h:195-358) with engine(seed): origin, direction, isinside, sdepth and the
+ * engine's next u01 draw, 9 words; leaf[i] (leaf may be NULL) = the leaf that ran, + ORC_LEAF_SOFT when
+ * the soft lobe ran. */
+enum {
+    ORC_LEAF_SSS_ENTER = 0, ORC_LEAF_SSS_DIFFUSE = 1, ORC_LEAF_TIR_REFLECT = 2, ORC_LEAF_TIR_DIFFUSE = 3,
+    ORC_LEAF_REFRACT = 4, ORC_LEAF_REFRACT_DIFFUSE = 5, ORC_LEAF_FRESNEL_REFLECT = 6, ORC_LEAF_REFLECT = 7,
+    ORC_LEAF_REFLECT_DIFFUSE = 8, ORC_LEAF_DIFFUSE = 9, ORC_LEAF_SOFT = 16
+};
+void orc_scatter_array(const float *in, int n, float *out, int *leaf);
+/* shadeMaterial's loop body (src/pathtrace.cu:2318-2366), one path and one material per row: colour and
+ * remainingBounces, 4 words */
+void orc_shade_array(const float *in, int n, float *out);
+/* boxIntersectionTest / sphereIntersectionTest (src/intersections.h:107-203) on a Geom of the row's three
+ * matrices: t, hit point, normal, 7 words; point and normal keep the caller's words where unwritten */
+void orc_geom_test_array(const float *in, int n, float *out);
+
 #ifdef __cplusplus
 }
 #endif

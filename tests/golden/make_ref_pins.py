@@ -16,6 +16,12 @@ outputs on the seeded inputs of tests/kat_inputs.py --
            (iter, index, depth) grid, the camera jitter's engine(utilhash(iter)) and raw edge seeds.
            `python tests/golden/make_ref_pins.py --thrust` refreshes only this section (it needs no
            /root/reference).
+  scatter, geom_tests  the reference's own scatterRay and boxIntersectionTest / sphereIntersectionTest
+           (oracle/_ref/ref_bounce = src/interactions.h + src/intersections.h compiled in place, host-only, with
+           rocThrust's engine; oracle/ref/ref_bounce_driver.cpp) on the 2^18 seeded rows each of
+           kat_inputs.scatter_inputs / geom_test_inputs.  The per-leaf counts come from the oracle's
+           orc_scatter_array, whose results the digests pin to the reference's.
+           `python tests/golden/make_ref_pins.py --bounce` refreshes only these two sections.
 """
 import json
 import os
@@ -37,6 +43,7 @@ from kdtreepathtraceroptimization_amd.fixtures import load_fixture_scene  # noqa
 
 REF_PINS = os.path.join(ROOT, "oracle", "_ref", "ref_pins")
 THRUST_RNG = os.path.join(ROOT, "oracle", "_ref", "thrust_rng")
+REF_BOUNCE = os.path.join(ROOT, "oracle", "_ref", "ref_bounce")
 SCENES = ("cornell", "cornell8", "cornellout_bunny")
 
 
@@ -108,7 +115,56 @@ def pin_thrust_rng(tmp):
     return out
 
 
+def ref_bounce(mode, x, out, tmp):
+    """oracle/_ref/ref_bounce MODE on rows x; `out` holds what the binary reads first (geom: sentinels)."""
+    xin, xout = os.path.join(tmp, "bounce.in"), os.path.join(tmp, "bounce.out")
+    x.tofile(xin)
+    out.tofile(xout)
+    subprocess.run([REF_BOUNCE, mode, str(len(x)), xin, xout], check=True, capture_output=True)
+    return np.fromfile(xout, np.float32).reshape(out.shape)
+
+
+def ref_scatter(x, tmp):
+    return ref_bounce("scatter", x, np.zeros((len(x), K.SCATTER_OUT), np.float32), tmp)
+
+
+def ref_geom_tests(x, tmp):
+    """t, hit point, normal per row, the point and the normal of a miss overwritten with the sentinel."""
+    return K.mask_missed(ref_bounce("geom", x, K.sentinels(len(x), K.GEOM_TEST_OUT), tmp))
+
+
+def digests(out):
+    return {"n": len(out), "sha256": K.sha256(out), "sha256_nan_canonical": K.sha256_nan_canonical(out),
+            "sha256_nan_masked": K.sha256(K.nan_words_masked(out, out))}
+
+
+def pin_bounce(tmp):
+    src = ("oracle/_ref/ref_bounce: /root/reference src/interactions.h + src/intersections.h compiled in place, "
+           "host-only, rocThrust engine")
+    x = K.scatter_inputs()
+    out = ref_scatter(x, tmp)
+    orc, leaf = oracle_lib.scatter_array(x)
+    assert K.sha256_nan_canonical(orc) == K.sha256_nan_canonical(out), "the oracle's scatter is not the reference's"
+    scatter = dict(digests(out), source=src, nan_values=int(np.isnan(out).sum()),
+                   nan_directions=int(np.isnan(out[:, 3:6]).any(axis=1).sum()),
+                   leaves={str(c): int((leaf == c).sum()) for c in sorted(set(leaf.tolist()))})
+    g = ref_geom_tests(K.geom_test_inputs(oracle_lib.geom_matrices), tmp)
+    hit = g[:, 0] > 0
+    geom = dict(digests(g), source=src, hits=int(hit.sum()), nan_t=int(np.isnan(g[:, 0]).sum()),
+                nan_values=int((np.isnan(g) & (g.view(np.uint32) != K.SENTINEL_BITS)).sum()))
+    return scatter, geom
+
+
 def main():
+    if "--bounce" in sys.argv:
+        path = os.path.join(HERE, "ref_pins.json")
+        pins = json.load(open(path))
+        with tempfile.TemporaryDirectory() as tmp:
+            pins["scatter"], pins["geom_tests"] = pin_bounce(tmp)
+        with open(path, "w") as f:
+            json.dump(pins, f, indent=1)
+        print(json.dumps({k: pins[k] for k in ("scatter", "geom_tests")}, indent=1))
+        return
     if "--thrust" in sys.argv:
         path = os.path.join(HERE, "ref_pins.json")
         pins = json.load(open(path))
@@ -143,6 +199,7 @@ def main():
                                     "hdr_sha256": hashlib.sha256(hdr).hexdigest(), "png_len": len(png),
                                     "hdr_len": len(hdr)}
         pins["thrust_rng"] = pin_thrust_rng(tmp)
+        pins["scatter"], pins["geom_tests"] = pin_bounce(tmp)
     with open(os.path.join(HERE, "ref_pins.json"), "w") as f:
         json.dump(pins, f, indent=1)
     print(json.dumps(pins, indent=1))

@@ -113,6 +113,9 @@ def lib():
         L.orc_save_image.argtypes = [P(C.c_float), C.c_int, C.c_int, C.c_float, P(C.c_uint8), P(C.c_float)]
         L.orc_glm_array.argtypes = [C.c_int, P(C.c_float), C.c_int, P(C.c_float)]
         L.orc_geom_matrices.argtypes = [P(C.c_float), C.c_int, P(C.c_float)]
+        L.orc_scatter_array.argtypes = [P(C.c_float), C.c_int, P(C.c_float), P(C.c_int)]
+        L.orc_shade_array.argtypes = [P(C.c_float), C.c_int, P(C.c_float)]
+        L.orc_geom_test_array.argtypes = [P(C.c_float), C.c_int, P(C.c_float)]
         _lib = L
     return _lib
 
@@ -364,4 +367,28 @@ def geom_matrices(trs: np.ndarray) -> np.ndarray:
     trs = np.ascontiguousarray(trs, np.float32).reshape(-1, 9)
     out = np.empty((len(trs), 48), np.float32)
     lib().orc_geom_matrices(_fp(trs), len(trs), _fp(out))
+    return out
+
+
+def scatter_array(x: np.ndarray):
+    """orc_scatter_array on kat_inputs.scatter_inputs' rows: (n, 9) float32 results and the leaf codes."""
+    x = np.ascontiguousarray(x, np.float32)
+    out, leaf = np.empty((len(x), 9), np.float32), np.empty(len(x), np.int32)
+    lib().orc_scatter_array(_fp(x), len(x), _fp(out), leaf.ctypes.data_as(C.POINTER(C.c_int)))
+    return out, leaf
+
+
+def shade_array(x: np.ndarray) -> np.ndarray:
+    """orc_shade_array on kat_inputs.shade_inputs' rows: (n, 4) words, colour and remainingBounces."""
+    x = np.ascontiguousarray(x, np.float32)
+    out = np.empty((len(x), 4), np.float32)
+    lib().orc_shade_array(_fp(x), len(x), _fp(out))
+    return out
+
+
+def geom_test_array(x: np.ndarray, out: np.ndarray) -> np.ndarray:
+    """orc_geom_test_array on kat_inputs.geom_test_inputs' rows; `out` (n, 7) holds the sentinels on entry."""
+    x = np.ascontiguousarray(x, np.float32)
+    assert out.dtype == np.float32 and out.flags.c_contiguous
+    lib().orc_geom_test_array(_fp(x), len(x), _fp(out))
     return out

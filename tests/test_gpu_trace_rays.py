@@ -97,6 +97,27 @@ def test_knob_routes_agree(kdpt):
             pt.set_tuning(knob, 1)
 
 
+def test_soft_mirror_nan_directions_share_waves_with_live_paths(kdpt, oracle):
+    """softness = 0.5 on the probe tableau (tests/geoms.py), whose axis-aligned unit cube carries the mirror
+    material: every fourth of the 4 096 caller rays is (0, 0, -1) onto the cube's +z face, reflects to exactly
+    (0, 0, +1) and leaves the soft lobe with a NaN direction (its axis is normalize of a zero cross product); the
+    others are ordinary rays that reach the light.  The two kinds are interleaved, so NaN lanes and live lanes
+    share waves and compaction tiles.  Radiance bits and segments equal the oracle's render_rays, on the fused
+    route and on the "shade_fused" = 0 route.  (tests/test_bounce_pins.py has the CPU side: the oracle gives
+    the degenerate rays a finite radiance and 2 segments each.)"""
+    import geoms
+    desc = geoms.geom_scene("far", res=(64, 64), depth=8)
+    o, d, deg = geoms.soft_mirror_rays(4096)
+    want, st = oracle.OracleScene.from_description(desc).render_rays(o, d, 1, 2, softness=0.5)
+    assert np.isfinite(want).all() and not want[deg].any() and st.segments > 2 * len(o)
+    with _pt(kdpt, desc, softness=0.5) as pt:
+        for fused in (1, 0):
+            pt.set_tuning("shade_fused", fused)
+            got = pt.trace_rays(o, d, 1, 2, normalize=False)
+            assert _same(got, want), (fused, int(np.sum(got != want)))
+            assert pt.trace_rays_stats().segments == st.segments, fused
+
+
 def test_count_sums_the_iterations_in_order(kdpt, oracle):
     """cacherays = 1: every iteration uses iteration 1's rays, so trace_rays(camera_rays(1), 1, 3) is the render of
     iterations 1..3 (one add per pixel and iteration, in order)."""

@@ -17,8 +17,11 @@ src/utilities.cpp and its vendored glm 0.9.6.3, compiled in place from /root/ref
   edge seeds.
 
 Where /root/reference exists the digests are recomputed from the reference binary as well, so the
-fixture itself stays pinned.  The bounce as a whole stays pinned only by the survey's anchor runs
-(reference kernels run host-side during the survey) and the oracle restatement.
+fixture itself stays pinned.  scatterRay and the box / sphere tests are pinned as units to the reference's
+src/interactions.h and src/intersections.h by tests/test_bounce_pins.py (the "scatter" and "geom_tests"
+sections); shadeMaterial and generateRayFromCamera are __global__s of src/pathtrace.cu that do not compile
+here, so shade and the camera stay pinned by the oracle restatement and the survey's anchor runs (reference
+kernels run host-side during the survey).
 """
 import hashlib
 import json
