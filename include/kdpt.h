@@ -495,6 +495,69 @@ int kdpt_noise_estimate(kdpt_ctx *ctx, float floor, float threshold, kdpt_noise 
 int kdpt_trace_rays_moments(kdpt_ctx *ctx, const float *origins, const float *directions, long long n,
                             int first_iter, int count, int flags, float *radiance, float *sumsq);
 
+/* ---- Adaptive sampling: re-trace only the pixels whose noise is above a threshold ----
+ * State: a context with moments on gains extra[p], a uint32 per pixel, allocated (zero) by the first kdpt_active_pixels
+ * or kdpt_trace_adaptive.  kdpt_reset zeroes it with the image and sumsq; kdpt_set_moments(ctx, 0) frees it;
+ * kdpt_set_options, kdpt_set_camera and kdpt_set_tuning keep it.  Pixel p's sample count is n_p = samples + extra[p],
+ * `samples` being kdpt_read_moments' counter of uniform iterations.  While extra is absent every other call does what
+ * it did before; once it exists kdpt_noise_map and kdpt_noise_estimate use n_p in place of n (kdpt_noise.samples
+ * stays the uniform count).
+ *
+ * Active rule: e_p is kdpt_noise_map's formula with n replaced by n_p, computed by the same device function in the
+ * same operation order; pixel p is active iff isfinite(e_p) && e_p > threshold -- the rule behind kdpt_noise_estimate's
+ * `above`, so a pixel whose sums are NaN or inf is never re-traced.  The active list A holds the active pixel indices
+ * (y*W + x) in ascending order; it is built on the device by a flag pass and an ordered compaction without atomics,
+ * so two calls on the same state give the same list.
+ *
+ * kdpt_active_pixels returns the list: *n = |A|, and pixels (|A| <= W*H ints; host memory or memory of the context's
+ * device; may be NULL for the count alone) its entries.  Synchronous; the render state is left alone.
+ *
+ * kdpt_trace_adaptive is synchronous, as kdpt_trace_rays is: it waits for the work queued on the context (the
+ * pipelined adds included), builds A once from the state before the call, reads |A| back (4 bytes: its only host read
+ * before the end) and runs iterations first_iter + k (k < count) over A on kdpt_trace_iterations' batched, pipelined
+ * route (pipeline and batch clamped as there; the result's bits do not depend on them).  With |A| = 0 or count = 0 it
+ * returns KDPT_OK with out->pixels and out->active filled, and nothing changes.  For each iteration `it`, in order:
+ * path j starts as the ray kdpt_camera_rays(it) returns for pixel A[j] (jitter, depth of field and the cacherays rule
+ * included) with colour (1, 1, 1), pixelIndex j and remainingBounces traceDepth; there are |A| paths; everything
+ * after that is the context's own pipeline with the RNG seeds (it, slot, depth) as they fall.  With x what that
+ * iteration's gathers add to slot j, for each channel image[A[j]] = fadd(image[A[j]], x) and sumsq[A[j]] =
+ * fadd(sumsq[A[j]], fmul(x, x)), and extra[A[j]] += 1.  That is, bit for bit, the composition
+ *   o, d = kdpt_camera_rays(it) restricted to A;  r = kdpt_trace_rays_moments(o, d, |A|, it, 1, 0);  x_j = r_j
+ * scattered through A; with A = every pixel, the image and sumsq of kdpt_trace_iterations(first_iter, count).
+ * Supported wherever kdpt_trace_rays is, with the same KDPT_ERR_UNSUPPORTED refusal, and its caveat about iteration
+ * 2's sort under compaction = 0 applies as written there.  kdpt_stats is left alone (iterations, total_segments and
+ * the intersect totals do not move: the call's totals go to `out`, as a query's do), and so are the moments' `samples`
+ * counter, kdpt_cast_rays' buffers and kdpt_trace_rays' state.  A later kdpt_set_moments(ctx, 1) asks for a reset, as
+ * after any iteration.
+ * Errors, reported before any device work: KDPT_ERR_ARG for first_iter < 1, count < 0, a null `out` or ctx, a floor
+ * that is not finite and > 0, a NaN threshold or fewer than 2 uniform iterations accumulated; KDPT_ERR_UNSUPPORTED
+ * while moments are off or the context is in a communicator (kdpt_comm_init: frames carry no per-pixel counts).
+ * kdpt_active_pixels takes the same checks.
+ * Pixels whose e_p reads exactly 0 after few samples (a pixel that saw the same value every time) are never
+ * revisited: enough uniform iterations before the first adaptive call are the caller's guard.
+ *
+ * kdpt_read_sample_counts writes n_p (W*H ints, host memory); before any adaptive call every entry is `samples`.
+ * kdpt_save_counted is kdpt_save_rgb8's pixel pass (rgb: 3*W*H bytes) and the floats kdpt_save_hdr writes (lin: 3*W*H
+ * floats), either of which may be NULL, with each source pixel divided by (float)n_p instead of one `samples`: with
+ * no extra samples bit-equal to kdpt_save_rgb8(ctx, (float)samples); a pixel with n_p = 0 gives 0.  Both return
+ * KDPT_ERR_UNSUPPORTED while moments are off.
+ * kdpt_selftest_active_list runs the list kernels' flag-and-compact part on npix caller-supplied values on device 0:
+ * pixels (npix ints) receives the indices i with isfinite(noise[i]) && noise[i] > threshold, ascending, *n their
+ * number. */
+typedef struct kdpt_adaptive {   /* 48 bytes */
+    long long pixels;            /* W*H */
+    long long active;            /* |A| of this call */
+    long long pixel_samples;     /* active * count */
+    long long segments, traced;  /* kdpt_trace_rays_stats' meanings, summed over the call */
+    double device_ms;            /* hipEvents on the context's stream, from after the list to after the last add */
+} kdpt_adaptive;
+int kdpt_active_pixels(kdpt_ctx *ctx, float floor, float threshold, int *pixels, long long *n);
+int kdpt_trace_adaptive(kdpt_ctx *ctx, int first_iter, int count, int pipeline, int batch, float floor,
+                        float threshold, kdpt_adaptive *out);
+int kdpt_read_sample_counts(kdpt_ctx *ctx, int *counts);
+int kdpt_save_counted(kdpt_ctx *ctx, uint8_t *rgb, float *lin);
+int kdpt_selftest_active_list(const float *noise, int npix, float threshold, int *pixels, int *n);
+
 int kdpt_destroy(kdpt_ctx *ctx);
 /* The message of the most recent failing call of any kdpt_* function on the calling thread (each thread has its
  * own; "" before the first failure).  A successful call leaves it alone, so read it only after a non-OK return.

@@ -34,7 +34,7 @@ KERNEL_SOURCES = ["kdpt_device.h", "kdpt_scene.h", "kdpt_geoms.h", "kdpt_travers
                   "kdpt_trace_phase.h", "kdpt_scatter.h", "kdpt_glm_kat.h", "kdpt_bounce_kat.h",
                   "kdpt_math.h", "kdpt_runtime.hip", "glibc_sincostab.h", "kernels_gen.h",
                   "kernels_trace.h", "kernels_brute.h", "kernels_shade.h", "kernels_image.h", "kernels_cast.h",
-                  "kernels_rays.h", "kernels_selftest.h", "kernels_moments.h"]
+                  "kernels_rays.h", "kernels_selftest.h", "kernels_moments.h", "kernels_adaptive.h"]
 
 
 def _run(cmd, log=None):

@@ -22,6 +22,11 @@ Not in the reference: --target-noise E renders until the image's mean relative s
 over the per-pixel second moments, --noise-floor F) is <= E, checking after each round of pipeline x batch
 iterations from --min-spp N on, with --iterations as the upper limit; --noise-map also writes BASE.noise.npy.  The
 PNG / HDR are divided by the samples actually rendered.  Without --target-noise nothing changes.
+
+--adaptive (with --target-noise E) re-traces only the noisy pixels: uniform rounds up to --min-spp, then rounds of
+kdpt_trace_adaptive over the pixels whose own noise is above --pixel-noise T (default E) until the mean is <= E, no
+pixel is above T or --iterations is reached.  The PNG / HDR then divide each pixel by its own sample count
+(kdpt_save_counted).  A pixel whose noise reads 0 after --min-spp samples is never revisited: --min-spp is the guard.
 """
 from __future__ import annotations
 
@@ -87,7 +92,18 @@ def parse_args(argv=None) -> argparse.Namespace:
                     help="with --target-noise: no estimate before N samples per pixel (at least 2)")
     ap.add_argument("--noise-map", action="store_true",
                     help="with --target-noise: also write BASE.noise.npy (H x W float32, kdpt_noise_map)")
+    ap.add_argument("--adaptive", action="store_true",
+                    help="with --target-noise: after --min-spp uniform samples re-trace only the pixels whose noise "
+                         "is above --pixel-noise (kdpt_trace_adaptive)")
+    ap.add_argument("--pixel-noise", type=float, default=None, metavar="T",
+                    help="with --adaptive: a pixel goes again while its noise is above T (default: E)")
     a = ap.parse_args(argv)
+    if a.adaptive and a.target_noise is None:
+        ap.error("--adaptive needs --target-noise")
+    if a.pixel_noise is not None and not a.adaptive:
+        ap.error("--pixel-noise needs --adaptive")
+    if a.pixel_noise is not None and not a.pixel_noise >= 0:
+        ap.error("--pixel-noise must be >= 0")
     if a.target_noise is None and a.noise_map:
         ap.error("--noise-map needs --target-noise")
     if a.target_noise is not None:
@@ -131,6 +147,37 @@ def render_to_noise(pt, a: argparse.Namespace, limit: int):
     return done, est
 
 
+def render_adaptive(pt, a: argparse.Namespace, limit: int):
+    """--adaptive: uniform rounds up to --min-spp samples per pixel, then, while the estimate's mean is above E, a
+    pixel is above T and fewer than `limit` iterations are done, one kdpt_trace_adaptive round of (at most) pipeline x
+    batch iterations over the pixels above T, continuing the iteration numbers.  Returns the iterations done (the
+    largest per-pixel count), the last estimate and the adaptive rounds' totals."""
+    pt.set_moments(True)
+    thr = a.target_noise if a.pixel_noise is None else a.pixel_noise
+    per_round = max(1, min(16, a.pipeline)) * max(1, min(16, a.batch))
+    done, est = 0, None
+    totals = {"pixel_samples": 0, "segments": 0, "rounds": []}
+    uniform = min(a.min_spp, limit)
+    while done < uniform:
+        n = min(per_round, uniform - done)
+        pt.trace_iterations(a.first_iteration + done, n, pipeline=a.pipeline, batch=a.batch)
+        pt.synchronize()
+        done += n
+    totals["pixel_samples"] = done * pt.width * pt.height
+    while done >= 2:
+        est = pt.noise_estimate(a.noise_floor, thr)
+        if est.mean <= a.target_noise or est.above == 0 or done >= limit:
+            break
+        n = min(per_round, limit - done)
+        r = pt.trace_adaptive(a.first_iteration + done, n, pipeline=a.pipeline, batch=a.batch, floor=a.noise_floor,
+                              threshold=thr)
+        done += n
+        totals["pixel_samples"] += int(r.pixel_samples)
+        totals["segments"] += int(r.segments)
+        totals["rounds"].append({"active": int(r.active), "iterations": n, "device_ms": round(r.device_ms, 4)})
+    return done, est, totals
+
+
 def main(argv=None) -> int:
     a = parse_args(argv)
     from .runtime import PathTracer, SceneData
@@ -153,7 +200,10 @@ def main(argv=None) -> int:
     spp, est = iterations, None  # the samples per pixel actually rendered, and the adaptive stop's last estimate
     with PathTracer(sd, opt, device=a.device) as pt:
         t0 = time.perf_counter()
-        if a.target_noise is not None:
+        adaptive = None  # --adaptive: the adaptive rounds' totals
+        if a.adaptive:
+            spp, est, adaptive = render_adaptive(pt, a, iterations)
+        elif a.target_noise is not None:
             spp, est = render_to_noise(pt, a, iterations)
         elif a.testing:  # one synchronous pathtrace() per iteration, like TESTINGMODE
             for it in range(a.first_iteration, a.first_iteration + iterations):
@@ -165,24 +215,39 @@ def main(argv=None) -> int:
         st = pt.stats()
         base = a.out or f"{hdr['file'] or os.path.splitext(os.path.basename(a.scene))[0]}.{spp}samp"
         written = []
-        if not a.no_png:
-            pt.save_png(base + ".png", float(spp))
-            written.append(base + ".png")
-        if a.hdr:
-            pt.save_hdr(base + ".hdr", float(spp))
-            written.append(base + ".hdr")
+        if adaptive is not None:  # every pixel divided by its own sample count, then the same host encoders
+            from .runtime import hdr_encode, png_encode
+            rgb, lin = pt.save_counted(lin=True)
+            counts = pt.sample_counts()
+            for ext, on, encode, pixels in ((".png", not a.no_png, png_encode, rgb), (".hdr", a.hdr, hdr_encode, lin)):
+                if on:
+                    with open(base + ext, "wb") as f:
+                        f.write(encode(pixels))
+                    written.append(base + ext)
+        else:
+            if not a.no_png:
+                pt.save_png(base + ".png", float(spp))
+                written.append(base + ".png")
+            if a.hdr:
+                pt.save_hdr(base + ".hdr", float(spp))
+                written.append(base + ".hdr")
         if a.noise_map and spp >= 2:
             import numpy as np
             np.save(base + ".noise.npy", pt.noise_map(a.noise_floor))
             written.append(base + ".noise.npy")
-    info.update({"segments": int(st.total_segments), "seconds": round(dt, 4),
-                 "mrays_per_s": round(st.total_segments / dt / 1e6, 2) if dt > 0 else None,
+    segments = int(st.total_segments) + (adaptive["segments"] if adaptive is not None else 0)
+    info.update({"segments": segments, "seconds": round(dt, 4),
+                 "mrays_per_s": round(segments / dt / 1e6, 2) if dt > 0 else None,
                  "ms_per_iteration": round(dt * 1e3 / spp, 4), "written": written})
     if a.target_noise is not None:
         info.update({"spp": spp, "target_noise": a.target_noise, "noise_floor": a.noise_floor,
                      "noise": None if est is None else {
                          "mean": est.mean, "max": est.max, "above": int(est.above), "nonfinite": int(est.nonfinite),
                          "pixels": int(est.pixels), "samples": int(est.samples)}})
+    if adaptive is not None:
+        info.update({"pixel_noise": a.target_noise if a.pixel_noise is None else a.pixel_noise,
+                     "pixel_samples": adaptive["pixel_samples"], "mean_spp": float(counts.mean()),
+                     "max_spp": int(counts.max()), "adaptive_rounds": adaptive["rounds"]})
     if a.testing:
         info["intersect_ms_total"] = round(st.intersect_ms_total, 4)
     print(json.dumps(info), flush=True)

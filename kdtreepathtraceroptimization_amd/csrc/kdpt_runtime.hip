@@ -1,7 +1,8 @@
 // kdpt_runtime.hip -- the runtime behind the C ABI (include/kdpt.h): the context and its device memory,
 // kdpt_create (upload of what kdpt_scene_prep.h prepared), the knobs, the launch sequence of an iteration
 // (launch_batch), pipelined / batched iterations, the multi-GPU frame path, the ray queries and the
-// caller-defined views (kdpt_set_camera, kdpt_camera_rays, kdpt_trace_rays).  One HIP
+// caller-defined views (kdpt_set_camera, kdpt_camera_rays, kdpt_trace_rays), the second moments and adaptive
+// sampling (kdpt_trace_adaptive).  One HIP
 // translation unit: the kernels live in the kernels_*.h headers included below, one per stage; scene
 // validation and packing live in kdpt_scene_prep.h and run before any device call.
 //
@@ -9,7 +10,9 @@
 // launch_batch for a batch of up to MAXB iterations in lockstep (blockIdx.y / the batch records = iteration):
 //   k_gen_geoms_b   : camera rays + bounce 0's analytic geoms and root-box test, which queue the rays that
 //                     meet the KD root box (k_gen_rays_b alone on the brute-force / viz routes); a path-traced ray
-//                     query (kdpt_trace_rays) starts from the caller's rays instead: k_user_geoms_b / k_user_rays_b
+//                     query (kdpt_trace_rays) starts from the caller's rays instead: k_user_geoms_b / k_user_rays_b,
+//                     an adaptive round (kdpt_trace_adaptive) from its list of pixels: k_adapt_geoms_b /
+//                     k_adapt_rays_b
 //   then per bounce (cap 8, src/pathtrace.cu:2608):
 //   k_trace         : the intersect kernel -- KD traversal of the queued rays, persistent waves pulling
 //                     64-ray chunks, the tree read from LDS when a record format fits (setup_trace); k_brute /
@@ -65,6 +68,7 @@ bool g_cu_mask_streams = true;  // kdpt_set_tuning(NULL, "cu_mask_streams", v): 
 #include "kernels_cast.h"
 #include "kernels_rays.h"
 #include "kernels_selftest.h"
+#include "kernels_adaptive.h"
 #include "kernels_moments.h"
 
 // ---------------------------------------------------------------------------
@@ -241,6 +245,19 @@ struct RayQuery {
   double ms = 0;                       // ... and its device time
 };
 
+// Adaptive sampling (kdpt_trace_adaptive, kdpt_active_pixels): the per-pixel count of samples added beyond the
+// uniform ones, the active list and the list kernels' buffers, the call's own segment and intersect totals (a ray
+// query's layout) and its events.  Made by the first adaptive call (adaptive_state); part of the moments, so they
+// go with them.  extra is the state: null means every pixel has Moments::samples samples.
+struct Adaptive {
+  DeviceBuf<uint32_t> extra;               // [npix]
+  DeviceBuf<int> list;                     // [npix] the active pixels, ascending
+  DeviceBuf<unsigned long long> masks;     // [4 workgroups] k_adapt_flags' ballots
+  DeviceBuf<int> blocks;                   // [workgroups] counts, [workgroups] offsets, then |A|
+  DeviceBuf<unsigned long long> totals;    // [0] ShadeArgs::total_segments, [1..3] trace_total / trace_rays
+  Event ev[2];
+};
+
 // Per-pixel second moments (kdpt_set_moments): sumsq beside the image, the partial image the solo state gathers
 // into while they are on (added with k_accumulate_moments at nb = 1), the number of iterations added since both
 // were zeroed, and kdpt_noise_map's / kdpt_noise_estimate's buffers.  All null / 0 while moments are off.
@@ -250,6 +267,7 @@ struct Moments {
   long long samples = 0;
   DeviceBuf<float> noise_stage;         // [npix] kdpt_noise_map into host memory
   DeviceBuf<NoisePartial> noise_parts;  // [workgroups + 1] k_noise_partials' partials, then k_noise_final's result
+  Adaptive adapt;
 };
 
 struct kdpt_ctx {
@@ -358,12 +376,22 @@ int dupload(kdpt_ctx* c, const T** field, const std::vector<T>& v) {
 
 int launch_iteration(kdpt_ctx* c, int iter, int stop_depth, bool count);
 int accumulate_iteration(kdpt_ctx* c, int iter);
-// A batch that starts from caller-supplied rays instead of the camera's (kdpt_trace_rays; one iteration per
-// batch): the rays in device memory, and where the shading adds what it would add to the context's intersect
-// totals (kdpt_ctx::trace_total's layout).
+// A batch that does not start from the camera's W*H rays: from caller-supplied rays in device memory
+// (kdpt_trace_rays; one iteration per batch), or, with `list`, from the camera's rays of the n listed pixels
+// (kdpt_trace_adaptive; up to MAXB iterations).  trace_total: where the shading adds what it would add to the
+// context's intersect totals (kdpt_ctx::trace_total's layout).
 struct RaySource {
   UserRays rays;
   unsigned long long* trace_total;
+  const int* list = nullptr;  // [n] pixel indices in device memory
+  int n = 0;
+};
+// An adaptive round's batches (enqueue_iterations): the list, and what the adds through it update.
+struct ActiveSet {
+  const int* list;
+  int n;
+  uint32_t* extra;
+  unsigned long long* totals;  // Adaptive::totals
 };
 int launch_batch(kdpt_ctx* c, IterState* const* its, const int* iters, int nb, hipStream_t st, int trace_grid,
                  int stop_depth, bool count, std::vector<Event>* bev, const RaySource* rays = nullptr);
@@ -502,10 +530,15 @@ __global__ void k_accumulate_batch(float* __restrict__ image, PartialImages part
 
 // The add of nb partial images (iteration order) into `target` on stream st: k_accumulate_batch, or, when the
 // context keeps second moments and the target is its image, k_accumulate_moments, which adds the squares into
-// mom_sumsq in the same pass.
-int launch_accumulate(kdpt_ctx* c, float* target, const float* const* partials, int nb, hipStream_t st) {
+// mom_sumsq in the same pass.  With an active set the partial images hold list slots, not pixels:
+// k_accumulate_adapt adds them through the list and counts the samples into `extra`.
+int launch_accumulate(kdpt_ctx* c, float* target, const float* const* partials, int nb, hipStream_t st,
+                      const ActiveSet* act = nullptr) {
   const int n3 = 3 * c->npix;
-  if (c->mom.on && target == c->image) {
+  if (act) {
+    hipLaunchKernelGGL(k_accumulate_adapt, dim3((act->n + 255) / 256), dim3(256), 0, st, target, c->mom.sumsq.get(),
+                       act->extra, act->list, act->n, fill_parts<AdaptParts>(partials, nb));
+  } else if (c->mom.on && target == c->image) {
     hipLaunchKernelGGL(k_accumulate_moments, dim3((n3 + 255) / 256), dim3(256), 0, st, target, c->mom.sumsq.get(),
                        fill_parts<MomentParts>(partials, nb), n3);
   } else {
@@ -662,6 +695,8 @@ int build_masks(kdpt_ctx* c, int n) {
 //     test_geom_render_equals_oracle "shade_batch" 0 (tilted, nested, glass: STAGE; nine, mats33, mats64: not)
 //   k_brute: count on -- test_brute_force_counters_match_oracle (use_bbox 0, 1); off --
 //     test_brute_force_bit_exact_vs_oracle (both); k_cast_resolve: H and B -- test_cast_equals_oracle
+//   k_adapt_geoms_b: every case of tests/test_gpu_adaptive.py but one; k_adapt_rays_b: its brute_sphere case
+//     (enable_kd = 0); k_adapt_flags: false -- the same tests, true -- test_selftest_active_list_equals_numpy
 // ---------------------------------------------------------------------------
 struct TraceKernel {
   void (*fn)(TraceArgs);
@@ -1156,6 +1191,8 @@ int kdpt_reset(kdpt_ctx* c) {
   HIP_TRY(hipMemsetAsync(c->total_segments, 0, sizeof(unsigned long long), c->stream));
   HIP_TRY(hipMemsetAsync(c->trace_total, 0, 3 * sizeof(unsigned long long), c->stream));
   if (c->mom.on) HIP_TRY(hipMemsetAsync(c->mom.sumsq.get(), 0, sizeof(float) * 3 * (size_t)c->npix, c->stream));
+  if (c->mom.adapt.extra)
+    HIP_TRY(hipMemsetAsync(c->mom.adapt.extra.get(), 0, sizeof(uint32_t) * (size_t)c->npix, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->mom.samples = 0;
   c->accumulated = false;
@@ -1228,8 +1265,11 @@ int kdpt_trace_iteration(kdpt_ctx* c, int frame, int iter) {
 // whole batch, so none holds an in-order hardware queue that batch streams share (HIP multiplexes a process's
 // streams onto GPU_MAX_HW_QUEUES queues, 4 by default).  zero_after: the target is first zeroed, after that
 // event (a frame buffer after its previous reduce).  Returns once everything is queued.
+// act (kdpt_trace_adaptive): every batch starts from the active list instead of the camera's W*H rays and is added
+// through it; the list was built on the context's stream, so each group's first launch of the call follows `entry`.
+// The segment and intersect totals go to the set's own, and kdpt_stats and the moments' counter do not move.
 int enqueue_iterations(kdpt_ctx* c, int first_iter, int count, int stride, int pipeline, int batch, float* target,
-                       hipEvent_t zero_after = nullptr) {
+                       hipEvent_t zero_after = nullptr, const ActiveSet* act = nullptr) {
   if (c->shade_oob) return refuse_shading();
   const int depth = std::min(16, std::max(1, pipeline));
   const int B = std::min(MAXB, std::max(1, batch));
@@ -1264,7 +1304,14 @@ int enqueue_iterations(kdpt_ctx* c, int first_iter, int count, int stride, int p
   // behind them.  (Sweep with every batch on its own hardware queue: a quarter is best at depths 8-12.)
   const int trace_grid =
       c->grid_env ? c->trace_grid : std::max(1, c->trace_grid * 2 / std::min(8, std::max(2, depth)));
-  c->stats.intersect_grid_share = (float)trace_grid / (float)std::max(1, c->full_trace_grid);
+  if (!act) c->stats.intersect_grid_share = (float)trace_grid / (float)std::max(1, c->full_trace_grid);
+  RaySource src{};
+  if (act) {
+    src.trace_total = act->totals + 1;
+    src.list = act->list;
+    src.n = act->n;
+  }
+  unsigned waited = 0;  // the groups whose stream has waited for `entry` in this call (an active set's)
   // diagnostic ("profile_batches" knob): the counting intersect kernel (kdpt_wave_profile after sync)
   if (c->profile_batches) HIP_TRY(hipMemsetAsync(c->counters, 0, sizeof(Counters), c->stream));
   bool first = true;
@@ -1285,7 +1332,7 @@ int enqueue_iterations(kdpt_ctx* c, int first_iter, int count, int stride, int p
       its[b] = grp.its[b].get();
     }
     std::vector<Event>* bev = nullptr;
-    if (c->opt.testing_mode) {
+    if (c->opt.testing_mode && !act) {
       std::vector<Event> evs;
       for (int e = 0; e < 2 * c->cap; e++) {
         Event ev;
@@ -1296,7 +1343,14 @@ int enqueue_iterations(kdpt_ctx* c, int first_iter, int count, int stride, int p
       c->pipe.pending_ev.push_back(std::move(evs));
       bev = &c->pipe.pending_ev.back();
     }
-    int rc = launch_batch(c, its, iters, nb, st, trace_grid, -1, c->profile_batches, bev);
+    if (act) {
+      if (!(waited >> g & 1u)) HIP_TRY(hipStreamWaitEvent(st, entry, 0));
+      waited |= 1u << g;
+      for (int b = 0; b < nb; b++) its[b]->total_segments = act->totals;
+    }
+    int rc = launch_batch(c, its, iters, nb, st, trace_grid, -1, c->profile_batches, bev, act ? &src : nullptr);
+    if (act)  // (the launches took the pointer by value)
+      for (int b = 0; b < nb; b++) its[b]->total_segments = c->total_segments;
     if (rc) return rc;
     // the add: after the previous add (the chain), and for the call's first batch after the context's stream,
     // the frames' image adds (when the target is the image) and the target's zeroing
@@ -1312,15 +1366,15 @@ int enqueue_iterations(kdpt_ctx* c, int first_iter, int count, int stride, int p
     }
     const float* partials[MAXB];
     for (int b = 0; b < nb; b++) partials[b] = its[b]->image;  // in iteration order
-    if ((rc = launch_accumulate(c, target, partials, nb, st))) return rc;
+    if ((rc = launch_accumulate(c, target, partials, nb, st, act))) return rc;
     HIP_TRY(hipEventRecord(grp.acc_ev, st));
     c->pipe.acc_last = grp.acc_ev;
     if (target == c->image) {
       c->accumulated = true;
-      if (c->mom.on) c->mom.samples += nb;
+      if (c->mom.on && !act) c->mom.samples += nb;
     }
   }
-  c->stats.iterations += count;
+  if (!act) c->stats.iterations += count;
   return KDPT_OK;
 }
 
@@ -1396,8 +1450,9 @@ int kdpt_write_pbo(kdpt_ctx* c, int iter, uint8_t* rgba) {
   return KDPT_OK;
 }
 
-// The saveImage pixel pass on the device; rgb (host, 3*W*H) and/or lin (host, 3*W*H floats).
-static int save_image_pass(kdpt_ctx* c, float samples, uint8_t* rgb, float* lin) {
+// The saveImage pixel pass on the device; rgb (host, 3*W*H) and/or lin (host, 3*W*H floats).  counted
+// (kdpt_save_counted): each pixel divided by its own sample count (k_save_counted) instead of `samples`.
+static int save_image_pass(kdpt_ctx* c, float samples, uint8_t* rgb, float* lin, bool counted = false) {
   HIP_TRY(hipSetDevice(c->device));
   for (auto& grp : c->pipe.groups) HIP_TRY(hipStreamSynchronize(grp.stream));
   if (c->frames.reduce_stream) HIP_TRY(hipStreamSynchronize(c->frames.reduce_stream));
@@ -1406,8 +1461,12 @@ static int save_image_pass(kdpt_ctx* c, float samples, uint8_t* rgb, float* lin)
   DeviceBuf<float> d_lin;  // (null without `lin`)
   HIP_TRY(d_rgb.alloc(n3));
   if (lin) HIP_TRY(d_lin.alloc(n3));
-  hipLaunchKernelGGL(k_save_image, dim3((c->npix + 255) / 256), dim3(256), 0, c->stream, c->image, c->W, c->H,
-                     samples, d_rgb.get(), d_lin.get());
+  if (counted)
+    hipLaunchKernelGGL(k_save_counted, dim3((c->npix + 255) / 256), dim3(256), 0, c->stream, c->image,
+                       c->mom.adapt.extra.get(), c->W, c->H, c->mom.samples, d_rgb.get(), d_lin.get());
+  else
+    hipLaunchKernelGGL(k_save_image, dim3((c->npix + 255) / 256), dim3(256), 0, c->stream, c->image, c->W, c->H,
+                       samples, d_rgb.get(), d_lin.get());
   HIP_TRY(hipGetLastError());
   if (rgb) HIP_TRY(hipMemcpyAsync(rgb, d_rgb.get(), n3, hipMemcpyDeviceToHost, c->stream));
   if (lin) HIP_TRY(hipMemcpyAsync(lin, d_lin.get(), n3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -1698,7 +1757,7 @@ struct Batch {
                     // brute-force and box-view intersect kernels, which have no first part)
   bool compact;
   ShadeArgs shade;  // the shading arguments that neither the bounce nor the iteration changes
-  const RaySource* rays = nullptr;  // a ray query's batch (nb = 1): bounce 0 loads these instead of the camera's
+  const RaySource* rays = nullptr;  // a ray query's batch (nb = 1) or an adaptive round's (a list): bounce 0's source
   unsigned long long* trace_total = nullptr;  // the intersect totals the shading adds to (the context's, or the query's)
 };
 
@@ -1729,13 +1788,28 @@ int user_rays_stage(const Batch& B) {
 }
 
 // The batch's camera rays in one launch (blockIdx.y = iteration), with bounce 0's geoms stage when gen_geoms.
+// With a list source (kdpt_trace_adaptive) the launch covers the listed pixels only: k_adapt_geoms_b / k_adapt_rays_b.
 int camera_stage(const Batch& B) {
-  if (B.rays) return user_rays_stage(B);
+  if (B.rays && !B.rays->list) return user_rays_stage(B);
   kdpt_ctx* c = B.c;
   GenBatch gb = gen_batch(c);
   for (int b = 0; b < B.nb; b++) {
     B.its[b]->cur = 0;
     gb.it[b] = B.its[b]->gen_iter(c->opt.cacherays ? 1 : B.iters[b]);
+  }
+  if (B.rays) {
+    const AdaptBatch ab{gb, B.rays->list, B.rays->n};
+    const dim3 grid((ab.n + GEN_BLOCK - 1) / GEN_BLOCK, B.nb);
+    if (B.gen_geoms) {
+      AdaptGeomsBatch ag{ab, B.S0, {}, B.count ? c->counters : nullptr};
+      B.its[0]->q->begin_use();
+      for (int b = 0; b < B.nb; b++) ag.it[b] = B.its[b]->gen_geoms_iter();
+      hipLaunchKernelGGL(k_adapt_geoms_b, grid, dim3(GEN_BLOCK), 0, B.st, ag);
+    } else {
+      hipLaunchKernelGGL(k_adapt_rays_b, grid, dim3(GEN_BLOCK), 0, B.st, ab);
+    }
+    HIP_TRY(hipGetLastError());
+    return KDPT_OK;
   }
   if (B.gen_geoms) {
     GenGeomsBatch gg{gb, B.S0, {}, B.count ? c->counters : nullptr};
@@ -2707,8 +2781,12 @@ int kdpt_noise_map(kdpt_ctx* c, float floor, float* noise) {
   if ((rc = join_accum(c))) return rc;
   const bool dev = on_context_device(c, noise);
   float* const d = dev ? noise : c->mom.noise_stage.get();
-  hipLaunchKernelGGL(k_noise_map, dim3((c->npix + 255) / 256), dim3(256), 0, c->stream, c->image, c->mom.sumsq.get(),
-                     c->npix, c->mom.samples, floor, d);
+  if (const uint32_t* extra = c->mom.adapt.extra.get())  // per-pixel sample counts since an adaptive call
+    hipLaunchKernelGGL(k_noise_map_counted, dim3((c->npix + 255) / 256), dim3(256), 0, c->stream, c->image,
+                       c->mom.sumsq.get(), extra, c->npix, c->mom.samples, floor, d);
+  else
+    hipLaunchKernelGGL(k_noise_map, dim3((c->npix + 255) / 256), dim3(256), 0, c->stream, c->image,
+                       c->mom.sumsq.get(), c->npix, c->mom.samples, floor, d);
   HIP_TRY(hipGetLastError());
   if ((rc = stage_out(dev, noise, d, (size_t)c->npix, c->stream))) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2724,8 +2802,12 @@ int kdpt_noise_estimate(kdpt_ctx* c, float floor, float threshold, kdpt_noise* o
   if ((rc = join_accum(c))) return rc;
   const int nb = noise_blocks(c);
   NoisePartial* const parts = c->mom.noise_parts.get();
-  hipLaunchKernelGGL(k_noise_partials, dim3(nb), dim3(NOISE_BLOCK), 0, c->stream, c->image, c->mom.sumsq.get(), c->npix,
-                     c->mom.samples, floor, threshold, parts);
+  if (const uint32_t* extra = c->mom.adapt.extra.get())
+    hipLaunchKernelGGL(k_noise_partials_counted, dim3(nb), dim3(NOISE_BLOCK), 0, c->stream, c->image,
+                       c->mom.sumsq.get(), extra, c->npix, c->mom.samples, floor, threshold, parts);
+  else
+    hipLaunchKernelGGL(k_noise_partials, dim3(nb), dim3(NOISE_BLOCK), 0, c->stream, c->image, c->mom.sumsq.get(),
+                       c->npix, c->mom.samples, floor, threshold, parts);
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_noise_final, dim3(1), dim3(NOISE_BLOCK), 0, c->stream, parts, nb, parts + nb);
   HIP_TRY(hipGetLastError());
@@ -2740,5 +2822,181 @@ int kdpt_noise_estimate(kdpt_ctx* c, float floor, float threshold, kdpt_noise* o
   out->nonfinite = r.nonfinite;
   out->mean = finite > 0 ? r.sum / (double)finite : 0.0;
   out->max = r.max;
+  return KDPT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Adaptive sampling (include/kdpt.h "Adaptive sampling"): kdpt_active_pixels, kdpt_trace_adaptive,
+// kdpt_read_sample_counts, kdpt_save_counted and kdpt_selftest_active_list.  The list is built on the context's
+// stream (k_adapt_flags, k_adapt_scan, k_adapt_list); the iterations over it take kdpt_trace_iterations' pipelined
+// route with an active set (enqueue_iterations): k_adapt_geoms_b / k_adapt_rays_b for the camera stage,
+// launch_batch's kernels as they are, k_accumulate_adapt for the add.
+// ---------------------------------------------------------------------------
+namespace {
+
+int adapt_blocks(int npix) { return (npix + ADAPT_BLOCK - 1) / ADAPT_BLOCK; }
+
+// What kdpt_active_pixels and kdpt_trace_adaptive refuse beyond their own arguments, before any device work.
+int check_adaptive_args(const kdpt_ctx* c, float floor, float threshold, const std::string& who) {
+  if (!(std::isfinite(floor) && floor > 0.0f)) return fail(KDPT_ERR_ARG, who + ": floor must be finite and > 0");
+  if (std::isnan(threshold)) return fail(KDPT_ERR_ARG, who + ": threshold is NaN");
+  if (!c) return fail(KDPT_ERR_ARG, who + ": null ctx");
+  if (!c->mom.on) return fail(KDPT_ERR_UNSUPPORTED, who + ": moments are off (kdpt_set_moments)");
+  if (c->frames.comm || c->frames.nranks > 1)
+    return fail(KDPT_ERR_UNSUPPORTED, who + ": the context is in a communicator (kdpt_comm_init): its frames reach "
+                                            "the image through a reduce that carries no per-pixel counts");
+  if (c->mom.samples < 2)
+    return fail(KDPT_ERR_ARG, who + ": " + std::to_string(c->mom.samples) +
+                                  " iteration(s) accumulated, a variance needs at least 2");
+  return KDPT_OK;
+}
+
+// The adaptive state, made on first use: extra starts at zero (filled on the context's stream and waited for).
+int adaptive_state(kdpt_ctx* c) {
+  Adaptive& a = c->mom.adapt;
+  if (a.extra) return KDPT_OK;
+  const size_t npix = (size_t)c->npix, nblk = (size_t)adapt_blocks(c->npix);
+  Adaptive fresh;
+  hipError_t e;
+  if ((e = fresh.extra.alloc(npix)) != hipSuccess || (e = fresh.list.alloc(npix)) != hipSuccess ||
+      (e = fresh.masks.alloc(nblk * (ADAPT_BLOCK / 64))) != hipSuccess ||
+      (e = fresh.blocks.alloc(2 * nblk + 1)) != hipSuccess || (e = fresh.totals.alloc(4)) != hipSuccess ||
+      (e = fresh.ev[0].create()) != hipSuccess || (e = fresh.ev[1].create()) != hipSuccess ||
+      (e = hipMemsetAsync(fresh.extra.get(), 0, sizeof(uint32_t) * npix, c->stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(c->stream)) != hipSuccess)
+    return hip_fail("adaptive sampling: device buffers", e);
+  a = std::move(fresh);
+  return KDPT_OK;
+}
+
+// The three list launches on stream st; values: the self test's per-pixel values (null: the context's noise).
+void launch_active_list(const float* image, const float* sumsq, const uint32_t* extra, const float* values, int npix,
+                        long long samples, float floor, float threshold, unsigned long long* masks, int* blocks,
+                        int* list, hipStream_t st) {
+  const int nblk = adapt_blocks(npix);
+  int* const counts = blocks, * const offs = blocks + nblk, * const total = blocks + 2 * nblk;
+  if (values)
+    hipLaunchKernelGGL(k_adapt_flags<true>, dim3(nblk), dim3(ADAPT_BLOCK), 0, st, image, sumsq, extra, values, npix,
+                       samples, floor, threshold, masks, counts);
+  else
+    hipLaunchKernelGGL(k_adapt_flags<false>, dim3(nblk), dim3(ADAPT_BLOCK), 0, st, image, sumsq, extra, values, npix,
+                       samples, floor, threshold, masks, counts);
+  hipLaunchKernelGGL(k_adapt_scan, dim3(1), dim3(ADAPT_BLOCK), 0, st, counts, nblk, offs, total);
+  hipLaunchKernelGGL(k_adapt_list, dim3(nblk), dim3(ADAPT_BLOCK), 0, st, masks, offs, list);
+}
+
+// The context's active list from its current sums, and |A| read back: the call's one host read before its end.
+// (The caller has synchronised the context.)
+int build_active_list(kdpt_ctx* c, float floor, float threshold, int* active) {
+  int rc = adaptive_state(c);
+  if (rc) return rc;
+  Adaptive& a = c->mom.adapt;
+  launch_active_list(c->image, c->mom.sumsq.get(), a.extra.get(), nullptr, c->npix, c->mom.samples, floor, threshold,
+                     a.masks.get(), a.blocks.get(), a.list.get(), c->stream);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(active, a.blocks.get() + 2 * adapt_blocks(c->npix), sizeof(int), hipMemcpyDeviceToHost,
+                         c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return KDPT_OK;
+}
+
+}  // namespace
+
+int kdpt_active_pixels(kdpt_ctx* c, float floor, float threshold, int* pixels, long long* n) {
+  if (!n) return fail(KDPT_ERR_ARG, "kdpt_active_pixels: null n");
+  int rc = check_adaptive_args(c, floor, threshold, "kdpt_active_pixels");
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  int active = 0;
+  if ((rc = kdpt_synchronize(c)) || (rc = build_active_list(c, floor, threshold, &active))) return rc;
+  *n = active;
+  if (!pixels || !active) return KDPT_OK;
+  if ((rc = stage_out(on_context_device(c, pixels), pixels, (const int*)c->mom.adapt.list.get(), (size_t)active,
+                      c->stream)))
+    return rc;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return KDPT_OK;
+}
+
+int kdpt_trace_adaptive(kdpt_ctx* c, int first_iter, int count, int pipeline, int batch, float floor,
+                        float threshold, kdpt_adaptive* out) {
+  const std::string who = "kdpt_trace_adaptive";
+  if (first_iter < 1) return fail(KDPT_ERR_ARG, who + ": first_iter must be >= 1");
+  if (count < 0) return fail(KDPT_ERR_ARG, who + ": count must be >= 0");
+  if (!out) return fail(KDPT_ERR_ARG, who + ": null out");
+  int rc = check_adaptive_args(c, floor, threshold, who);
+  if (rc) return rc;
+  if (c->shade_oob) return refuse_shading();
+  HIP_TRY(hipSetDevice(c->device));
+  // everything queued on the context first, the pipelined adds included: the list is built from the state before
+  // the call
+  int active = 0;
+  if ((rc = kdpt_synchronize(c)) || (rc = build_active_list(c, floor, threshold, &active))) return rc;
+  memset(out, 0, sizeof *out);
+  out->pixels = c->npix;
+  out->active = active;
+  if (!active || !count) return KDPT_OK;
+  Adaptive& a = c->mom.adapt;
+  const hipStream_t st = c->stream;
+  HIP_TRY(hipEventRecord(a.ev[0], st));
+  HIP_TRY(hipMemsetAsync(a.totals.get(), 0, sizeof(unsigned long long) * 4, st));
+  const ActiveSet act{a.list.get(), active, a.extra.get(), a.totals.get()};
+  if ((rc = enqueue_iterations(c, first_iter, count, 1, pipeline, batch, c->image, nullptr, &act))) return rc;
+  if ((rc = join_accum(c))) return rc;  // the context's stream after the last add
+  HIP_TRY(hipEventRecord(a.ev[1], st));
+  unsigned long long totals[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(totals, a.totals.get(), sizeof totals, hipMemcpyDeviceToHost, st));
+  if ((rc = kdpt_synchronize(c))) return rc;  // (the groups' fault words too)
+  float ms = 0;
+  HIP_TRY(hipEventElapsedTime(&ms, a.ev[0], a.ev[1]));
+  out->pixel_samples = (long long)active * count;
+  out->segments = (long long)totals[0];
+  out->traced = (long long)totals[3];
+  out->device_ms = ms;
+  return KDPT_OK;
+}
+
+int kdpt_read_sample_counts(kdpt_ctx* c, int* counts) {
+  if (!c) return fail(KDPT_ERR_ARG, "kdpt_read_sample_counts: null ctx");
+  if (!counts) return fail(KDPT_ERR_ARG, "kdpt_read_sample_counts: null counts");
+  if (!c->mom.on) return fail(KDPT_ERR_UNSUPPORTED, "kdpt_read_sample_counts: moments are off (kdpt_set_moments)");
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = join_accum(c);
+  if (rc) return rc;
+  const size_t npix = (size_t)c->npix;
+  if (c->mom.adapt.extra)
+    HIP_TRY(hipMemcpyAsync(counts, c->mom.adapt.extra.get(), sizeof(int) * npix, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (size_t p = 0; p < npix; p++) counts[p] = (int)c->mom.samples + (c->mom.adapt.extra ? counts[p] : 0);
+  return KDPT_OK;
+}
+
+int kdpt_save_counted(kdpt_ctx* c, uint8_t* rgb, float* lin) {
+  if (!c) return fail(KDPT_ERR_ARG, "kdpt_save_counted: null ctx");
+  if (!rgb && !lin) return fail(KDPT_ERR_ARG, "kdpt_save_counted: null rgb and lin");
+  if (!c->mom.on) return fail(KDPT_ERR_UNSUPPORTED, "kdpt_save_counted: moments are off (kdpt_set_moments)");
+  return save_image_pass(c, 0.0f, rgb, lin, true);
+}
+
+int kdpt_selftest_active_list(const float* noise, int npix, float threshold, int* pixels, int* n) {
+  if (npix < 0 || !n || (npix && (!noise || !pixels)) || std::isnan(threshold))
+    return fail(KDPT_ERR_ARG, "kdpt_selftest_active_list: bad arguments");
+  *n = 0;
+  if (!npix) return KDPT_OK;
+  const size_t nblk = (size_t)adapt_blocks(npix);
+  DeviceBuf<float> values;
+  DeviceBuf<unsigned long long> masks;
+  DeviceBuf<int> blocks, list;
+  HIP_TRY(values.alloc((size_t)npix));
+  HIP_TRY(masks.alloc(nblk * (ADAPT_BLOCK / 64)));
+  HIP_TRY(blocks.alloc(2 * nblk + 1));
+  HIP_TRY(list.alloc((size_t)npix));
+  HIP_TRY(hipMemcpy(values.get(), noise, sizeof(float) * (size_t)npix, hipMemcpyHostToDevice));
+  launch_active_list(nullptr, nullptr, nullptr, values.get(), npix, 0, 1.0f, threshold, masks.get(), blocks.get(),
+                     list.get(), 0);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(n, blocks.get() + 2 * nblk, sizeof(int), hipMemcpyDeviceToHost));
+  if (*n < 0 || *n > npix) return fail(KDPT_ERR_HIP, "kdpt_selftest_active_list: count out of range");
+  if (*n) HIP_TRY(hipMemcpy(pixels, list.get(), sizeof(int) * (size_t)*n, hipMemcpyDeviceToHost));
   return KDPT_OK;
 }

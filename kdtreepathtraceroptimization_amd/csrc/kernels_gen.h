@@ -56,20 +56,24 @@ __device__ __attribute__((always_inline)) inline void gen_prologue(int index, in
   for (int e = index; e < nlb; e += gridDim.x * blockDim.x) lb[e] = 0ull;  // k_shade_fused's look-back records
 }
 
+// Lane `index` of the launch makes path `index` of npaths -- the slot: where the path, its pixelIndex and its entry
+// of zero_image go -- from the camera's ray through a pixel: pixel `index` for the camera kernels (pixels null, npaths
+// = W*H), pixel pixels[index] for a launch over a list of pixels (kernels_adaptive.h).
 __device__ __attribute__((always_inline)) inline bool gen_rays_body(
     const kdpt_camera& cam, int iter, int traceDepth, PathBuf out, float focalLength, float dofAngle, int antialias,
     int* counts, int ncounts, int* work, int nwork, unsigned long long* trace_t, unsigned long long* lb, int nlb,
-    float* zero_image, f3& ray_o, f3& ray_d) {
+    float* zero_image, int npaths, const int* pixels, f3& ray_o, f3& ray_d) {
   const int W = cam.resolution[0], H = cam.resolution[1];
   const int index = blockIdx.x * blockDim.x + threadIdx.x;
-  gen_prologue(index, W * H, counts, ncounts, work, nwork, trace_t, lb, nlb);
-  if (index >= W * H) return false;
+  gen_prologue(index, npaths, counts, ncounts, work, nwork, trace_t, lb, nlb);
+  if (index >= npaths) return false;
   if (zero_image) {  // batched iterations: this iteration's partial image starts at zero (no separate fill)
     zero_image[3 * index] = 0.0f;
     zero_image[3 * index + 1] = 0.0f;
     zero_image[3 * index + 2] = 0.0f;
   }
-  const int x = index % W, y = index / W;
+  const int pixel = pixels ? pixels[index] : index;
+  const int x = pixel % W, y = pixel / W;
   const f3 view = mk3(cam.view[0], cam.view[1], cam.view[2]);
   const f3 right = mk3(cam.right[0], cam.right[1], cam.right[2]);
   const f3 upv = mk3(cam.up[0], cam.up[1], cam.up[2]);
@@ -192,7 +196,8 @@ __global__ __launch_bounds__(256) void k_gen_rays_b(GenBatch B) {
   const GenIter& g = B.it[blockIdx.y];
   f3 o, d;
   (void)gen_rays_body(B.cam, g.iter, B.traceDepth, g.out, B.focalLength, B.dofAngle, B.antialias, g.counts,
-                      B.ncounts, g.work, B.nwork, g.trace_t, g.lb, B.nlb, g.zero_image, o, d);
+                      B.ncounts, g.work, B.nwork, g.trace_t, g.lb, B.nlb, g.zero_image,
+                      B.cam.resolution[0] * B.cam.resolution[1], nullptr, o, d);
 }
 
 __device__ inline void flush_counters(Counters* C, const TraverseCounters& cnt, WaveProf* W,
@@ -350,7 +355,7 @@ __global__ __launch_bounds__(GEN_BLOCK) void k_gen_geoms_b(GenGeomsBatch B) {
   f3 o = mk3(0, 0, 0), d = mk3(0, 0, 1);
   const bool valid = gen_rays_body(B.g.cam, g.iter, B.g.traceDepth, g.out, B.g.focalLength, B.g.dofAngle,
                                    B.g.antialias, g.counts, B.g.ncounts, g.work, B.g.nwork, g.trace_t, g.lb, B.g.nlb,
-                                   g.zero_image, o, d);
+                                   g.zero_image, B.g.cam.resolution[0] * B.g.cam.resolution[1], nullptr, o, d);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i == 0) *q.ccount0_next = 0;
   geoms_core<GEN_BLOCK>(B.S, valid && B.g.traceDepth > 0, i, o, d, q.cray, q.hits, q.cand, q.ccount0, q.qbase,

@@ -1,6 +1,7 @@
 // kernels_moments.h -- per-pixel second moments: k_accumulate_moments (the sibling of k_accumulate_batch that
 // also adds the squares), k_noise_map and the two-stage reduction of kdpt_noise_estimate (k_noise_partials,
-// k_noise_final).
+// k_noise_final), and the first two again for per-pixel sample counts (k_noise_map_counted,
+// k_noise_partials_counted: after kdpt_trace_adaptive).
 //
 // A section of kdpt_runtime.hip's translation unit, not a stand-alone header: kdpt_runtime.hip includes it
 // after kernels_selftest.h, and the kernels keep that order in the code object.  Device code and launch-argument
@@ -92,6 +93,53 @@ __global__ __launch_bounds__(NOISE_BLOCK) void k_noise_partials(const float* __r
     const long long p = ((long long)blockIdx.x * NOISE_PER_LANE + k) * NOISE_BLOCK + threadIdx.x;
     if (p >= npix) break;
     const float e = noise_of_pixel(image, sumsq, (int)p, samples, floor);
+    if (isfinite(e)) {
+      r.sum += (double)e;
+      r.max = e > r.max ? e : r.max;
+      r.above += e > threshold ? 1 : 0;
+    } else {
+      r.nonfinite += 1;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    NoisePartial o;
+    o.sum = __shfl_down(r.sum, off, 64);
+    o.above = __shfl_down(r.above, off, 64);
+    o.nonfinite = __shfl_down(r.nonfinite, off, 64);
+    o.max = __shfl_down(r.max, off, 64);
+    r = noise_merge(r, o);
+  }
+  if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = r;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    NoisePartial t = waves[0];
+    for (int w = 1; w < NOISE_BLOCK / 64; w++) t = noise_merge(t, waves[w]);
+    t.pad_ = 0.0f;
+    partials[blockIdx.x] = t;
+  }
+}
+
+// The two per-pixel passes again with per-pixel sample counts n_p = samples + extra[p] (after kdpt_trace_adaptive,
+// kernels_adaptive.h): noise_of_pixel as it is, and k_noise_partials' reduction restated, so that the kernels above
+// stay the code they were.
+__global__ void k_noise_map_counted(const float* __restrict__ image, const float* __restrict__ sumsq,
+                                    const uint32_t* __restrict__ extra, int npix, long long samples, float floor,
+                                    float* __restrict__ noise) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= npix) return;
+  noise[p] = noise_of_pixel(image, sumsq, p, samples + (long long)extra[p], floor);
+}
+__global__ __launch_bounds__(NOISE_BLOCK) void k_noise_partials_counted(
+    const float* __restrict__ image, const float* __restrict__ sumsq, const uint32_t* __restrict__ extra, int npix,
+    long long samples, float floor, float threshold, NoisePartial* __restrict__ partials) {
+  __shared__ NoisePartial waves[NOISE_BLOCK / 64];
+  NoisePartial r{0.0, 0, 0, 0.0f, 0.0f};
+#pragma unroll
+  for (int k = 0; k < NOISE_PER_LANE; k++) {  // (coalesced: the workgroup's lanes take neighbouring pixels)
+    const long long p = ((long long)blockIdx.x * NOISE_PER_LANE + k) * NOISE_BLOCK + threadIdx.x;
+    if (p >= npix) break;
+    const float e = noise_of_pixel(image, sumsq, (int)p, samples + (long long)extra[p], floor);
     if (isfinite(e)) {
       r.sum += (double)e;
       r.max = e > r.max ? e : r.max;

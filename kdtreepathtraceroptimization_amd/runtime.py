@@ -131,7 +131,12 @@ class Noise(C.Structure):  # kdpt_noise: kdpt_noise_estimate's result
                 ("nonfinite", C.c_longlong), ("mean", C.c_double), ("max", C.c_float), ("pad_", C.c_float)]
 
 
-assert C.sizeof(Noise) == 48
+class Adaptive(C.Structure):  # kdpt_adaptive: kdpt_trace_adaptive's result
+    _fields_ = [("pixels", C.c_longlong), ("active", C.c_longlong), ("pixel_samples", C.c_longlong),
+                ("segments", C.c_longlong), ("traced", C.c_longlong), ("device_ms", C.c_double)]
+
+
+assert C.sizeof(Noise) == 48 and C.sizeof(Adaptive) == 48
 assert C.sizeof(Geom) == 236 and C.sizeof(Material) == 56 and C.sizeof(Camera) == 84
 assert C.sizeof(NodeBare) == 64 and C.sizeof(TriBare) == 76 and C.sizeof(PathSegment) == 56
 
@@ -148,6 +153,8 @@ EXPORTS = [
     "kdpt_set_camera", "kdpt_camera_rays", "kdpt_trace_rays", "kdpt_trace_rays_stats", "kdpt_shade_staged",
     "kdpt_set_moments", "kdpt_read_moments", "kdpt_noise_map", "kdpt_noise_estimate", "kdpt_trace_rays_moments",
     "kdpt_selftest_scatter", "kdpt_selftest_shade",
+    "kdpt_active_pixels", "kdpt_trace_adaptive", "kdpt_read_sample_counts", "kdpt_save_counted",
+    "kdpt_selftest_active_list",
 ]
 
 REDUCE_RCCL, REDUCE_COPY = 0, 1  # kdpt_render_sharded's reduce (KDPT_REDUCE_*)
@@ -262,6 +269,13 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.kdpt_noise_estimate.argtypes = [C.c_void_p, C.c_float, C.c_float, P(Noise)]
         lib.kdpt_trace_rays_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int,
                                                 C.c_int, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "kdpt_trace_adaptive"):  # absent from older builds used in A/B runs
+        lib.kdpt_active_pixels.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_void_p, P(C.c_longlong)]
+        lib.kdpt_trace_adaptive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                            P(Adaptive)]
+        lib.kdpt_read_sample_counts.argtypes = [C.c_void_p, P(C.c_int)]
+        lib.kdpt_save_counted.argtypes = [C.c_void_p, P(C.c_uint8), P(C.c_float)]
+        lib.kdpt_selftest_active_list.argtypes = [P(C.c_float), C.c_int, C.c_float, P(C.c_int), P(C.c_int)]
     _lib = lib
     return lib
 
@@ -630,6 +644,46 @@ class PathTracer:
         _check(self.lib.kdpt_noise_estimate(self._ctx, float(floor), float(threshold), C.byref(r)),
                "kdpt_noise_estimate")
         return r
+
+    def active_pixels(self, floor: float = 1e-2, threshold: float = 0.0, out_ptr: Optional[int] = None):
+        """kdpt_active_pixels: the indices (y*W + x, ascending, int32) of the pixels whose noise is finite and above
+        `threshold` -- the list kdpt_trace_adaptive would trace.  out_ptr: write them to that raw pointer (W*H ints of
+        host memory or of the context's device) instead and return their number."""
+        n = C.c_longlong()
+        if out_ptr is not None:
+            _check(self.lib.kdpt_active_pixels(self._ctx, float(floor), float(threshold), C.c_void_p(int(out_ptr)),
+                                               C.byref(n)), "kdpt_active_pixels")
+            return int(n.value)
+        out = np.empty(self.height * self.width, dtype=np.int32)
+        _check(self.lib.kdpt_active_pixels(self._ctx, float(floor), float(threshold), C.c_void_p(out.ctypes.data),
+                                           C.byref(n)), "kdpt_active_pixels")
+        return out[:int(n.value)].copy()
+
+    def trace_adaptive(self, first_iter: int, count: int, pipeline: int = 8, batch: int = 16, floor: float = 1e-2,
+                       threshold: float = 0.0) -> Adaptive:
+        """kdpt_trace_adaptive: iterations first_iter .. first_iter + count - 1 over the active pixels only (noise
+        finite and above `threshold`), added into the image, the second moments and the per-pixel sample counts.
+        Synchronous; returns the call's kdpt_adaptive record."""
+        r = Adaptive()
+        _check(self.lib.kdpt_trace_adaptive(self._ctx, int(first_iter), int(count), int(pipeline), int(batch),
+                                            float(floor), float(threshold), C.byref(r)), "kdpt_trace_adaptive")
+        return r
+
+    def sample_counts(self) -> np.ndarray:
+        """kdpt_read_sample_counts: the samples per pixel, (H, W) int32 (uniform iterations + adaptive ones)."""
+        out = np.empty((self.height, self.width), dtype=np.int32)
+        _check(self.lib.kdpt_read_sample_counts(self._ctx, out.ctypes.data_as(C.POINTER(C.c_int))),
+               "kdpt_read_sample_counts")
+        return out
+
+    def save_counted(self, lin: bool = False):
+        """kdpt_save_counted: save_rgb8's bytes with every pixel divided by its own sample count, (H, W, 3) uint8;
+        lin=True returns (rgb, lin), lin being the (H, W, 3) float32 image save_hdr would write."""
+        rgb = np.empty((self.height, self.width, 3), dtype=np.uint8)
+        flt = np.empty((self.height, self.width, 3), dtype=np.float32) if lin else None
+        _check(self.lib.kdpt_save_counted(self._ctx, rgb.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                          _fptr(flt) if lin else None), "kdpt_save_counted")
+        return (rgb, flt) if lin else rgb
 
     def trace_rays_ptr(self, origins_ptr: int, directions_ptr: int, n: int, radiance_ptr: int, first_iter: int = 1,
                        count: int = 1, normalize: bool = True):

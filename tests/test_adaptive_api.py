@@ -1,0 +1,130 @@
+"""Adaptive sampling (kdpt_active_pixels, kdpt_trace_adaptive, kdpt_read_sample_counts, kdpt_save_counted,
+kdpt_selftest_active_list): what can be checked without a device -- the symbols, kdpt_adaptive's layout against the
+header, every argument refusal with a message that names its entry point, the Python mirror, the section header's
+conventions and the command line's new flags."""
+import ctypes as C
+import math
+import os
+import re
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+from kdtreepathtraceroptimization_amd import cli
+
+KDPT_ERR_ARG = -1
+ENTRY_POINTS = ["kdpt_active_pixels", "kdpt_trace_adaptive", "kdpt_read_sample_counts", "kdpt_save_counted",
+                "kdpt_selftest_active_list"]
+FIELDS = ["pixels", "active", "pixel_samples", "segments", "traced", "device_ms"]
+KERNELS = ("k_adapt_flags", "k_adapt_scan", "k_adapt_list", "k_adapt_rays_b", "k_adapt_geoms_b", "k_accumulate_adapt",
+           "k_save_counted")
+
+
+def test_symbols_are_exported_and_mirrored(kdpt):
+    lib = kdpt.load_library()
+    out = subprocess.run(["nm", "-D", "--defined-only", kdpt.LIB_PATH], capture_output=True, text=True,
+                         check=True).stdout
+    for n in ENTRY_POINTS:
+        assert hasattr(lib, n), n
+        assert re.search(rf"\bT {n}\b", out), n
+        assert n in kdpt.EXPORTS
+    P = C.POINTER
+    assert lib.kdpt_active_pixels.argtypes == [C.c_void_p, C.c_float, C.c_float, C.c_void_p, P(C.c_longlong)]
+    assert lib.kdpt_trace_adaptive.argtypes == [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                                P(kdpt.Adaptive)]
+    assert lib.kdpt_read_sample_counts.argtypes == [C.c_void_p, P(C.c_int)]
+    assert lib.kdpt_save_counted.argtypes == [C.c_void_p, P(C.c_uint8), P(C.c_float)]
+    assert lib.kdpt_selftest_active_list.argtypes == [P(C.c_float), C.c_int, C.c_float, P(C.c_int), P(C.c_int)]
+    for method in ("trace_adaptive", "active_pixels", "sample_counts", "save_counted"):
+        assert callable(getattr(kdpt.PathTracer, method)), method
+
+
+def test_kdpt_adaptive_layout_agrees_with_the_header(kdpt, tmp_path):
+    """A C program compiled against include/kdpt.h prints sizeof(kdpt_adaptive) and every field's offset; the ctypes
+    mirror must say the same (48 bytes)."""
+    src = tmp_path / "layout.c"
+    src.write_text("#include <stdio.h>\n#include <stddef.h>\n#include \"kdpt.h\"\nint main(void) {\n"
+                   "  printf(\"%zu\", sizeof(kdpt_adaptive));\n" +
+                   "".join(f"  printf(\" %zu\", offsetof(kdpt_adaptive, {f}));\n" for f in FIELDS) +
+                   "  printf(\"\\n\");\n  return 0;\n}\n")
+    exe = tmp_path / "layout"
+    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o",
+                    str(exe)], check=True)
+    vals = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    assert vals[0] == 48 == C.sizeof(kdpt.Adaptive)
+    assert vals[1:] == [0, 8, 16, 24, 32, 40] == [getattr(kdpt.Adaptive, f).offset for f in FIELDS]
+    assert [n for n, _ in kdpt.Adaptive._fields_] == FIELDS
+    assert kdpt.Adaptive.device_ms.size == 8 and dict(kdpt.Adaptive._fields_)["device_ms"] is C.c_double
+
+
+def _trace(lib, ctx, first=5, count=1, floor=1e-2, thr=0.5, out=True, kdpt=None):
+    rec = kdpt.Adaptive()
+    return lib.kdpt_trace_adaptive(ctx, first, count, 2, 2, floor, thr, C.byref(rec) if out else None)
+
+
+@pytest.mark.parametrize("kw, word", [
+    (dict(), b"null ctx"), (dict(out=False), b"null out"), (dict(first=0), b"first_iter must be"),
+    (dict(count=-1), b"count must be"), (dict(floor=0.0), b"floor must be"), (dict(floor=-1.0), b"floor must be"),
+    (dict(floor=math.inf), b"floor must be"), (dict(floor=math.nan), b"floor must be"),
+    (dict(thr=math.nan), b"threshold is NaN")], ids=lambda v: None if isinstance(v, dict) else v.decode())
+def test_trace_adaptive_argument_errors_need_no_device(kdpt, kw, word):
+    lib = kdpt.load_library()
+    assert lib.kdpt_create(None, None, 0, C.byref(C.c_void_p())) != 0  # another call's message is current
+    assert _trace(lib, None, kdpt=kdpt, **kw) == KDPT_ERR_ARG
+    msg = lib.kdpt_last_error()
+    assert msg.startswith(b"kdpt_trace_adaptive:") and word in msg, msg
+
+
+def test_the_other_entry_points_refuse_null_arguments_by_name(kdpt):
+    lib = kdpt.load_library()
+    n, buf = C.c_longlong(-7), (C.c_int * 4)()
+    for floor, thr, word in ((1e-2, 0.5, b"null ctx"), (0.0, 0.5, b"floor must be"), (1e-2, math.nan, b"threshold")):
+        assert lib.kdpt_active_pixels(None, floor, thr, C.cast(buf, C.c_void_p), C.byref(n)) == KDPT_ERR_ARG
+        msg = lib.kdpt_last_error()
+        assert msg.startswith(b"kdpt_active_pixels:") and word in msg and n.value == -7, msg
+    assert lib.kdpt_active_pixels(None, 1e-2, 0.5, None, None) == KDPT_ERR_ARG
+    assert lib.kdpt_last_error().startswith(b"kdpt_active_pixels:")
+    assert lib.kdpt_read_sample_counts(None, buf) == KDPT_ERR_ARG
+    assert lib.kdpt_last_error().startswith(b"kdpt_read_sample_counts:") and b"null ctx" in lib.kdpt_last_error()
+    assert lib.kdpt_save_counted(None, None, None) == KDPT_ERR_ARG
+    assert lib.kdpt_last_error().startswith(b"kdpt_save_counted:") and b"null ctx" in lib.kdpt_last_error()
+    vals, cnt = (C.c_float * 4)(), C.c_int(-7)
+    for args in ((None, 4, 0.5, buf, C.byref(cnt)), (vals, -1, 0.5, buf, C.byref(cnt)),
+                 (vals, 4, 0.5, None, C.byref(cnt)), (vals, 4, 0.5, buf, None), (vals, 4, math.nan, buf, C.byref(cnt))):
+        assert lib.kdpt_selftest_active_list(*args) == KDPT_ERR_ARG
+        assert lib.kdpt_last_error().startswith(b"kdpt_selftest_active_list:")
+    assert cnt.value == -7
+
+
+def test_section_header_holds_device_code_only():
+    """csrc/kernels_adaptive.h is a section of kdpt_runtime.hip: kernels and argument structs, no HIP host call
+    (tests/test_stream_discipline.py reads kdpt_runtime.hip alone), and no ordering that depends on an atomic."""
+    csrc = os.path.join(ROOT, "kdtreepathtraceroptimization_amd", "csrc")
+    src = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "kernels_adaptive.h")).read())
+    assert not re.search(r"\bhip[A-Z]\w*\s*\(", src)
+    for kernel in KERNELS:
+        assert re.search(r"__global__[^;{]*\b" + kernel + r"\b", src), kernel
+    assert "atomic" not in src
+    moments = open(os.path.join(csrc, "kernels_moments.h")).read()
+    for kernel in ("k_noise_map_counted", "k_noise_partials_counted"):
+        assert re.search(r"__global__[^;{]*\b" + kernel + r"\b", moments), kernel
+    runtime = open(os.path.join(csrc, "kdpt_runtime.hip")).read()
+    assert "kernels_adaptive.h" in re.findall(r'#include "(kernels_\w+\.h)"', runtime)
+    from kdtreepathtraceroptimization_amd import _build
+    assert "kernels_adaptive.h" in _build.KERNEL_SOURCES
+
+
+def test_cli_parses_the_adaptive_mode():
+    a = cli.parse_args(["s.txt", "--target-noise", "0.3", "--adaptive", "--min-spp", "4", "--iterations", "24"])
+    assert a.adaptive and a.pixel_noise is None and (a.target_noise, a.min_spp, a.iterations) == (0.3, 4, 24)
+    b = cli.parse_args(["s.txt", "--target-noise", "0.3", "--adaptive", "--pixel-noise", "0.5"])
+    assert b.adaptive and b.pixel_noise == 0.5
+    d = cli.parse_args(["s.txt", "--target-noise", "0.3"])
+    assert not d.adaptive and d.pixel_noise is None
+    for bad in (["--adaptive"], ["--target-noise", "0.3", "--pixel-noise", "0.5"],
+                ["--target-noise", "0.3", "--adaptive", "--pixel-noise", "-1"],
+                ["--target-noise", "0.3", "--adaptive", "--pixel-noise", "nan"],
+                ["--target-noise", "0.3", "--adaptive", "--testing"]):
+        with pytest.raises(SystemExit):
+            cli.parse_args(["s.txt", *bad])

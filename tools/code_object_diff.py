@@ -42,6 +42,8 @@ def symbols(lib, tmp, tag):
         if m:
             cur = out.setdefault(m.group(2), [])
             starts.append((int(m.group(1), 16), m.group(2)))
+        elif cur is not None and line.strip() == "...":
+            continue  # objdump's mark for the zero padding up to the next symbol's alignment: not part of the body
         elif cur is not None and line.strip():
             ins, _, note = line.partition("//")
             ins = re.sub(r"\s+", " ", ins).strip()
