@@ -29,12 +29,14 @@ COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "
 # k_trace launch -1 %, profiles/r02_ab_log.md; it reorders instructions only, so the results stay
 # bit-identical).  tools/build_variant.sh takes them from here, so A/B variants build like the product.
 DEVICE_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
-# the sources whose device code the runtime's kernels are compiled from
+# the sources whose device code the runtime's kernels are compiled from: the files that hold device code, and
+# kdpt_runtime.hip, which lists the sections (its host_*.h sections hold host code only and are not hashed)
 KERNEL_SOURCES = ["kdpt_device.h", "kdpt_scene.h", "kdpt_geoms.h", "kdpt_traverse.h", "kdpt_cull.h", "kdpt_wave.h",
                   "kdpt_trace_phase.h", "kdpt_scatter.h", "kdpt_glm_kat.h", "kdpt_bounce_kat.h",
                   "kdpt_math.h", "kdpt_runtime.hip", "glibc_sincostab.h", "kernels_gen.h",
                   "kernels_trace.h", "kernels_brute.h", "kernels_shade.h", "kernels_image.h", "kernels_cast.h",
-                  "kernels_rays.h", "kernels_selftest.h", "kernels_moments.h", "kernels_adaptive.h"]
+                  "kernels_rays.h", "kernels_selftest.h", "kernels_masks.h", "kernels_frames.h", "kernels_moments.h",
+                  "kernels_adaptive.h"]
 
 
 def _run(cmd, log=None):

@@ -1,5 +1,5 @@
 // image_io.cpp -- headless output of the reference's framebuffer (host side of kdpt_save_png /
-// kdpt_save_hdr; the pixel pass itself runs on the GPU, k_save_image in kdpt_runtime.hip).
+// kdpt_save_hdr; the pixel pass itself runs on the GPU, k_save_image in kernels_image.h).
 //
 // The reference writes its image with the vendored stb_image_write (external/include/
 // stb_image_write.h, used by image::savePNG / image::saveHDR, src/image.cpp:22-45).  The encoders

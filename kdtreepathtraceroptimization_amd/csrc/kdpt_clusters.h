@@ -532,7 +532,7 @@ inline void mask_buckets(int n, std::vector<double>& bd) {
 }
 
 // The masks on the host, bucket-major (masks[b ncl + c]: DevScene::cl_mask).  Test infrastructure: the product
-// builds the same cells on the device (kdpt_runtime.hip k_build_masks, the same dir_mask_cell over the same
+// builds the same cells on the device (kernels_masks.h k_build_masks, the same dir_mask_cell over the same
 // entries and buckets; tests/test_gpu_masks.py compares the two).
 inline void build_dir_masks(const ClusterSet& cs, int n, float Kf, std::vector<unsigned long long>& masks) {
   const int ncl = (int)cs.info.size(), nb = 6 * n * n;

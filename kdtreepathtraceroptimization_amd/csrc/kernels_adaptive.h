@@ -4,8 +4,8 @@
 // images through the list (k_accumulate_adapt) and the save pass with per-pixel sample counts (k_save_counted).
 //
 // A section of kdpt_runtime.hip's translation unit, not a stand-alone header: kdpt_runtime.hip includes it
-// after kernels_selftest.h, and the kernels keep that order in the code object.  Device code and launch-argument
-// structs only: no HIP host call lives here (tests/test_stream_discipline.py reads kdpt_runtime.hip).
+// after kernels_frames.h, and the kernels keep that order in the code object.  Device code and launch-argument
+// structs only: no HIP host call lives here (tests/test_stream_discipline.py checks that; the guards read host_*.h).
 #pragma once
 
 namespace {

@@ -2,7 +2,7 @@
 //
 // A section of kdpt_runtime.hip's translation unit, not a stand-alone header: kdpt_runtime.hip includes it
 // after kernels_image.h, and the kernels keep that order in the code object.  Device code and launch-argument
-// structs only: no HIP host call lives here (tests/test_stream_discipline.py reads kdpt_runtime.hip).
+// structs only: no HIP host call lives here (tests/test_stream_discipline.py checks that; the guards read host_*.h).
 #pragma once
 
 namespace {

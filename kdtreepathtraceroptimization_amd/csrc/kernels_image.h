@@ -1,8 +1,9 @@
-// kernels_image.h -- k_final_gather, k_pbo, k_save_image and k_unpack.
+// kernels_image.h -- k_final_gather, k_pbo, k_save_image, k_unpack and k_accumulate_batch (the add of a batch's
+// partial images).
 //
 // A section of kdpt_runtime.hip's translation unit, not a stand-alone header: kdpt_runtime.hip includes it
-// after kernels_shade.h, and the kernels keep that order in the code object.  Device code and launch-argument
-// structs only: no HIP host call lives here (tests/test_stream_discipline.py reads kdpt_runtime.hip).
+// after kernels_shade.h.  Device code and launch-argument structs only: no HIP host call lives here (the
+// static guards read the host sections; tests/test_stream_discipline.py checks that none is here).
 #pragma once
 
 namespace {
@@ -68,6 +69,20 @@ __global__ void k_unpack(PathBuf src, const int* counts, int depth, kdpt_path_se
   s.remainingBounces = fbits(q2.w);
   s.materialIdHit = src.pm[i];
   out[i] = s;
+}
+
+// A batch's partial images added in iteration order (one add per pixel and iteration, as partialGather
+// does), with one read and one write of the accumulation image per batch instead of one per iteration.
+struct PartialImages {
+  const float* p[MAXB];
+  int nb;
+};
+__global__ void k_accumulate_batch(float* __restrict__ image, PartialImages parts, int n3) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n3) return;
+  float v = image[i];
+  for (int b = 0; b < parts.nb; b++) v += parts.p[b][i];
+  image[i] = v;
 }
 
 }  // namespace

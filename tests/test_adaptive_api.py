@@ -99,7 +99,7 @@ def test_the_other_entry_points_refuse_null_arguments_by_name(kdpt):
 
 def test_section_header_holds_device_code_only():
     """csrc/kernels_adaptive.h is a section of kdpt_runtime.hip: kernels and argument structs, no HIP host call
-    (tests/test_stream_discipline.py reads kdpt_runtime.hip alone), and no ordering that depends on an atomic."""
+    (tests/test_stream_discipline.py reads the host sections alone), and no ordering that depends on an atomic."""
     csrc = os.path.join(ROOT, "kdtreepathtraceroptimization_amd", "csrc")
     src = re.sub(r"//[^\n]*", "", open(os.path.join(csrc, "kernels_adaptive.h")).read())
     assert not re.search(r"\bhip[A-Z]\w*\s*\(", src)

@@ -1,4 +1,4 @@
-"""The masked cull's tables as kdpt_create builds them on the device (kdpt_runtime.hip k_build_masks), and the
+"""The masked cull's tables as kdpt_create builds them on the device (kernels_masks.h k_build_masks), and the
 cost of (re)creating a context, which the drop-in shim pays on every camera move (src/main.cpp:1134-1137 calls
 pathtraceFree + pathtraceInit).
 

@@ -105,7 +105,7 @@ def test_python_mirror_declares_the_argtypes(kdpt):
 
 def test_section_header_holds_device_code_only():
     """csrc/kernels_moments.h is a section of kdpt_runtime.hip: kernels and argument structs, no HIP host call
-    (tests/test_stream_discipline.py reads kdpt_runtime.hip alone)."""
+    (tests/test_stream_discipline.py reads the host sections alone)."""
     csrc = os.path.join(ROOT, "kdtreepathtraceroptimization_amd", "csrc")
     src = open(os.path.join(csrc, "kernels_moments.h")).read()
     src = re.sub(r"//[^\n]*", "", src)

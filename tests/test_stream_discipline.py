@@ -22,8 +22,19 @@ import pytest
 
 from conftest import ROOT
 
-SOURCES = [os.path.join(ROOT, "kdtreepathtraceroptimization_amd", "csrc", f)
-           for f in ("kdpt_runtime.hip", "kd_build.hip", "kdpt_owned.h")]
+CSRC = os.path.join(ROOT, "kdtreepathtraceroptimization_amd", "csrc")
+
+
+def runtime_sections(prefix: str):
+    """The sections of kdpt_runtime.hip's translation unit whose names start with `prefix` ("host_": host code,
+    "kernels_": device code), in the order of its #include lines: a new section is read because it is included."""
+    runtime = open(os.path.join(CSRC, "kdpt_runtime.hip")).read()
+    return [os.path.join(CSRC, f) for f in re.findall(r'^#include "(' + prefix + r'\w+\.h)"', runtime, flags=re.M)]
+
+
+# the runtime and every host section it includes, then the device KD build and the owner of the HIP resources
+RUNTIME = [os.path.join(CSRC, "kdpt_runtime.hip")] + runtime_sections("host_")
+SOURCES = RUNTIME + [os.path.join(CSRC, f) for f in ("kd_build.hip", "kdpt_owned.h")]
 SYNC = re.compile(r"\b(hipStreamSynchronize|hipEventSynchronize|hipDeviceSynchronize|kdpt_synchronize)\s*\(")
 DEFAULT_STREAMS = {"0", "nullptr", "NULL", "hipStreamLegacy", "hipStreamPerThread", "0u"}
 # functions where a synchronous copy or fill is fine by construction
@@ -119,7 +130,7 @@ def test_no_null_stream_fills_or_unsynchronised_copies(path):
 
 
 def test_helpers_with_synchronous_copies_are_called_after_a_synchronisation():
-    src = _strip(open(SOURCES[0]).read())
+    src = _strip("\n".join(open(p).read() for p in RUNTIME))  # the runtime with all its host sections
     funcs = _functions(src)
     bad = []
     for helper in CALLERS_SYNC:
@@ -130,6 +141,17 @@ def test_helpers_with_synchronous_copies_are_called_after_a_synchronisation():
                 if not SYNC.search(body[:off]):
                     bad.append(f"{name} calls {helper} at +{off} with no synchronisation before it")
     assert not bad, "\n".join(bad)
+
+
+def test_the_runtime_is_a_list_of_sections():
+    """What lets the guards read the host sections alone: kdpt_runtime.hip defines no function, every host call
+    lives in a host section (no kernels_*.h holds one) and every kernel in a kernel section."""
+    assert len(RUNTIME) > 1 and runtime_sections("kernels_")
+    assert [n for n, _, _ in _functions(_strip(open(RUNTIME[0]).read()))] == []
+    for path in runtime_sections("kernels_"):
+        assert not re.search(r"\bhip[A-Z]\w*\s*\(", _strip(open(path).read())), os.path.basename(path)
+    for path in RUNTIME:
+        assert "__global__" not in _strip(open(path).read()), os.path.basename(path)
 
 
 def test_the_guard_sees_the_pattern():
