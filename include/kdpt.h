@@ -558,6 +558,93 @@ int kdpt_read_sample_counts(kdpt_ctx *ctx, int *counts);
 int kdpt_save_counted(kdpt_ctx *ctx, uint8_t *rgb, float *lin);
 int kdpt_selftest_active_list(const float *noise, int npix, float threshold, int *pixels, int *n);
 
+/* ---- A persistent group: the in-process sharded renderer as an object ----
+ * kdpt_render_sharded's contexts kept alive: one context per device in this process, created once (scene upload
+ * and mask tables once per rank), rendering frames call after call, and, with KDPT_GROUP_MOMENTS, carrying second
+ * moments through the cross-rank reduce, so that the noise estimate and adaptive sampling work on the sharded
+ * deployment.  kdpt_render_sharded is kdpt_group_create, kdpt_group_render_frames, kdpt_group_synchronize and
+ * kdpt_group_destroy.
+ *
+ * kdpt_group_create takes kdpt_render_sharded's arguments and rules: ndev 1 .. 8 contexts on devices[0 .. ndev), a
+ * device may repeat with KDPT_REDUCE_COPY, opt->external_image is ignored, RCCL is loaded at run time
+ * (KDPT_ERR_UNSUPPORTED when it is absent).  KDPT_ERR_ARG, reported before any device work as kdpt_create reports
+ * its own, for a null scene, devices or out, ndev outside 1 .. 8, a reduce that is neither KDPT_REDUCE_*, or an
+ * unknown flag bit; a scene kdpt_create refuses is refused with kdpt_create's code and message, before any device
+ * work too.  A failure part-way releases everything already made and leaves *out NULL.  The group owns its contexts,
+ * the copy reduce's staging buffers, the events recorded across devices and the communicators;
+ * kdpt_group_destroy(NULL) is KDPT_OK.
+ * flags = KDPT_GROUP_MOMENTS: every rank's frame buffers hold S and Q (6*W*H floats, S first, one allocation, so
+ * one reduce moves both) and rank 0's context has moments on (kdpt_set_moments): it keeps sumsq, the sample counter
+ * and, from the first adaptive call on, extra.  Device memory per rank: 2 x 6*W*H floats of frame buffers in
+ * place of 2 x 3*W*H (and rank 0's reduced frame and the copy reduce's staged parts likewise), plus W*H ints for an
+ * adaptive round's list on every rank but the first.
+ *
+ * kdpt_group_render_frames queues frames first_frame .. first_frame + frames - 1 and returns; frames, shares and
+ * the reduce are kdpt_render_sharded's (frame f = global iterations f*spp + 1 .. (f+1)*spp, rank r those with
+ * (iteration - 1 - f*spp) % N == r, two frame buffers in flight, `out` as there: host or rank 0's device memory,
+ * frames * 3*W*H floats, or NULL; a pageable host `out` stays pinned until kdpt_group_synchronize and must stay
+ * allocated until it returns).  kdpt_group_synchronize waits for every rank, checks every rank's fault words
+ * (every rank is drained even when one reports a fault; the first failure is returned) and releases the pinned
+ * `out`.  Without KDPT_GROUP_MOMENTS rank 0's image and `out` are bit-equal to kdpt_render_sharded's for the same
+ * arguments.  A later call continues on the same contexts: its frames add into rank 0's image in frame order, so
+ * frames 0-1 then 2-3 give the image of frames 0-3 in one call, bit for bit.
+ *
+ * Frames with second moments (KDPT_GROUP_MOMENTS).  Rank r's iterations of the frame i1 < i2 < ... (global
+ * numbers, stride N), x an iteration's partial value, from a zeroed buffer and in iteration order:
+ *   S_r = fadd(S_r, x);  Q_r = fadd(Q_r, fmul(x, x))
+ * (two roundings for Q, never a fused multiply-add, as kdpt_set_moments spells for sumsq).  One reduce over 6*W*H
+ * floats: the copy reduce adds the ranks in rank order, S_f = (S_0 + S_1) + ..., Q_f likewise; RCCL runs one
+ * ncclReduce (its order); a rank without an iteration in the frame contributes zeros.  Rank 0 then, per frame and
+ * in one pass: image = fadd(image, S_f), sumsq = fadd(sumsq, Q_f), samples += spp.  `out` receives S_f alone; Q is
+ * read with kdpt_read_moments on rank 0's context.  The image's bits are those of the same group without the flag.
+ * As frames against kdpt_trace_iterations, this is not the bit pattern of one context that adds every iteration
+ * into its image: partial sums are added once per frame.
+ *
+ * kdpt_group_context lends rank `rank`'s context (borrowed: the group still owns it) for calls that leave the
+ * render state alone: kdpt_read_image, kdpt_read_moments, kdpt_noise_map, kdpt_noise_estimate,
+ * kdpt_read_sample_counts, kdpt_save_*, kdpt_get_stats, kdpt_cast_rays, kdpt_trace_rays[_moments],
+ * kdpt_camera_rays.  They see the frames queued so far (rank 0's reads follow the group's last image add without
+ * a kdpt_group_synchronize; fault words are checked only there).  A borrowed context must not receive
+ * kdpt_destroy, nor a call that changes its state: kdpt_trace_iteration[s][_async], kdpt_render_frames,
+ * kdpt_trace_adaptive, kdpt_active_pixels, kdpt_reset, kdpt_set_moments, kdpt_set_options, kdpt_set_camera,
+ * kdpt_set_tuning, kdpt_comm_init -- the kdpt_group_* calls are their counterparts.
+ *
+ * kdpt_group_set_camera and kdpt_group_set_options validate once (kdpt_set_camera's and kdpt_set_options' rules)
+ * and apply to every rank, or, on a refusal, to none; kdpt_group_set_options waits for the queued work first.
+ * kdpt_group_reset waits and resets every rank (rank 0's image, sumsq, samples and extra are zero afterwards).
+ *
+ * Adaptive rounds (KDPT_GROUP_MOMENTS; KDPT_ERR_UNSUPPORTED without it).  extra[p] lives on rank 0, made on first
+ * use, zeroed by kdpt_group_reset.  kdpt_group_active_pixels returns the list A kdpt_active_pixels would build from
+ * rank 0's image, sumsq, samples and extra: the same kernels and the same rule, ascending.
+ * kdpt_group_trace_adaptive is synchronous: it synchronises the group, builds A on rank 0, reads |A| back once,
+ * copies the list to every other rank's device, and gives iteration first_iter + k (k < count) to rank k mod N.
+ * Each rank runs its iterations over A on the batched, pipelined route (path j = the camera's ray of that
+ * iteration through pixel A[j], pixelIndex j, as in kdpt_trace_adaptive) and accumulates them in order, from a
+ * zeroed buffer of 6 |A| floats: s_r[j] = fadd(s_r[j], x), q_r[j] = fadd(q_r[j], fmul(x, x)).  The slot buffers
+ * are reduced as frames are (rank order for the copy reduce), and rank 0 does, for every slot j and channel,
+ *   image[A[j]] = fadd(image[A[j]], s[j]);  sumsq[A[j]] = fadd(sumsq[A[j]], q[j]);  extra[A[j]] += count.
+ * The partial sums are added once per round, not once per iteration, so the result is NOT the bit pattern of
+ * kdpt_trace_adaptive on one context (as frames are not kdpt_trace_iterations'); it does not depend on pipeline
+ * or batch.  `out` is filled as kdpt_trace_adaptive fills it, segments and traced summed over the ranks,
+ * device_ms rank 0's (from after the list to after the round's add).  With |A| = 0 or count = 0 nothing changes;
+ * the uniform `samples` counter and every rank's kdpt_stats do not move.  Errors are kdpt_trace_adaptive's (a
+ * null group for its null ctx), reported before any device work; the single-context calls keep refusing a
+ * context that is in a communicator. */
+typedef struct kdpt_group kdpt_group;
+#define KDPT_GROUP_MOMENTS 1   /* every rank carries second moments; rank 0 keeps sumsq, samples, extra */
+int kdpt_group_create(const kdpt_scene *scene, const kdpt_options *opt, int ndev, const int *devices,
+                      int reduce, int flags, kdpt_group **out);
+int kdpt_group_render_frames(kdpt_group *g, int first_frame, int frames, int spp, int pipeline, int batch, float *out);
+int kdpt_group_synchronize(kdpt_group *g);
+int kdpt_group_context(kdpt_group *g, int rank, kdpt_ctx **ctx);   /* borrowed */
+int kdpt_group_active_pixels(kdpt_group *g, float floor, float threshold, int *pixels, long long *n);
+int kdpt_group_trace_adaptive(kdpt_group *g, int first_iter, int count, int pipeline, int batch,
+                              float floor, float threshold, kdpt_adaptive *out);
+int kdpt_group_set_camera(kdpt_group *g, const kdpt_camera *camera);
+int kdpt_group_set_options(kdpt_group *g, const kdpt_options *opt);
+int kdpt_group_reset(kdpt_group *g);
+int kdpt_group_destroy(kdpt_group *g);
+
 int kdpt_destroy(kdpt_ctx *ctx);
 /* The message of the most recent failing call of any kdpt_* function on the calling thread (each thread has its
  * own; "" before the first failure).  A successful call leaves it alone, so read it only after a non-OK return.

@@ -27,11 +27,19 @@ PNG / HDR are divided by the samples actually rendered.  Without --target-noise 
 kdpt_trace_adaptive over the pixels whose own noise is above --pixel-noise T (default E) until the mean is <= E, no
 pixel is above T or --iterations is reached.  The PNG / HDR then divide each pixel by its own sample count
 (kdpt_save_counted).  A pixel whose noise reads 0 after --min-spp samples is never revisited: --min-spp is the guard.
+
+--devices 0,1,... renders on a persistent group of contexts, one per listed device (kdpt_group; --reduce rccl, or copy,
+which also lets a device repeat): samples per pixel sharded over the ranks in frames of pipeline x batch x ndev
+iterations, the rest of --iterations in shorter frames that keep the iteration numbers.  --target-noise checks rank
+0's estimate after every frame, --adaptive switches to kdpt_group_trace_adaptive rounds after --min-spp, and the
+output comes from rank 0's context through the same save paths; the JSON gains "devices" and "frames".  Without
+--devices nothing changes.
 """
 from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -48,6 +56,17 @@ def scene_header(path: str) -> dict:
             elif len(tok) >= 2 and tok[0] == "FILE":
                 out["file"] = tok[1]
     return out
+
+
+def device_list(text: str):
+    """--devices: "0,1,2" -> [0, 1, 2] (1 to 8 entries, each >= 0)."""
+    try:
+        devs = [int(t) for t in text.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a comma-separated list of device numbers: {text!r}")
+    if not 1 <= len(devs) <= 8 or min(devs) < 0:
+        raise argparse.ArgumentTypeError("1 to 8 device numbers, each >= 0")
+    return devs
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -97,7 +116,18 @@ def parse_args(argv=None) -> argparse.Namespace:
                          "is above --pixel-noise (kdpt_trace_adaptive)")
     ap.add_argument("--pixel-noise", type=float, default=None, metavar="T",
                     help="with --adaptive: a pixel goes again while its noise is above T (default: E)")
+    ap.add_argument("--devices", type=device_list, default=None, metavar="0,1,...",
+                    help="render on a persistent group of contexts, one per listed device (kdpt_group): samples per "
+                         "pixel sharded over them in frames of pipeline x batch x ndev iterations")
+    ap.add_argument("--reduce", choices=["rccl", "copy"], default="rccl",
+                    help="with --devices: the frames' cross-rank reduce (copy: peer copies to the first device, which "
+                         "also lets a device repeat)")
     a = ap.parse_args(argv)
+    if a.devices is not None:
+        if a.testing:
+            ap.error("--devices renders in pipelined frames; it cannot be combined with --testing")
+        if a.first_iteration != 1:
+            ap.error("--devices numbers its frames' iterations from 1; --first-iteration cannot be combined with it")
     if a.adaptive and a.target_noise is None:
         ap.error("--adaptive needs --target-noise")
     if a.pixel_noise is not None and not a.adaptive:
@@ -178,6 +208,111 @@ def render_adaptive(pt, a: argparse.Namespace, limit: int):
     return done, est, totals
 
 
+def frame_plan(done: int, limit: int, per_frame: int):
+    """The next kdpt_group_render_frames call after `done` iterations (a multiple of per_frame) with `limit` as the
+    end: (first_frame, frames, spp).  A whole frame of per_frame iterations while one fits; the rest in frames of
+    gcd(per_frame, rest) iterations, whose numbering continues where the whole frames ended."""
+    rest = limit - done
+    if rest >= per_frame:
+        return done // per_frame, 1, per_frame
+    g = math.gcd(per_frame, rest)
+    return done // g, rest // g, g
+
+
+def render_group(grp, a: argparse.Namespace, limit: int):
+    """--devices: frames through the group up to `limit` iterations, or with --target-noise until rank 0's estimate
+    is <= E (checked after every call from --min-spp on), or with --adaptive uniform frames up to --min-spp and then
+    kdpt_group_trace_adaptive rounds as render_adaptive runs them on one context.  Returns the iterations done, the
+    last estimate, the adaptive totals (None without --adaptive) and the frames rendered."""
+    ndev = len(grp.devices)
+    per_frame = max(1, min(16, a.pipeline)) * max(1, min(16, a.batch)) * ndev
+    pt = grp.context(0)
+    thr = a.target_noise if a.pixel_noise is None else a.pixel_noise
+    uniform = min(a.min_spp, limit) if a.adaptive else limit
+    done, frames, est = 0, 0, None
+    while done < uniform:
+        first, n, spp = frame_plan(done, uniform, per_frame)
+        grp.render_frames(first, n, spp, pipeline=a.pipeline, batch=a.batch)
+        grp.synchronize()
+        done += n * spp
+        frames += n
+        if a.target_noise is not None and not a.adaptive and done >= a.min_spp:
+            est = pt.noise_estimate(a.noise_floor, a.target_noise)
+            if est.mean <= a.target_noise:
+                break
+    if not a.adaptive:
+        return done, est, None, frames
+    totals = {"pixel_samples": done * pt.width * pt.height, "segments": 0, "rounds": []}
+    while done >= 2:
+        est = pt.noise_estimate(a.noise_floor, thr)
+        if est.mean <= a.target_noise or est.above == 0 or done >= limit:
+            break
+        n = min(per_frame, limit - done)
+        r = grp.trace_adaptive(1 + done, n, pipeline=a.pipeline, batch=a.batch, floor=a.noise_floor, threshold=thr)
+        done += n
+        totals["pixel_samples"] += int(r.pixel_samples)
+        totals["segments"] += int(r.segments)
+        totals["rounds"].append({"active": int(r.active), "iterations": n, "device_ms": round(r.device_ms, 4)})
+    return done, est, totals, frames
+
+
+def write_outputs(pt, a: argparse.Namespace, base: str, spp: int, counted: bool):
+    """The PNG / HDR / noise map of a context's image: the files written.  counted: every pixel divided by its own
+    sample count (after adaptive rounds), then the same host encoders."""
+    written = []
+    if counted:
+        from .runtime import hdr_encode, png_encode
+        rgb, lin = pt.save_counted(lin=True)
+        for ext, on, encode, pixels in ((".png", not a.no_png, png_encode, rgb), (".hdr", a.hdr, hdr_encode, lin)):
+            if on:
+                with open(base + ext, "wb") as f:
+                    f.write(encode(pixels))
+                written.append(base + ext)
+    else:
+        if not a.no_png:
+            pt.save_png(base + ".png", float(spp))
+            written.append(base + ".png")
+        if a.hdr:
+            pt.save_hdr(base + ".hdr", float(spp))
+            written.append(base + ".hdr")
+    if a.noise_map and spp >= 2:
+        import numpy as np
+        np.save(base + ".noise.npy", pt.noise_map(a.noise_floor))
+        written.append(base + ".noise.npy")
+    return written
+
+
+def main_group(a: argparse.Namespace, sd, hdr: dict, iterations: int, info: dict) -> int:
+    """main() with --devices: the render through a RenderGroup, the output from rank 0's context."""
+    from .runtime import REDUCE_COPY, REDUCE_RCCL, RenderGroup
+    moments = a.target_noise is not None
+    with RenderGroup(sd, a.devices, options_from_args(a), reduce=REDUCE_COPY if a.reduce == "copy" else REDUCE_RCCL,
+                     moments=moments) as grp:
+        t0 = time.perf_counter()
+        spp, est, adaptive, frames = render_group(grp, a, iterations)
+        dt = time.perf_counter() - t0
+        pt = grp.context(0)
+        segments = sum(int(grp.context(r).stats().total_segments) for r in range(len(a.devices)))
+        base = a.out or f"{hdr['file'] or os.path.splitext(os.path.basename(a.scene))[0]}.{spp}samp"
+        written = write_outputs(pt, a, base, spp, adaptive is not None)
+        counts = pt.sample_counts() if adaptive is not None else None
+    segments += adaptive["segments"] if adaptive is not None else 0
+    info.update({"devices": a.devices, "reduce": a.reduce, "frames": frames, "segments": segments,
+                 "seconds": round(dt, 4), "mrays_per_s": round(segments / dt / 1e6, 2) if dt > 0 else None,
+                 "ms_per_iteration": round(dt * 1e3 / spp, 4), "written": written})
+    if a.target_noise is not None:
+        info.update({"spp": spp, "target_noise": a.target_noise, "noise_floor": a.noise_floor,
+                     "noise": None if est is None else {
+                         "mean": est.mean, "max": est.max, "above": int(est.above), "nonfinite": int(est.nonfinite),
+                         "pixels": int(est.pixels), "samples": int(est.samples)}})
+    if adaptive is not None:
+        info.update({"pixel_noise": a.target_noise if a.pixel_noise is None else a.pixel_noise,
+                     "pixel_samples": adaptive["pixel_samples"], "mean_spp": float(counts.mean()),
+                     "max_spp": int(counts.max()), "adaptive_rounds": adaptive["rounds"]})
+    print(json.dumps(info), flush=True)
+    return 0
+
+
 def main(argv=None) -> int:
     a = parse_args(argv)
     from .runtime import PathTracer, SceneData
@@ -185,7 +320,8 @@ def main(argv=None) -> int:
     iterations = a.iterations if a.iterations is not None else (hdr["iterations"] or 1)
     if iterations < 1:
         raise SystemExit("--iterations must be >= 1")
-    kd_dev = a.device if (a.kd_build == "gpu" and not a.dry_run) else None  # --dry-run needs no GPU
+    build_dev = a.devices[0] if a.devices is not None else a.device
+    kd_dev = build_dev if (a.kd_build == "gpu" and not a.dry_run) else None  # --dry-run needs no GPU
     sd = SceneData.from_files(a.scene, a.mesh, res=tuple(a.res) if a.res else None, depth=a.depth, kd_device=kd_dev)
     W, H = sd.resolution
     info = {"scene": a.scene, "mesh": a.mesh, "resolution": [W, H], "iterations": iterations,
@@ -196,6 +332,8 @@ def main(argv=None) -> int:
         print(json.dumps(info), flush=True)
         sd.close()
         return 0
+    if a.devices is not None:
+        return main_group(a, sd, hdr, iterations, info)
     opt = options_from_args(a)
     spp, est = iterations, None  # the samples per pixel actually rendered, and the adaptive stop's last estimate
     with PathTracer(sd, opt, device=a.device) as pt:

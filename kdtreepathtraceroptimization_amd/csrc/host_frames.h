@@ -1,5 +1,6 @@
-// host_frames.h -- spp-sharded frames across GPUs (kdpt_comm_*, kdpt_render_frames, kdpt_render_sharded), RCCL
-// loaded at run time, and kdpt_destroy (which releases the communicator).
+// host_frames.h -- spp-sharded frames across GPUs (kdpt_comm_*, kdpt_render_frames), RCCL loaded at run time, and
+// kdpt_destroy (which releases the communicator).  The in-process group of contexts (kdpt_group_*, and
+// kdpt_render_sharded on top of it) is host_group.h, which uses this section's frame helpers.
 //
 // A host section of kdpt_runtime.hip's translation unit, not a stand-alone header: kdpt_runtime.hip includes it
 // after host_output.h.  Host code only: no kernel is defined here (the kernels_*.h sections hold them), and
@@ -76,8 +77,13 @@ void release_comm(kdpt_ctx* c) {
   c->frames.owns_comm = false;
 }
 
-int frame_buffers(kdpt_ctx* c) {
-  const size_t n3 = 3 * (size_t)c->npix;
+// Floats of a frame buffer: S alone, or, for a rank of a group whose frames carry second moments, S then Q in one
+// allocation, so that one reduce moves both.  (The flag is the group's: a context's buffers are made once, by the
+// first frame, and a context belongs to one group for its whole life.)
+size_t frame_floats(const kdpt_ctx* c, bool moments) { return (moments ? 6 : 3) * (size_t)c->npix; }
+
+int frame_buffers(kdpt_ctx* c, bool moments = false) {
+  const size_t n3 = frame_floats(c, moments);
   if (!c->frames.reduce_stream) {
     int rc = create_stream(c, &c->frames.reduce_stream);
     if (rc) return rc;
@@ -113,17 +119,22 @@ void frame_share(int f, int spp, int n, int r, int* first, int* count) {
 // Queue frame f's share of this rank into frame_buf[f & 1] (zeroed first, after its previous reduce), and make
 // the reduce stream wait for it: the share's last add (c->pipe.acc_last), or, for a rank with no iterations in the
 // frame, the zeroing itself, done on the reduce stream (which already follows the previous reduce).
-int enqueue_frame(kdpt_ctx* c, int f, int spp, int pipeline, int batch) {
-  int rc = frame_buffers(c);
+int enqueue_frame(kdpt_ctx* c, int f, int spp, int pipeline, int batch, bool moments = false) {
+  int rc = frame_buffers(c, moments);
   if (rc) return rc;
   float* fb = c->frames.buf[f & 1].get();
   int first, count;
   frame_share(f, spp, c->frames.nranks, c->frames.rank, &first, &count);
+  const size_t nf = frame_floats(c, moments);
   if (count > 0) {
-    if ((rc = enqueue_iterations(c, {first, count, c->frames.nranks, pipeline, batch, fb, c->frames.ev[f & 1]}))) return rc;
+    IterationsCall call{first, count, c->frames.nranks, pipeline, batch, fb, c->frames.ev[f & 1]};
+    // a frame that carries second moments: the share's squares go to the buffer's second half in the same adds
+    if (moments) call.sumsq = fb + 3 * (size_t)c->npix;
+    call.zero_floats = nf;
+    if ((rc = enqueue_iterations(c, call))) return rc;
     HIP_TRY(hipStreamWaitEvent(c->frames.reduce_stream, c->pipe.acc_last, 0));
   } else {
-    HIP_TRY(hipMemsetAsync(fb, 0, sizeof(float) * 3 * (size_t)c->npix, c->frames.reduce_stream));
+    HIP_TRY(hipMemsetAsync(fb, 0, sizeof(float) * nf, c->frames.reduce_stream));
   }
   return KDPT_OK;
 }
@@ -235,125 +246,5 @@ int kdpt_render_frames(kdpt_ctx* c, int first_frame, int frames, int spp, int pi
     // (entry points that read or write the image, and adds into it, follow the last reduce: join_accum)
     c->pipe.img_last = c->frames.ev[f & 1];
   }
-  return KDPT_OK;
-}
-
-int kdpt_render_sharded(const kdpt_scene* scene, const kdpt_options* opt, int ndev, const int* devices,
-                        int first_frame, int frames, int spp, int pipeline, int batch, int reduce, float* out) {
-  if (!scene || ndev < 1 || ndev > 8 || !devices || first_frame < 0 || frames < 0 || spp < 1 ||
-      (reduce != KDPT_REDUCE_RCCL && reduce != KDPT_REDUCE_COPY))
-    return fail(KDPT_ERR_ARG, "bad arguments");
-  kdpt_options o;
-  if (opt) o = *opt;
-  else kdpt_default_options(&o);
-  o.external_image = nullptr;
-  // Owning locals, released at every return last first: the contexts (kdpt_destroy drains a context's streams),
-  // then the copy reduce's staged frames, then every event this call records across devices, each on its device.
-  struct XEvents {
-    std::vector<std::pair<int, Event>> v;
-    ~XEvents() {
-      for (auto& de : v)
-        if (hipSetDevice(de.first) == hipSuccess) de.second.reset();
-    }
-  } xev;
-  std::vector<DeviceBuf<float>> staged(ndev);  // copy reduce: the other ranks' frames on device 0
-  std::vector<std::unique_ptr<kdpt_ctx, int (*)(kdpt_ctx*)>> cs;
-  int rc;
-  for (int i = 0; i < ndev; i++) {
-    kdpt_ctx* ci = nullptr;
-    if ((rc = kdpt_create(scene, &o, devices[i], &ci))) return rc;
-    cs.emplace_back(ci, kdpt_destroy);
-    cs[i]->frames.nranks = ndev;
-    cs[i]->frames.rank = i;
-  }
-  const Rccl* R = nullptr;
-  if (reduce == KDPT_REDUCE_RCCL) {
-    R = rccl();
-    if (!R) return fail(KDPT_ERR_UNSUPPORTED, "librccl.so.1 not found");
-    std::vector<ncclComm_t> comms(ndev);
-    const ncclResult_t e = R->commInitAll(comms.data(), ndev, devices);
-    if (e != ncclSuccess) return fail(KDPT_ERR_HIP, std::string("rccl: ") + R->errorString(e));
-    for (int i = 0; i < ndev; i++) {
-      cs[i]->frames.comm = comms[i];
-      cs[i]->frames.owns_comm = true;
-    }
-  }
-  kdpt_ctx* c0 = cs[0].get();
-  const int n3 = 3 * c0->npix;
-  if (reduce == KDPT_REDUCE_COPY)
-    for (int i = 1; i < ndev; i++)
-      if (const hipError_t e = staged[i].alloc((size_t)n3)) return hip_fail("hipMalloc", e);
-  // a pageable host `out` pinned for the call (released by the final kdpt_synchronize of c0)
-  pin_host_out(c0, out, sizeof(float) * (size_t)n3 * (size_t)frames);
-  hipError_t he;  // the HIP status behind a failing step
-  auto xevent = [&](int dev, hipStream_t st, hipEvent_t* e) {
-    Event ev;
-    if ((he = hipSetDevice(dev)) != hipSuccess || (he = ev.create_untimed()) != hipSuccess ||
-        (he = hipEventRecord(ev, st)) != hipSuccess)
-      return false;
-    *e = ev;
-    xev.v.emplace_back(dev, std::move(ev));
-    return true;
-  };
-  for (int k = 0; k < frames; k++) {
-    const int f = first_frame + k;
-    // each rank queues its share on its batch streams; its reduce stream waits for the share (as in
-    // kdpt_render_frames), so frame f + 1's adds never queue behind frame f's reduce
-    std::vector<hipEvent_t> share_done(ndev, nullptr);  // each rank's last add of the frame (copy reduce)
-    for (int i = 0; i < ndev; i++) {
-      kdpt_ctx* ci = cs[i].get();
-      if ((he = hipSetDevice(ci->device)) != hipSuccess) return hip_fail("hipSetDevice", he);
-      if ((rc = enqueue_frame(ci, f, spp, pipeline, batch))) return rc;
-      if ((rc = reduce_spin(ci, ci->frames.reduce_stream))) return rc;
-      // (recorded on the rank's reduce stream, which already waits for the share)
-      if (!xevent(ci->device, ci->frames.reduce_stream, &share_done[i])) return hip_fail("frame events", he);
-    }
-    if ((he = hipSetDevice(c0->device)) != hipSuccess) return hip_fail("hipSetDevice", he);
-    if ((rc = frame_buffers(c0))) return rc;
-    if (reduce == KDPT_REDUCE_RCCL) {
-      R->groupStart();
-      ncclResult_t e = ncclSuccess;
-      for (int i = 0; i < ndev && e == ncclSuccess; i++)
-        e = R->reduce(cs[i]->frames.buf[f & 1].get(), i == 0 ? c0->frames.sum.get() : nullptr, (size_t)n3, ncclFloat32,
-                      ncclSum, 0, (ncclComm_t)cs[i]->frames.comm, cs[i]->frames.reduce_stream);
-      const ncclResult_t e2 = R->groupEnd();
-      if (e != ncclSuccess || e2 != ncclSuccess)
-        return fail(KDPT_ERR_HIP, std::string("rccl: ") + R->errorString(e != ncclSuccess ? e : e2));
-    } else {
-      // device 0's reduce stream waits for every rank's share and copies the others' over (peer copies: xGMI
-      // between GPUs), then adds them in rank order
-      FrameParts parts{};
-      parts.n = ndev;
-      parts.p[0] = c0->frames.buf[f & 1].get();
-      for (int i = 1; i < ndev; i++) {
-        kdpt_ctx* ci = cs[i].get();
-        if ((he = hipSetDevice(c0->device)) != hipSuccess ||
-            (he = hipStreamWaitEvent(c0->frames.reduce_stream, share_done[i], 0)) != hipSuccess ||
-            (he = hipMemcpyPeerAsync(staged[i].get(), c0->device, ci->frames.buf[f & 1].get(), ci->device,
-                                     sizeof(float) * (size_t)n3, c0->frames.reduce_stream)) != hipSuccess)
-          return hip_fail("copy reduce: peer copy", he);
-        parts.p[i] = staged[i].get();
-      }
-      hipLaunchKernelGGL(k_sum_frames, dim3((n3 + 255) / 256), dim3(256), 0, c0->frames.reduce_stream,
-                         c0->frames.sum.get(), parts, n3);
-      if ((he = hipGetLastError()) != hipSuccess) return hip_fail("k_sum_frames", he);
-      // the other ranks' frame_buf[f & 1] may be reused (frame f + 2) once these copies are done
-      hipEvent_t done;
-      if (!xevent(c0->device, c0->frames.reduce_stream, &done)) return hip_fail("copy reduce: done event", he);
-      for (int i = 1; i < ndev; i++)
-        if ((he = hipSetDevice(cs[i]->device)) != hipSuccess ||
-            (he = hipStreamWaitEvent(cs[i]->frames.reduce_stream, done, 0)) != hipSuccess)
-          return hip_fail("copy reduce: wait for the done event", he);
-    }
-    if ((he = hipSetDevice(c0->device)) != hipSuccess) return hip_fail("hipSetDevice", he);
-    if ((rc = finish_frame(c0, c0->frames.sum.get(), out, k, c0->frames.reduce_stream))) return rc;
-    for (int i = 0; i < ndev; i++) {
-      if ((he = hipSetDevice(cs[i]->device)) != hipSuccess ||
-          (he = hipEventRecord(cs[i]->frames.ev[f & 1], cs[i]->frames.reduce_stream)) != hipSuccess)
-        return hip_fail("hipEventRecord", he);
-    }
-  }
-  for (int i = 0; i < ndev; i++)
-    if ((rc = kdpt_synchronize(cs[i].get()))) return rc;
   return KDPT_OK;
 }

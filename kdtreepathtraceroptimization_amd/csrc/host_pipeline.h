@@ -10,6 +10,8 @@
 namespace {
 
 // The pixels an adaptive round traces (its batches' source) and the add through them: `extra` counts the samples.
+// extra null (a rank of kdpt_group_trace_adaptive): the add goes to a slot buffer, not through the list -- slot j's
+// three floats at 3 j of the call's target and of its sumsq, for the group's reduce to carry to rank 0.
 struct ActiveSet {
   const int* list;
   int n;
@@ -28,11 +30,12 @@ Parts fill_parts(const float* const* partials, int nb) {
 // The add of nb partial images (iteration order) into `target` on stream st: k_accumulate_batch, or, with `sumsq`
 // (the context keeps second moments and the target is its image), k_accumulate_moments, which adds the squares
 // into it in the same pass.  With an active set the partial images hold list slots, not pixels:
-// k_accumulate_adapt adds them through the list and counts the samples into `extra`.
+// k_accumulate_adapt adds them through the list and counts the samples into `extra`; an active set without `extra`
+// adds the 3 n slot floats in place (k_accumulate_moments over the slots).
 int launch_accumulate(kdpt_ctx* c, float* target, float* sumsq, const float* const* partials, int nb, hipStream_t st,
                       const ActiveSet* act = nullptr) {
-  const int n3 = 3 * c->npix;
-  if (act) {
+  const int n3 = 3 * (act ? act->n : c->npix);
+  if (act && act->extra) {
     hipLaunchKernelGGL(k_accumulate_adapt, dim3((act->n + 255) / 256), dim3(256), 0, st, target, sumsq, act->extra,
                        act->list, act->n, fill_parts<AdaptParts>(partials, nb));
   } else if (sumsq) {
@@ -99,11 +102,13 @@ int accumulate_iteration(kdpt_ctx* c, int iter) {
 
 // Iterations first_iter + k * stride (k < count) in batches of `batch`, `pipeline` batches in flight, their
 // partial images added into `target` (the context's image, or a frame buffer of kdpt_render_frames) in
-// iteration order.  Each batch's add runs on the batch's own stream, after the previous batch's add (the one
+// iteration order; with `sumsq` (beside a target that is not the image: a frame buffer that carries second moments,
+// a group's slot buffer) their squares into it in the same pass, as the image's moments get them.  Each batch's add runs on the batch's own stream, after the previous batch's add (the one
 // cross-stream wait of the pipeline, normally satisfied by the time it is reached): no stream ever waits for a
 // whole batch, so none holds an in-order hardware queue that batch streams share (HIP multiplexes a process's
 // streams onto GPU_MAX_HW_QUEUES queues, 4 by default).  zero_after: the target is first zeroed, after that
-// event (a frame buffer after its previous reduce).  Returns once everything is queued.
+// event (a frame buffer after its previous reduce), zero_floats of it (0: 3 W H; a target with its sumsq behind it in
+// one allocation says how many).  Returns once everything is queued.
 // act (kdpt_trace_adaptive): every batch starts from the active list instead of the camera's W*H rays and is added
 // through it; the list was built on the context's stream, so each group's first launch of the call follows `entry`.
 // The segment and intersect totals go to the round's own (`totals`, Adaptive::totals' layout), and kdpt_stats and
@@ -114,6 +119,8 @@ struct IterationsCall {
   hipEvent_t zero_after = nullptr;
   const ActiveSet* act = nullptr;
   unsigned long long* totals = nullptr;  // with act
+  float* sumsq = nullptr;                // the second target, beside a target that is not the image
+  size_t zero_floats = 0;
 };
 int enqueue_iterations(kdpt_ctx* c, const IterationsCall& call) {
   if (c->shade_oob) return refuse_shading();
@@ -210,13 +217,14 @@ int enqueue_iterations(kdpt_ctx* c, const IterationsCall& call) {
       if (c->pipe.img_last && into_image) HIP_TRY(hipStreamWaitEvent(st, c->pipe.img_last, 0));
       if (call.zero_after) {
         HIP_TRY(hipStreamWaitEvent(st, call.zero_after, 0));
-        HIP_TRY(hipMemsetAsync(call.target, 0, sizeof(float) * 3 * (size_t)c->npix, st));
+        const size_t nz = call.zero_floats ? call.zero_floats : 3 * (size_t)c->npix;
+        HIP_TRY(hipMemsetAsync(call.target, 0, sizeof(float) * nz, st));
       }
       first = false;
     }
     const float* partials[MAXB];
     for (int b = 0; b < nb; b++) partials[b] = its[b]->partial;  // in iteration order
-    float* const sumsq = into_image && c->mom.on ? c->mom.sumsq.get() : nullptr;
+    float* const sumsq = !into_image ? call.sumsq : c->mom.on ? c->mom.sumsq.get() : nullptr;
     if ((rc = launch_accumulate(c, call.target, sumsq, partials, nb, st, act))) return rc;
     HIP_TRY(hipEventRecord(grp.acc_ev, st));
     c->pipe.acc_last = grp.acc_ev;

@@ -73,4 +73,5 @@ using namespace kdpt;
 #include "host_frames.h"
 #include "host_queries.h"
 #include "host_moments.h"
+#include "host_group.h"
 #include "host_selftest.h"

@@ -1,7 +1,7 @@
 // kernels_adaptive.h -- adaptive sampling (kdpt_trace_adaptive): the list of the pixels whose noise is above a
 // threshold (k_adapt_flags, k_adapt_scan, k_adapt_list), bounce 0 of a batch that starts from that list
 // (k_adapt_rays_b, k_adapt_geoms_b, the counterparts of k_gen_rays_b / k_gen_geoms_b), the add of a batch's partial
-// images through the list (k_accumulate_adapt) and the save pass with per-pixel sample counts (k_save_counted).
+// images through the list (k_accumulate_adapt), a group's round added through it (k_adapt_slots) and the save pass with per-pixel sample counts (k_save_counted).
 //
 // A section of kdpt_runtime.hip's translation unit, not a stand-alone header: kdpt_runtime.hip includes it
 // after kernels_frames.h, and the kernels keep that order in the code object.  Device code and launch-argument
@@ -170,6 +170,29 @@ __global__ void k_accumulate_adapt(float* __restrict__ image, float* __restrict_
     sumsq[dst + c] = q;
   }
   extra[list[j]] += (uint32_t)parts.nb;
+}
+
+// An adaptive round of a group (kdpt_group_trace_adaptive) on rank 0, one lane per slot.  Every part is a rank's slot
+// buffer after the round: s at [0, 3 n), q at [3 n, 6 n) (the copy reduce's N staged parts, or RCCL's one reduced
+// buffer).  For slot j, pixel p = list[j] and each channel: s = the parts' s[j] in rank order, q likewise, image[p] =
+// fadd(image[p], s), sumsq[p] = fadd(sumsq[p], q), and extra[p] += count.  The list has no pixel twice.
+__global__ void k_adapt_slots(float* __restrict__ image, float* __restrict__ sumsq, uint32_t* __restrict__ extra,
+                              const int* __restrict__ list, int n, FrameParts parts, uint32_t count) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int p = list[j];
+  const size_t dst = 3 * (size_t)p, src = 3 * (size_t)j, n3 = 3 * (size_t)n;
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    float s = parts.p[0][src + c], q = parts.p[0][n3 + src + c];
+    for (int k = 1; k < parts.n; k++) {
+      s = __fadd_rn(s, parts.p[k][src + c]);
+      q = __fadd_rn(q, parts.p[k][n3 + src + c]);
+    }
+    image[dst + c] = __fadd_rn(image[dst + c], s);
+    sumsq[dst + c] = __fadd_rn(sumsq[dst + c], q);
+  }
+  extra[p] += count;
 }
 
 // k_save_image with each source pixel divided by its own sample count n_p = samples + extra[p] (extra null: every

@@ -155,9 +155,13 @@ EXPORTS = [
     "kdpt_selftest_scatter", "kdpt_selftest_shade",
     "kdpt_active_pixels", "kdpt_trace_adaptive", "kdpt_read_sample_counts", "kdpt_save_counted",
     "kdpt_selftest_active_list",
+    "kdpt_group_create", "kdpt_group_render_frames", "kdpt_group_synchronize", "kdpt_group_context",
+    "kdpt_group_active_pixels", "kdpt_group_trace_adaptive", "kdpt_group_set_camera", "kdpt_group_set_options",
+    "kdpt_group_reset", "kdpt_group_destroy",
 ]
 
 REDUCE_RCCL, REDUCE_COPY = 0, 1  # kdpt_render_sharded's reduce (KDPT_REDUCE_*)
+GROUP_MOMENTS = 1  # kdpt_group_create flag (KDPT_GROUP_MOMENTS)
 
 
 def set_process_tuning(name: str, value: float):
@@ -276,6 +280,18 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.kdpt_read_sample_counts.argtypes = [C.c_void_p, P(C.c_int)]
         lib.kdpt_save_counted.argtypes = [C.c_void_p, P(C.c_uint8), P(C.c_float)]
         lib.kdpt_selftest_active_list.argtypes = [P(C.c_float), C.c_int, C.c_float, P(C.c_int), P(C.c_int)]
+    if hasattr(lib, "kdpt_group_create"):  # absent from older builds used in A/B runs
+        lib.kdpt_group_create.argtypes = [P(Scene), P(Options), C.c_int, P(C.c_int), C.c_int, C.c_int, P(C.c_void_p)]
+        lib.kdpt_group_render_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        lib.kdpt_group_synchronize.argtypes = [C.c_void_p]
+        lib.kdpt_group_context.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p)]
+        lib.kdpt_group_active_pixels.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_void_p, P(C.c_longlong)]
+        lib.kdpt_group_trace_adaptive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                                  C.c_float, P(Adaptive)]
+        lib.kdpt_group_set_camera.argtypes = [C.c_void_p, P(Camera)]
+        lib.kdpt_group_set_options.argtypes = [C.c_void_p, P(Options)]
+        lib.kdpt_group_reset.argtypes = [C.c_void_p]
+        lib.kdpt_group_destroy.argtypes = [C.c_void_p]
     _lib = lib
     return lib
 
@@ -809,10 +825,114 @@ class PathTracer:
             prof["chord_rays"] = [int(out[k]) for k in range(k0 + 136, k0 + 144)]
         return prof
 
+    _owner = None  # a view of a context someone else owns (RenderGroup.context): the owner, kept alive
+
+    @classmethod
+    def borrowed(cls, owner, scene: SceneData, options: Options, handle: C.c_void_p) -> "PathTracer":
+        """A PathTracer over a context that `owner` owns: close() lets go of the handle and destroys nothing."""
+        self = cls.__new__(cls)
+        self.scene, self.lib, self.opt, self._ctx, self._owner = scene, load_library(), options, handle, owner
+        self.width, self.height = scene.resolution
+        return self
+
     def close(self):
-        if self._ctx:
+        if self._ctx and self._owner is None:
             self.lib.kdpt_destroy(self._ctx)
-            self._ctx = C.c_void_p()
+        self._ctx = C.c_void_p()
+        self._owner = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RenderGroup:
+    """kdpt_group: one process, one context per device, kept alive between calls -- frames sharded over the ranks,
+    with moments=True second moments through the reduce, the noise estimate on rank 0 and adaptive rounds across
+    the ranks.  A context manager; close() destroys the group and every context."""
+
+    def __init__(self, scene: SceneData, devices, options: Optional[Options] = None, reduce: int = REDUCE_RCCL,
+                 moments: bool = False):
+        self.scene = scene
+        self.lib = load_library()
+        self.opt = options if options is not None else default_options()
+        self.devices = [int(d) for d in devices]
+        self.reduce = int(reduce)
+        self.moments = bool(moments)
+        self.width, self.height = scene.resolution
+        self._g = C.c_void_p()
+        devs = (C.c_int * len(self.devices))(*self.devices)
+        _check(self.lib.kdpt_group_create(C.byref(scene.view), C.byref(self.opt), len(self.devices), devs,
+                                          self.reduce, GROUP_MOMENTS if self.moments else 0, C.byref(self._g)),
+               "kdpt_group_create")
+
+    def render_frames(self, first_frame: int, frames: int, spp: int, pipeline: int = 8, batch: int = 8, out=None):
+        """kdpt_group_render_frames (async): out is None, a device pointer (int) or a float32 numpy array of
+        frames * 3*W*H values, complete at synchronize()."""
+        ptr = None if out is None else (int(out) if isinstance(out, int) else out.ctypes.data)
+        _check(self.lib.kdpt_group_render_frames(self._g, int(first_frame), int(frames), int(spp), int(pipeline),
+                                                 int(batch), ptr), "kdpt_group_render_frames")
+
+    def render(self, first_frame: int, frames: int, spp: int, pipeline: int = 8, batch: int = 8) -> np.ndarray:
+        """render_frames + synchronize: the reduced frames, (frames, H, W, 3) float32."""
+        out = np.zeros((frames, self.height, self.width, 3), dtype=np.float32)
+        self.render_frames(first_frame, frames, spp, pipeline, batch, out)
+        self.synchronize()
+        return out
+
+    def synchronize(self):
+        _check(self.lib.kdpt_group_synchronize(self._g), "kdpt_group_synchronize")
+
+    def context(self, rank: int = 0) -> PathTracer:
+        """kdpt_group_context: rank's context as a PathTracer that does not own it, for reads and queries (image,
+        moments, noise_map, noise_estimate, sample_counts, save_*, stats, cast_rays, trace_rays, camera_rays)."""
+        h = C.c_void_p()
+        _check(self.lib.kdpt_group_context(self._g, int(rank), C.byref(h)), "kdpt_group_context")
+        return PathTracer.borrowed(self, self.scene, self.opt, h)
+
+    def active_pixels(self, floor: float = 1e-2, threshold: float = 0.0) -> np.ndarray:
+        """kdpt_group_active_pixels: the list the next trace_adaptive would trace (int32, ascending)."""
+        n = C.c_longlong()
+        out = np.empty(self.height * self.width, dtype=np.int32)
+        _check(self.lib.kdpt_group_active_pixels(self._g, float(floor), float(threshold),
+                                                 C.c_void_p(out.ctypes.data), C.byref(n)),
+               "kdpt_group_active_pixels")
+        return out[:int(n.value)].copy()
+
+    def trace_adaptive(self, first_iter: int, count: int, pipeline: int = 8, batch: int = 16, floor: float = 1e-2,
+                       threshold: float = 0.0) -> Adaptive:
+        """kdpt_group_trace_adaptive: iterations first_iter .. first_iter + count - 1 over the active pixels, dealt
+        to the ranks in turn and added on rank 0.  Synchronous; returns the call's kdpt_adaptive record."""
+        r = Adaptive()
+        _check(self.lib.kdpt_group_trace_adaptive(self._g, int(first_iter), int(count), int(pipeline), int(batch),
+                                                  float(floor), float(threshold), C.byref(r)),
+               "kdpt_group_trace_adaptive")
+        return r
+
+    def set_camera(self, camera):
+        """kdpt_group_set_camera: every rank's camera (a Camera, or a SceneData whose camera is taken)."""
+        cam = camera.view.camera if isinstance(camera, SceneData) else camera
+        _check(self.lib.kdpt_group_set_camera(self._g, C.byref(cam)), "kdpt_group_set_camera")
+
+    def set_options(self, options: Options):
+        _check(self.lib.kdpt_group_set_options(self._g, C.byref(options)), "kdpt_group_set_options")
+        self.opt = options
+
+    def reset(self):
+        _check(self.lib.kdpt_group_reset(self._g), "kdpt_group_reset")
+
+    def close(self):
+        if self._g:
+            self.lib.kdpt_group_destroy(self._g)
+            self._g = C.c_void_p()
 
     def __enter__(self):
         return self
