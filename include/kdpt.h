@@ -558,6 +558,85 @@ int kdpt_read_sample_counts(kdpt_ctx *ctx, int *counts);
 int kdpt_save_counted(kdpt_ctx *ctx, uint8_t *rgb, float *lin);
 int kdpt_selftest_active_list(const float *noise, int npix, float threshold, int *pixels, int *n);
 
+/* ---- Denoising: a variance-guided edge-avoiding a-trous filter ----
+ * The other use of the per-pixel variance: a cleaner image from the samples already spent.  The filter is the
+ * spatial core of SVGF (Schied et al. 2017: the variance of each pixel steers its luminance tolerance, and is
+ * filtered along) on the a-trous wavelet of Dammertz et al. 2010, without the temporal part.  Like the other
+ * contracts here it is a bit pattern: float32 add, subtract, multiply, divide, sqrt, compare and abs only, every
+ * operation rounded on its own (no fused multiply-add), denormals kept, no transcendental -- which is why the
+ * edge-stopping function is the rational g below and not exp -- so a numpy float32 restatement gives the same bits.
+ *
+ * Inputs for a W x H image, pixel p = y*W + x: color[p][3], variance[p] (the variance of the pixel's mean),
+ * normal[p][3], point[p][3], depth[p], id[p].  Pixel p is valid iff its 11 floats are finite, depth[p] > 0 and
+ * variance[p] >= 0; validity is decided once, from the inputs, and holds for every pass.  An invalid pixel is never
+ * a tap, and its own colour and variance pass through every pass unchanged, bit for bit.
+ *
+ * kdpt_denoise_params (kdpt_default_denoise_params fills the defaults): passes 0 .. 8 (5); normal_power_log2
+ * 0 .. 10 (7: cos^128); sigma_l > 0 (4), sigma_z > 0 (0.02), eps_l > 0 (1e-8), all finite.  passes = 0 copies the
+ * inputs to the outputs.
+ *
+ * Pass k = 0 .. passes-1, step s = 1 << k, reads pass k-1's colour and variance (the inputs for k = 0) and, for
+ * every valid pixel p = (x, y):
+ *   prefilter: g3 = [1/4, 1/2, 1/4]; for dy = -1..1 (outer), dx = -1..1 (inner), always at step 1, over the taps q
+ *     inside the image and valid: sg = sg + g3[dy+1] g3[dx+1];  sv = sv + (g3[dy+1] g3[dx+1]) variance[q];
+ *     sd = sqrt(sv / sg)
+ *   lum(c) = ((c.r + c.g) + c.b) / 3;  den_l = sigma_l sd + eps_l;  den_z = sigma_z depth[p];
+ *   g(x) = 1 / (1 + x (1 + 0.5 x))
+ *   taps: h = [1/16, 1/4, 3/8, 1/4, 1/16]; for dy = -2..2 (outer), dx = -2..2 (inner), q = (x + s dx, y + s dy), the
+ *     centre included and treated like any other; q is skipped when outside the image, invalid or id[q] != id[p]:
+ *       dn = (n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z, clamped to [0, 1] (dn < 0 -> 0, then dn > 1 -> 1: a NaN
+ *            stays), then squared normal_power_log2 times
+ *       e = point[q] - point[p];  xz = |(n_p.x e.x + n_p.y e.y) + n_p.z e.z| / den_z
+ *       xl = |lum(color[p]) - lum(color[q])| / den_l
+ *       w = ((h[dy+2] h[dx+2]) dn) g(xz) g(xl), multiplied left to right
+ *     a tap whose w is not > 0 is skipped (a NaN from an overflowed luminance or an underflowed denominator
+ *     included); otherwise sw = sw + w;  sc[c] = sc[c] + w color[q][c];  sv2 = sv2 + (w w) variance[q]
+ *   output: sw > 0: color'[p] = sc / sw, variance'[p] = sv2 / (sw sw); otherwise p passes through.
+ * Out-of-image and invalid taps are skipped, never clamped.  g agrees with exp(-x) to second order at 0 and has a
+ * heavier tail.
+ *
+ * kdpt_denoise_buffers is the filter alone on caller data on `device`: host arrays (3*w*h floats for color, normal,
+ * point; w*h for variance, depth, id), w, h >= 1, w*h <= 2^26; out_color (3*w*h floats) and out_variance (w*h
+ * floats, may be NULL) are host memory and must not alias the inputs.  Argument errors (a null pointer, w or h < 1,
+ * w*h > 2^26, params out of range) are KDPT_ERR_ARG, reported before any device call.  It is what denoises data
+ * that is not the context's image, a kdpt_trace_rays_moments bake for instance.
+ *
+ * kdpt_denoise is the same filter on the context's own render, defined as a composition:
+ *   colour:   n_p = samples + extra[p] (samples while extra is absent);  color[p][c] = fdiv(image[p][c], (float)n_p)
+ *   variance: v_c and vbar exactly as kdpt_noise_map spells them with n = n_p, in double, in that order;
+ *             variance[p] = (float)(vbar / n).  This is the channel-mean variance beside the channel-mean
+ *             luminance: a proxy for the variance of the luminance itself (an upper bound of it when the channels
+ *             move together), not that variance.
+ *   guides:   the camera's pinhole ray through every pixel -- from the eye, direction
+ *             normalize(view - right pixelLength.x (x - W/2) - up pixelLength.y (y - H/2)), generateRayFromCamera's
+ *             first part in its operation order, without jitter or lens whatever the context's options say (they are
+ *             left alone) -- and for each ray the record kdpt_cast_rays(flags = 0) returns: normal, point,
+ *             depth = t, id = material; depth = -1 where kind <= 0, so that pixel is invalid and passes through.
+ *             (These are not the rays kdpt_camera_rays returns with antialias = 0 and dof_angle = 0: its lens
+ *             arithmetic, (eye + d f) - d f and a second normalize, moves the last bit of some of them.)
+ *             First-hit guides describe the surface, not what is seen in it: mirrors and glass are filtered as the
+ *             surface they are.
+ * Synchronous: waits for the work queued on the context (the pipelined adds included), runs on its stream, and
+ * writes out_color (3*W*H floats) and out_variance (W*H floats, may be NULL), each host memory or memory of the
+ * context's device, told apart as kdpt_write_pbo does.  It leaves the image, sumsq, samples, extra, kdpt_stats, the
+ * pipeline slots, kdpt_cast_rays' buffers and counters and kdpt_trace_rays' state as they were.  Its buffers are
+ * made on first use, owned by the context, freed by kdpt_destroy and remade after kdpt_set_tuning; the guides are
+ * rebuilt on every call (no cache to invalidate).  Errors, reported before any device work: KDPT_ERR_ARG for a null
+ * ctx, params or out_color, params out of range, or fewer than 2 uniform iterations accumulated;
+ * KDPT_ERR_UNSUPPORTED while moments are off, and for contexts with enable_kd = 0 or viz_kd = 1 (kdpt_cast_rays'
+ * own refusal).  kdpt_denoise_stats reports the last call's device times (hipEvents on the context's stream): the
+ * guides (rays, traversal, hit records) and the filter (packing, the passes, the copy out). */
+typedef struct kdpt_denoise_params {  /* 24 bytes */
+    int passes, normal_power_log2;
+    float sigma_l, sigma_z, eps_l, pad_;
+} kdpt_denoise_params;
+void kdpt_default_denoise_params(kdpt_denoise_params *p);
+int kdpt_denoise_buffers(int device, int w, int h, const float *color, const float *variance, const float *normal,
+                         const float *point, const float *depth, const int *id, const kdpt_denoise_params *p,
+                         float *out_color, float *out_variance /* may be NULL */);
+int kdpt_denoise(kdpt_ctx *ctx, const kdpt_denoise_params *p, float *out_color, float *out_variance /* may be NULL */);
+int kdpt_denoise_stats(kdpt_ctx *ctx, double *guide_ms, double *filter_ms);
+
 /* ---- A persistent group: the in-process sharded renderer as an object ----
  * kdpt_render_sharded's contexts kept alive: one context per device in this process, created once (scene upload
  * and mask tables once per rank), rendering frames call after call, and, with KDPT_GROUP_MOMENTS, carrying second
@@ -603,7 +682,8 @@ int kdpt_selftest_active_list(const float *noise, int npix, float threshold, int
  * kdpt_group_context lends rank `rank`'s context (borrowed: the group still owns it) for calls that leave the
  * render state alone: kdpt_read_image, kdpt_read_moments, kdpt_noise_map, kdpt_noise_estimate,
  * kdpt_read_sample_counts, kdpt_save_*, kdpt_get_stats, kdpt_cast_rays, kdpt_trace_rays[_moments],
- * kdpt_camera_rays.  They see the frames queued so far (rank 0's reads follow the group's last image add without
+ * kdpt_camera_rays, kdpt_denoise (rank 0 of a KDPT_GROUP_MOMENTS group: the sharded render denoised).  They see the
+ * frames queued so far (rank 0's reads follow the group's last image add without
  * a kdpt_group_synchronize; fault words are checked only there).  A borrowed context must not receive
  * kdpt_destroy, nor a call that changes its state: kdpt_trace_iteration[s][_async], kdpt_render_frames,
  * kdpt_trace_adaptive, kdpt_active_pixels, kdpt_reset, kdpt_set_moments, kdpt_set_options, kdpt_set_camera,

@@ -34,6 +34,11 @@ iterations, the rest of --iterations in shorter frames that keep the iteration n
 0's estimate after every frame, --adaptive switches to kdpt_group_trace_adaptive rounds after --min-spp, and the
 output comes from rank 0's context through the same save paths; the JSON gains "devices" and "frames".  Without
 --devices nothing changes.
+
+--denoise [PASSES] also writes BASE.denoised.png (BASE.denoised.hdr with --hdr): the per-pixel means through
+kdpt_denoise's variance-guided edge-avoiding filter (PASSES a-trous passes, default 5), then saveImage's pixel pass
+with samples = 1 (save_pixels).  It keeps second moments while rendering, as --target-noise does, works with --adaptive
+(the per-pixel counts are inside the means) and --devices (rank 0's context), and needs at least 2 iterations.
 """
 from __future__ import annotations
 
@@ -122,7 +127,16 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--reduce", choices=["rccl", "copy"], default="rccl",
                     help="with --devices: the frames' cross-rank reduce (copy: peer copies to the first device, which "
                          "also lets a device repeat)")
+    ap.add_argument("--denoise", type=int, nargs="?", const=5, default=None, metavar="PASSES",
+                    help="also write BASE.denoised.png (and BASE.denoised.hdr with --hdr): the per-pixel means through "
+                         "the variance-guided edge-avoiding filter (kdpt_denoise), PASSES a-trous passes (0 .. 8, "
+                         "default 5); keeps second moments while rendering and needs at least 2 iterations")
     a = ap.parse_args(argv)
+    if a.denoise is not None:
+        if not 0 <= a.denoise <= 8:
+            ap.error("--denoise: PASSES must be in 0 .. 8")
+        if a.brute or a.viz_kd:
+            ap.error("--denoise takes its guides from the KD traversal; it cannot be combined with --brute or --viz-kd")
     if a.devices is not None:
         if a.testing:
             ap.error("--devices renders in pipelined frames; it cannot be combined with --testing")
@@ -256,6 +270,33 @@ def render_group(grp, a: argparse.Namespace, limit: int):
     return done, est, totals, frames
 
 
+def save_pixels(mean):
+    """saveImage's pixel pass (src/main.cpp:1087-1108, image::savePNG) on an (H, W, 3) float32 image of per-pixel
+    means, samples = 1: (rgb, lin) -- lin the image flipped in x (what image::saveHDR writes), rgb its bytes,
+    clamp(v, 0, 1) * 255.f in float32 truncated to uint8 (a NaN gives 0)."""
+    import numpy as np
+    lin = np.ascontiguousarray(np.asarray(mean, np.float32)[:, ::-1, :])
+    with np.errstate(invalid="ignore"):
+        cl = np.where(lin < 0, np.float32(0), lin)
+        cl = np.where(cl > 1, np.float32(1), cl) * np.float32(255)
+    return np.nan_to_num(cl, nan=0.0).astype(np.uint8), lin
+
+
+def write_denoised(pt, a: argparse.Namespace, base: str):
+    """--denoise: BASE.denoised.png / BASE.denoised.hdr from kdpt_denoise's means (the context's per-pixel sample
+    counts are inside them): the files written."""
+    from .runtime import default_denoise_params, hdr_encode, png_encode
+    rgb, lin = save_pixels(pt.denoise(default_denoise_params(passes=a.denoise)))
+    written = []
+    for ext, on, encode, pixels in ((".denoised.png", not a.no_png, png_encode, rgb),
+                                    (".denoised.hdr", a.hdr, hdr_encode, lin)):
+        if on:
+            with open(base + ext, "wb") as f:
+                f.write(encode(pixels))
+            written.append(base + ext)
+    return written
+
+
 def write_outputs(pt, a: argparse.Namespace, base: str, spp: int, counted: bool):
     """The PNG / HDR / noise map of a context's image: the files written.  counted: every pixel divided by its own
     sample count (after adaptive rounds), then the same host encoders."""
@@ -279,13 +320,15 @@ def write_outputs(pt, a: argparse.Namespace, base: str, spp: int, counted: bool)
         import numpy as np
         np.save(base + ".noise.npy", pt.noise_map(a.noise_floor))
         written.append(base + ".noise.npy")
+    if a.denoise is not None:
+        written += write_denoised(pt, a, base)
     return written
 
 
 def main_group(a: argparse.Namespace, sd, hdr: dict, iterations: int, info: dict) -> int:
     """main() with --devices: the render through a RenderGroup, the output from rank 0's context."""
     from .runtime import REDUCE_COPY, REDUCE_RCCL, RenderGroup
-    moments = a.target_noise is not None
+    moments = a.target_noise is not None or a.denoise is not None
     with RenderGroup(sd, a.devices, options_from_args(a), reduce=REDUCE_COPY if a.reduce == "copy" else REDUCE_RCCL,
                      moments=moments) as grp:
         t0 = time.perf_counter()
@@ -332,6 +375,9 @@ def main(argv=None) -> int:
         print(json.dumps(info), flush=True)
         sd.close()
         return 0
+    if a.denoise is not None and iterations < 2:
+        raise SystemExit("--denoise needs at least 2 iterations: the filter is guided by the per-pixel variance, "
+                         f"and {iterations} iteration gives none (raise --iterations)")
     if a.devices is not None:
         return main_group(a, sd, hdr, iterations, info)
     opt = options_from_args(a)
@@ -339,6 +385,8 @@ def main(argv=None) -> int:
     with PathTracer(sd, opt, device=a.device) as pt:
         t0 = time.perf_counter()
         adaptive = None  # --adaptive: the adaptive rounds' totals
+        if a.denoise is not None:  # the filter's variance: second moments from the first iteration on
+            pt.set_moments(True)
         if a.adaptive:
             spp, est, adaptive = render_adaptive(pt, a, iterations)
         elif a.target_noise is not None:
@@ -373,6 +421,8 @@ def main(argv=None) -> int:
             import numpy as np
             np.save(base + ".noise.npy", pt.noise_map(a.noise_floor))
             written.append(base + ".noise.npy")
+        if a.denoise is not None:
+            written += write_denoised(pt, a, base)
     segments = int(st.total_segments) + (adaptive["segments"] if adaptive is not None else 0)
     info.update({"segments": segments, "seconds": round(dt, 4),
                  "mrays_per_s": round(segments / dt / 1e6, 2) if dt > 0 else None,

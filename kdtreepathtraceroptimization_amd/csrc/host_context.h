@@ -210,6 +210,28 @@ struct Moments {
   Adaptive adapt;
 };
 
+// Denoising (kdpt_denoise): the filter's records and the guide pass's working set -- the pinhole rays, a ray query's
+// queue, hit records and counters (CastArgs' layout, one chunk of W*H rays) and its results -- made on first use
+// (denoise_buffers) and dropped by kdpt_set_tuning; nothing here is shared with the render path, kdpt_cast_rays or
+// kdpt_trace_rays.  `b = {}` drops the buffers.
+struct Denoiser {
+  struct Buffers {
+    int npix = 0;                      // the pixel count the buffers were made for (0: none)
+    DeviceBuf<float4> g0, g1;          // [npix] {normal, depth}, {point, id}
+    DeviceBuf<float4> cv[2];           // [npix] {colour, variance}, ping-pong
+    DeviceBuf<float> rays;             // [6 npix] origins, then directions
+    DeviceBuf<kdpt_ray_hit> hits_out;  // [npix]
+    DeviceBuf<float4> cray;            // [2 npix]
+    DeviceBuf<int> cand;               // [npix]
+    DeviceBuf<int2> hits;              // [npix]
+    DeviceBuf<int> cnt;                // [2]
+    DeviceBuf<unsigned long long> tt;  // [3]
+    DeviceBuf<float> out_stage;        // [4 npix] colour, then variance, on their way to host memory
+  } b;
+  Event ev[3];                         // before the guides, between guides and filter, after the filter
+  double guide_ms = 0, filter_ms = 0;  // the last call's (kdpt_denoise_stats)
+};
+
 struct kdpt_ctx {
   int device = 0;
   Stream stream;  // (declared before every other resource: destroyed last)
@@ -265,6 +287,7 @@ struct kdpt_ctx {
   CastQuery cast;
   RayQuery query;
   Moments mom;
+  Denoiser den;
   // an iteration (or a frame) has been added into the image since create / kdpt_reset: with stats.iterations what
   // kdpt_set_moments(1) refuses on (kdpt_trace_iteration_async counts no iteration)
   bool accumulated = false;

@@ -61,6 +61,7 @@ using namespace kdpt;
 #include "kernels_masks.h"
 #include "kernels_frames.h"
 #include "kernels_adaptive.h"
+#include "kernels_denoise.h"
 #include "kernels_moments.h"
 
 // The host code, one section per feature; a section uses what the sections before it define.
@@ -73,5 +74,6 @@ using namespace kdpt;
 #include "host_frames.h"
 #include "host_queries.h"
 #include "host_moments.h"
+#include "host_denoise.h"
 #include "host_group.h"
 #include "host_selftest.h"

@@ -136,7 +136,17 @@ class Adaptive(C.Structure):  # kdpt_adaptive: kdpt_trace_adaptive's result
                 ("segments", C.c_longlong), ("traced", C.c_longlong), ("device_ms", C.c_double)]
 
 
-assert C.sizeof(Noise) == 48 and C.sizeof(Adaptive) == 48
+class DenoiseParams(C.Structure):  # kdpt_denoise_params: the filter's knobs (kdpt_default_denoise_params)
+    _fields_ = [("passes", C.c_int), ("normal_power_log2", C.c_int), ("sigma_l", C.c_float), ("sigma_z", C.c_float),
+                ("eps_l", C.c_float), ("pad_", C.c_float)]
+
+
+class DenoiseStats(NamedTuple):  # kdpt_denoise_stats: of the last kdpt_denoise
+    guide_ms: float   # the pinhole rays, their traversal and hit records
+    filter_ms: float  # packing, the passes and the copy out
+
+
+assert C.sizeof(Noise) == 48 and C.sizeof(Adaptive) == 48 and C.sizeof(DenoiseParams) == 24
 assert C.sizeof(Geom) == 236 and C.sizeof(Material) == 56 and C.sizeof(Camera) == 84
 assert C.sizeof(NodeBare) == 64 and C.sizeof(TriBare) == 76 and C.sizeof(PathSegment) == 56
 
@@ -158,6 +168,7 @@ EXPORTS = [
     "kdpt_group_create", "kdpt_group_render_frames", "kdpt_group_synchronize", "kdpt_group_context",
     "kdpt_group_active_pixels", "kdpt_group_trace_adaptive", "kdpt_group_set_camera", "kdpt_group_set_options",
     "kdpt_group_reset", "kdpt_group_destroy",
+    "kdpt_default_denoise_params", "kdpt_denoise_buffers", "kdpt_denoise", "kdpt_denoise_stats",
 ]
 
 REDUCE_RCCL, REDUCE_COPY = 0, 1  # kdpt_render_sharded's reduce (KDPT_REDUCE_*)
@@ -292,6 +303,14 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         lib.kdpt_group_set_options.argtypes = [C.c_void_p, P(Options)]
         lib.kdpt_group_reset.argtypes = [C.c_void_p]
         lib.kdpt_group_destroy.argtypes = [C.c_void_p]
+    if hasattr(lib, "kdpt_denoise"):  # absent from older builds used in A/B runs
+        lib.kdpt_default_denoise_params.argtypes = [P(DenoiseParams)]
+        lib.kdpt_default_denoise_params.restype = None
+        lib.kdpt_denoise_buffers.argtypes = [C.c_int, C.c_int, C.c_int, P(C.c_float), P(C.c_float), P(C.c_float),
+                                             P(C.c_float), P(C.c_float), P(C.c_int), P(DenoiseParams), P(C.c_float),
+                                             P(C.c_float)]
+        lib.kdpt_denoise.argtypes = [C.c_void_p, P(DenoiseParams), C.c_void_p, C.c_void_p]
+        lib.kdpt_denoise_stats.argtypes = [C.c_void_p, P(C.c_double), P(C.c_double)]
     _lib = lib
     return lib
 
@@ -484,6 +503,41 @@ def default_options(**overrides) -> Options:
             raise KeyError(k)
         setattr(o, k, v)
     return o
+
+
+def default_denoise_params(**overrides) -> DenoiseParams:
+    """kdpt_default_denoise_params: 5 passes, cos^128 normals, sigma_l 4, sigma_z 0.02, eps_l 1e-8."""
+    p = DenoiseParams()
+    load_library().kdpt_default_denoise_params(C.byref(p))
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def denoise_buffers(color, variance, normal, point, depth, ids, params: Optional[DenoiseParams] = None,
+                    device: int = 0, return_variance: bool = False):
+    """kdpt_denoise_buffers: the filter alone on caller data -- color, normal, point (H, W, 3) float32, variance and
+    depth (H, W) float32, ids (H, W) int32 -- on `device`.  Returns the filtered colour (H, W, 3), or (colour,
+    variance) with return_variance."""
+    col = np.ascontiguousarray(color, dtype=np.float32)
+    if col.ndim != 3 or col.shape[2] != 3:
+        raise ValueError(f"color: expected (H, W, 3), got {col.shape}")
+    h, w = col.shape[:2]
+    var, dep = (np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in (variance, depth))
+    nrm, pnt = (np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in (normal, point))
+    idv = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+    for name, a, n in (("variance", var, 1), ("depth", dep, 1), ("ids", idv, 1), ("normal", nrm, 3), ("point", pnt, 3)):
+        if a.size != n * w * h:
+            raise ValueError(f"{name}: {a.size} values for a {w} x {h} image")
+    p = params if params is not None else default_denoise_params()
+    out = np.empty((h, w, 3), dtype=np.float32)
+    ov = np.empty((h, w), dtype=np.float32) if return_variance else None
+    _check(load_library().kdpt_denoise_buffers(int(device), w, h, _fptr(col), _fptr(var), _fptr(nrm), _fptr(pnt),
+                                               _fptr(dep), _iptr(idv), C.byref(p), _fptr(out),
+                                               _fptr(ov) if return_variance else None), "kdpt_denoise_buffers")
+    return (out, ov) if return_variance else out
 
 
 class PathTracer:
@@ -701,6 +755,30 @@ class PathTracer:
                                           _fptr(flt) if lin else None), "kdpt_save_counted")
         return (rgb, flt) if lin else rgb
 
+    def denoise(self, params: Optional[DenoiseParams] = None, variance: bool = False):
+        """kdpt_denoise: the render's per-pixel means through the variance-guided edge-avoiding filter (include/kdpt.h
+        "Denoising"), (H, W, 3) float32; variance=True returns (colour, variance), the latter (H, W) float32: the
+        filtered variance of the means.  Needs moments and at least 2 iterations; leaves the render state alone."""
+        p = params if params is not None else default_denoise_params()
+        col = np.empty((self.height, self.width, 3), dtype=np.float32)
+        var = np.empty((self.height, self.width), dtype=np.float32) if variance else None
+        _check(self.lib.kdpt_denoise(self._ctx, C.byref(p), C.c_void_p(col.ctypes.data),
+                                     C.c_void_p(var.ctypes.data) if variance else None), "kdpt_denoise")
+        return (col, var) if variance else col
+
+    def denoise_ptr(self, params: Optional[DenoiseParams], color_ptr: int, variance_ptr: Optional[int] = None):
+        """kdpt_denoise into raw pointers (host memory or the context's device): 3*W*H floats, and W*H floats."""
+        p = params if params is not None else default_denoise_params()
+        _check(self.lib.kdpt_denoise(self._ctx, C.byref(p), C.c_void_p(int(color_ptr)),
+                                     C.c_void_p(int(variance_ptr)) if variance_ptr is not None else None),
+               "kdpt_denoise")
+
+    def denoise_stats(self) -> "DenoiseStats":
+        """kdpt_denoise_stats: the last denoise's device times in ms (guides, filter)."""
+        g, f = C.c_double(), C.c_double()
+        _check(self.lib.kdpt_denoise_stats(self._ctx, C.byref(g), C.byref(f)), "kdpt_denoise_stats")
+        return DenoiseStats(g.value, f.value)
+
     def trace_rays_ptr(self, origins_ptr: int, directions_ptr: int, n: int, radiance_ptr: int, first_iter: int = 1,
                        count: int = 1, normalize: bool = True):
         """kdpt_trace_rays on raw pointers, each host memory or memory of the context's device (e.g. a torch
@@ -893,7 +971,8 @@ class RenderGroup:
 
     def context(self, rank: int = 0) -> PathTracer:
         """kdpt_group_context: rank's context as a PathTracer that does not own it, for reads and queries (image,
-        moments, noise_map, noise_estimate, sample_counts, save_*, stats, cast_rays, trace_rays, camera_rays)."""
+        moments, noise_map, noise_estimate, sample_counts, save_*, stats, cast_rays, trace_rays, camera_rays, and
+        denoise on rank 0 of a group with moments)."""
         h = C.c_void_p()
         _check(self.lib.kdpt_group_context(self._g, int(rank), C.byref(h)), "kdpt_group_context")
         return PathTracer.borrowed(self, self.scene, self.opt, h)
