@@ -637,6 +637,92 @@ int kdpt_denoise_buffers(int device, int w, int h, const float *color, const flo
 int kdpt_denoise(kdpt_ctx *ctx, const kdpt_denoise_params *p, float *out_color, float *out_variance /* may be NULL */);
 int kdpt_denoise_stats(kdpt_ctx *ctx, double *guide_ms, double *filter_ms);
 
+/* ---- Temporal accumulation: the denoiser's history, reprojected across views ----
+ * SVGF's other half (Schied et al. 2017), for a camera that moves through a static scene: kdpt_set_camera, kdpt_reset,
+ * a few iterations, and kdpt_denoise_temporal in place of kdpt_denoise.  The frame's colour and variance are blended
+ * with the previous call's before the spatial filter sees them.  The scene does not move, so the world-space point of
+ * every first hit -- already in the denoiser's guides -- is its own motion vector: a pixel projects its hit point
+ * through the previous camera and accepts a history tap only when the tap lies on the same surface in world space.
+ * The projection only proposes taps, the world-space tests accept them: a camera that is not orthonormal, or rounding
+ * in fx, can cost history but never mix surfaces.
+ * Like "Denoising" the contract is a bit pattern: float32 add, subtract, multiply, divide, compare, abs, floorf and
+ * float -> int conversion only, every operation rounded on its own (no fused multiply-add), denormals kept, so a
+ * numpy float32 restatement gives the same bits.
+ *
+ * Current frame, W x H, pixel p = y*W + x: color C[p][3], variance V[p] (of the pixel's mean), normal n_p, point X_p,
+ * depth_p, id_p; p is valid by "Denoising"'s rule (its 11 floats finite, depth > 0, variance >= 0).
+ * History (absent, or the previous call's): the same six quantities and a length L[q] (float, >= 0: how many frames
+ * the pixel has accumulated), and the camera cam' they were made under.  A history pixel q is usable iff
+ * depth[q] > 0 and L[q] > 0 (nothing else is asked of it: its colour and variance enter as they are).
+ *
+ * kdpt_temporal_params (kdpt_default_temporal_params fills the defaults, chosen by eye): alpha in (0, 1] (0.2);
+ * sigma_z > 0 (0.02); normal_min in [-1, 1] (0.9); max_history 1 .. 4096 (32); the floats finite.
+ *
+ * An invalid pixel passes through, C' = C, V' = V, and stores L' = 0.  A valid pixel p, in this order:
+ *   projection: e = X_p - cam'.position;  z = (e.x v.x + e.y v.y) + e.z v.z with v = cam'.view;  a and b the same
+ *     dot product with cam'.right and cam'.up.  No history if !(z > 0).
+ *     fx = W 0.5f - (a / z) / pixelLength.x;  fy = H 0.5f - (b / z) / pixelLength.y  (the inverse of the guides'
+ *     pinhole direction: pixel x is the centre of its own ray, no half-pixel offset).
+ *     No history if !(fx > -1 && fx < W && fy > -1 && fy < H).
+ *     ix = (int)floorf(fx), tx = fx - floorf(fx);  iy, ty likewise.
+ *   taps: q = (ix, iy), (ix+1, iy), (ix, iy+1), (ix+1, iy+1) in that order, w = wx wy with wx = 1 - tx or tx and
+ *     wy = 1 - ty or ty.  A tap is skipped when it is outside the image, when q is not usable, when id[q] != id_p,
+ *     when !((n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z >= normal_min), when, with d = X_q - X_p,
+ *     !(|(n_p.x d.x + n_p.y d.y) + n_p.z d.z| / (sigma_z depth_p) <= 1), or when !(w > 0); a NaN anywhere in these
+ *     therefore rejects the tap.  Otherwise sw = sw + w;  sc[c] = sc[c] + w C_h[q][c];  sv = sv + w V_h[q];
+ *     sl = sl + w L[q].
+ *   blend: !(sw > 0): no history, C' = C, V' = V, L' = 1, bit for bit.  Otherwise h = sc / sw, vh = sv / sw,
+ *     lh = sl / sw;  l = lh + 1;  L' = l < (float)max_history ? l : (float)max_history;  r = 1 / L';
+ *     A = r > alpha ? r : alpha;  B = 1 - A;
+ *     C'[c] = fadd(fmul(B, h[c]), fmul(A, C[c]));  V' = fadd(fmul(fmul(B, B), vh), fmul(fmul(A, A), V)).
+ * The blend is a weighted sum of independent frame means, so its variance is the squared-weight sum: the stage
+ * carries the variance itself, not luminance moments.  V_h is resampled with weight w, not w^2 (the variance of the
+ * interpolated history would be smaller): deliberately conservative.
+ *
+ * kdpt_temporal_buffers is the stage alone on caller data on `device`, with kdpt_denoise_buffers' conventions: host
+ * arrays (3*w*h floats for color, normal, point; w*h for variance, depth, id, length), w, h >= 1, w*h <= 2^26;
+ * out_color (3*w*h floats), out_variance and out_length (w*h floats each) are host memory, all required, and must
+ * not alias the inputs.  The eight history arguments (seven arrays and h_camera) are all NULL -- no history -- or all
+ * given; h_camera->resolution must be (w, h).  Argument errors (a null pointer, a history given in part, w or h < 1,
+ * w*h > 2^26, params out of range or not finite, a resolution mismatch) are KDPT_ERR_ARG, reported before any device
+ * call.
+ *
+ * kdpt_denoise_temporal is a composition, with temporal() the stage above and filter() "Denoising"'s passes:
+ *   C, V and the guides G are exactly what kdpt_denoise derives from the context's current state;
+ *   (C', V', L') = temporal(C, V, G; history, history camera);
+ *   history := (C', V', L', G) and the context's current camera;
+ *   output = filter(C', V', G, dp); dp->passes = 0 gives the temporal stage's output itself.
+ * With no history the result is kdpt_denoise's, bit for bit.  Synchronous, on the context's stream, out_color and
+ * out_variance (may be NULL) host memory or memory of the context's device, as kdpt_denoise's; it leaves alone
+ * everything kdpt_denoise leaves alone, and the only state it changes is the history.  The history is owned by the
+ * context, made on first use: two sets of 52 bytes per pixel (three 16-byte records and the length; the frame is
+ * built in one while the other is read, and the two swap roles), 104 bytes per pixel beside kdpt_denoise's buffers.
+ * It survives kdpt_reset, kdpt_set_camera and kdpt_set_options -- a frame of a camera path is "set camera, reset,
+ * trace, denoise" -- and is dropped by kdpt_temporal_reset, by kdpt_set_tuning (with the denoiser's other buffers)
+ * and by kdpt_destroy.  Errors are kdpt_denoise's, plus KDPT_ERR_ARG for a null or out-of-range tp; they are
+ * reported before any device work and leave the history untouched.
+ * kdpt_temporal_stats reports the last call: three device times (hipEvents on the context's stream: the guides; the
+ * packing and the temporal stage; the passes and the copy out) and two counts, the frame's valid pixels and those
+ * of them that found history (sw > 0). */
+typedef struct kdpt_temporal_params {  /* 24 bytes */
+    float alpha, sigma_z, normal_min;
+    int max_history;
+    float pad_[2];
+} kdpt_temporal_params;
+void kdpt_default_temporal_params(kdpt_temporal_params *p);
+int kdpt_temporal_buffers(int device, int w, int h,
+                          const float *color, const float *variance, const float *normal, const float *point,
+                          const float *depth, const int *id,
+                          const float *h_color, const float *h_variance, const float *h_normal, const float *h_point,
+                          const float *h_depth, const int *h_id, const float *h_length,
+                          const kdpt_camera *h_camera, const kdpt_temporal_params *p,
+                          float *out_color, float *out_variance, float *out_length);
+int kdpt_denoise_temporal(kdpt_ctx *ctx, const kdpt_temporal_params *tp, const kdpt_denoise_params *dp,
+                          float *out_color, float *out_variance /* may be NULL */);
+int kdpt_temporal_reset(kdpt_ctx *ctx);
+int kdpt_temporal_stats(kdpt_ctx *ctx, double *guide_ms, double *temporal_ms, double *filter_ms,
+                        long long *valid, long long *with_history);
+
 /* ---- A persistent group: the in-process sharded renderer as an object ----
  * kdpt_render_sharded's contexts kept alive: one context per device in this process, created once (scene upload
  * and mask tables once per rank), rendering frames call after call, and, with KDPT_GROUP_MOMENTS, carrying second
@@ -682,7 +768,8 @@ int kdpt_denoise_stats(kdpt_ctx *ctx, double *guide_ms, double *filter_ms);
  * kdpt_group_context lends rank `rank`'s context (borrowed: the group still owns it) for calls that leave the
  * render state alone: kdpt_read_image, kdpt_read_moments, kdpt_noise_map, kdpt_noise_estimate,
  * kdpt_read_sample_counts, kdpt_save_*, kdpt_get_stats, kdpt_cast_rays, kdpt_trace_rays[_moments],
- * kdpt_camera_rays, kdpt_denoise (rank 0 of a KDPT_GROUP_MOMENTS group: the sharded render denoised).  They see the
+ * kdpt_camera_rays, kdpt_denoise, kdpt_denoise_temporal and kdpt_temporal_reset (rank 0 of a KDPT_GROUP_MOMENTS
+ * group: the sharded render denoised; the history is the only state they change).  They see the
  * frames queued so far (rank 0's reads follow the group's last image add without
  * a kdpt_group_synchronize; fault words are checked only there).  A borrowed context must not receive
  * kdpt_destroy, nor a call that changes its state: kdpt_trace_iteration[s][_async], kdpt_render_frames,

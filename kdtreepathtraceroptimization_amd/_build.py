@@ -36,7 +36,7 @@ KERNEL_SOURCES = ["kdpt_device.h", "kdpt_scene.h", "kdpt_geoms.h", "kdpt_travers
                   "kdpt_math.h", "kdpt_runtime.hip", "glibc_sincostab.h", "kernels_gen.h",
                   "kernels_trace.h", "kernels_brute.h", "kernels_shade.h", "kernels_image.h", "kernels_cast.h",
                   "kernels_rays.h", "kernels_selftest.h", "kernels_masks.h", "kernels_frames.h", "kernels_moments.h",
-                  "kernels_adaptive.h", "kernels_denoise.h"]
+                  "kernels_adaptive.h", "kernels_denoise.h", "kernels_temporal.h"]
 
 
 def _run(cmd, log=None):

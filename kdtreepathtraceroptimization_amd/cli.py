@@ -39,6 +39,15 @@ output comes from rank 0's context through the same save paths; the JSON gains "
 kdpt_denoise's variance-guided edge-avoiding filter (PASSES a-trous passes, default 5), then saveImage's pixel pass
 with samples = 1 (save_pixels).  It keeps second moments while rendering, as --target-noise does, works with --adaptive
 (the per-pixel counts are inside the means) and --devices (rank 0's context), and needs at least 2 iterations.
+
+--orbit FRAMES DEGREES renders a camera path: FRAMES views, view f the scene's camera turned about its lookAt point
+around its up axis by f * DEGREES / FRAMES (runtime.orbit_camera; view 0 is the scene's own, and 360 degrees close the
+turntable), each with --iterations samples of its own after a reset (view f takes the iteration numbers after
+view f - 1's, so no two views draw the same samples), written as BASE.fNNNN.png (and .hdr, and with --denoise
+BASE.fNNNN.denoised.png / .hdr).  --temporal (with --denoise) denoises each frame with kdpt_denoise_temporal: the
+previous frame's result is reprojected into the new view before the filter runs; the history is reset before frame 0,
+and every frame prints how many of its valid pixels found history.  Both work with --devices (kdpt_group_set_camera,
+kdpt_group_reset; rank 0's context denoises).  Without them nothing changes.
 """
 from __future__ import annotations
 
@@ -131,7 +140,26 @@ def parse_args(argv=None) -> argparse.Namespace:
                     help="also write BASE.denoised.png (and BASE.denoised.hdr with --hdr): the per-pixel means through "
                          "the variance-guided edge-avoiding filter (kdpt_denoise), PASSES a-trous passes (0 .. 8, "
                          "default 5); keeps second moments while rendering and needs at least 2 iterations")
+    ap.add_argument("--orbit", nargs=2, default=None, metavar=("FRAMES", "DEGREES"),
+                    help="render FRAMES views, view f turned about the camera's lookAt point around its up axis by "
+                         "f * DEGREES / FRAMES, each with --iterations samples after a reset; writes BASE.fNNNN.png "
+                         "(with --denoise also BASE.fNNNN.denoised.png)")
+    ap.add_argument("--temporal", action="store_true",
+                    help="with --denoise: denoise each frame with kdpt_denoise_temporal (the previous frame's result "
+                         "reprojected into the new view first) and print each frame's with_history / valid")
     a = ap.parse_args(argv)
+    if a.orbit is not None:
+        try:
+            a.orbit = (int(a.orbit[0]), float(a.orbit[1]))
+        except ValueError:
+            ap.error("--orbit: FRAMES must be an integer and DEGREES a number")
+        if a.orbit[0] < 1 or not math.isfinite(a.orbit[1]):
+            ap.error("--orbit: FRAMES must be >= 1 and DEGREES finite")
+        if a.target_noise is not None or a.adaptive or a.testing:
+            ap.error("--orbit renders a fixed number of samples per view; it cannot be combined with --target-noise, "
+                     "--adaptive or --testing")
+    if a.temporal and a.denoise is None:
+        ap.error("--temporal needs --denoise")
     if a.denoise is not None:
         if not 0 <= a.denoise <= 8:
             ap.error("--denoise: PASSES must be in 0 .. 8")
@@ -284,9 +312,10 @@ def save_pixels(mean):
 
 def write_denoised(pt, a: argparse.Namespace, base: str):
     """--denoise: BASE.denoised.png / BASE.denoised.hdr from kdpt_denoise's means (the context's per-pixel sample
-    counts are inside them): the files written."""
+    counts are inside them), with --temporal from kdpt_denoise_temporal's: the files written."""
     from .runtime import default_denoise_params, hdr_encode, png_encode
-    rgb, lin = save_pixels(pt.denoise(default_denoise_params(passes=a.denoise)))
+    params = default_denoise_params(passes=a.denoise)
+    rgb, lin = save_pixels(pt.denoise_temporal(dparams=params) if a.temporal else pt.denoise(params))
     written = []
     for ext, on, encode, pixels in ((".denoised.png", not a.no_png, png_encode, rgb),
                                     (".denoised.hdr", a.hdr, hdr_encode, lin)):
@@ -323,6 +352,66 @@ def write_outputs(pt, a: argparse.Namespace, base: str, spp: int, counted: bool)
     if a.denoise is not None:
         written += write_denoised(pt, a, base)
     return written
+
+
+def orbit_frame_name(base: str, frame: int) -> str:
+    return f"{base}.f{frame:04d}"
+
+
+def main_orbit(a: argparse.Namespace, sd, hdr: dict, iterations: int, info: dict) -> int:
+    """main() with --orbit: FRAMES views of `iterations` samples each, on one context or (--devices) a group whose
+    rank 0 writes the outputs.  A view is "set camera, reset, render, write"; with --temporal the denoiser's history
+    is reset before view 0 and carried from view to view."""
+    from .runtime import REDUCE_COPY, REDUCE_RCCL, PathTracer, RenderGroup, orbit_camera
+    nframes, degrees = a.orbit
+    base = a.out or f"{hdr['file'] or os.path.splitext(os.path.basename(a.scene))[0]}.{iterations}samp"
+    moments = a.denoise is not None
+    if a.devices is not None:
+        owner = RenderGroup(sd, a.devices, options_from_args(a), moments=moments,
+                            reduce=REDUCE_COPY if a.reduce == "copy" else REDUCE_RCCL)
+    else:
+        owner = PathTracer(sd, options_from_args(a), device=a.device)
+    written, temporal, segments = [], [], 0
+    with owner:
+        pt = owner.context(0) if a.devices is not None else owner
+        if moments and a.devices is None:
+            pt.set_moments(True)
+        if a.temporal:
+            pt.temporal_reset()
+        t0 = time.perf_counter()
+        for f in range(nframes):
+            owner.synchronize()
+            owner.set_camera(orbit_camera(sd.view.camera, degrees * f / nframes))
+            owner.reset()
+            # view f takes iterations f * N + 1 .. (f + 1) * N (from --first-iteration on one context): an iteration
+            # number is a random seed, and the temporal blend wants every view's samples to be its own
+            if a.devices is not None:
+                per_frame = max(1, min(16, a.pipeline)) * max(1, min(16, a.batch)) * len(a.devices)
+                spp = iterations if iterations <= per_frame else math.gcd(per_frame, iterations)
+                owner.render_frames(f * (iterations // spp), iterations // spp, spp, pipeline=a.pipeline,
+                                    batch=a.batch)
+                owner.synchronize()
+            else:
+                pt.trace_iterations(a.first_iteration + f * iterations, iterations, pipeline=a.pipeline,
+                                    batch=a.batch)
+                pt.synchronize()
+            ranks = range(len(a.devices)) if a.devices is not None else (0,)
+            segments += sum(int((owner.context(r) if a.devices is not None else pt).stats().total_segments)
+                            for r in ranks)
+            written += write_outputs(pt, a, orbit_frame_name(base, f), iterations, False)
+            if a.temporal:
+                st = pt.temporal_stats()
+                temporal.append({"frame": f, "with_history": st.with_history, "valid": st.valid})
+                print(f"frame {f}: with_history / valid = {st.with_history} / {st.valid}", flush=True)
+        dt = time.perf_counter() - t0
+    info.update({"orbit": {"frames": nframes, "degrees": degrees}, "segments": segments, "seconds": round(dt, 4),
+                 "ms_per_iteration": round(dt * 1e3 / (iterations * nframes), 4), "written": written})
+    if a.devices is not None:
+        info.update({"devices": a.devices, "reduce": a.reduce})
+    if a.temporal:
+        info["temporal"] = temporal
+    print(json.dumps(info), flush=True)
+    return 0
 
 
 def main_group(a: argparse.Namespace, sd, hdr: dict, iterations: int, info: dict) -> int:
@@ -378,6 +467,8 @@ def main(argv=None) -> int:
     if a.denoise is not None and iterations < 2:
         raise SystemExit("--denoise needs at least 2 iterations: the filter is guided by the per-pixel variance, "
                          f"and {iterations} iteration gives none (raise --iterations)")
+    if a.orbit is not None:
+        return main_orbit(a, sd, hdr, iterations, info)
     if a.devices is not None:
         return main_group(a, sd, hdr, iterations, info)
     opt = options_from_args(a)

@@ -232,6 +232,29 @@ struct Denoiser {
   double guide_ms = 0, filter_ms = 0;  // the last call's (kdpt_denoise_stats)
 };
 
+// Temporal accumulation (kdpt_denoise_temporal): two frames in the denoiser's record layout plus a length per pixel
+// -- set[cur] is the history (the guides, C', V' and L' of the last call, with the camera they were made under),
+// set[cur ^ 1] the frame the next call builds, so that storing the new history is `cur ^= 1` and not a copy.
+// Made on first use (temporal_sets), dropped by kdpt_temporal_reset and, with the denoiser's buffers, by
+// kdpt_set_tuning.  `s = {}` drops the sets and the history with them.
+struct Temporal {
+  struct Set {
+    DeviceBuf<float4> g0, g1, cv;  // [npix]
+    DeviceBuf<float> len;          // [npix]
+  };
+  struct Sets {
+    int npix = 0;      // the pixel count the sets were made for (0: none)
+    Set set[2];
+    DeviceBuf<unsigned int> counts;  // [2] valid pixels, of which with history
+    int cur = 0;
+    bool have = false;  // set[cur] holds a history
+    kdpt_camera cam{};  // ... made under this camera
+  } s;
+  Event ev[4];  // before the guides, before the temporal stage, before the filter, after it
+  double guide_ms = 0, temporal_ms = 0, filter_ms = 0;  // the last call's (kdpt_temporal_stats)
+  long long valid = 0, with_history = 0;
+};
+
 struct kdpt_ctx {
   int device = 0;
   Stream stream;  // (declared before every other resource: destroyed last)
@@ -288,6 +311,7 @@ struct kdpt_ctx {
   RayQuery query;
   Moments mom;
   Denoiser den;
+  Temporal tmp;
   // an iteration (or a frame) has been added into the image since create / kdpt_reset: with stats.iterations what
   // kdpt_set_moments(1) refuses on (kdpt_trace_iteration_async counts no iteration)
   bool accumulated = false;

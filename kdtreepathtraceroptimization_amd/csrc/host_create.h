@@ -285,6 +285,7 @@ int kdpt_set_tuning(kdpt_ctx* c, const char* name, double value) {
   }
   HIP_TRY(hipSetDevice(c->device));
   c->den.b = {};  // kdpt_denoise's buffers (nothing is queued on them): its next call remakes them
+  c->tmp.s = {};  // ... and kdpt_denoise_temporal's history with them
   // queued iterations finish first: setup_trace and build_masks free and reallocate device memory their
   // kernels read.  The pipeline's states hold no knobs; they are still dropped, as include/kdpt.h documents
   // (the next kdpt_trace_iterations remakes them).

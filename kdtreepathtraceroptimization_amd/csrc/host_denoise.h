@@ -31,13 +31,14 @@ int check_denoise_params(const kdpt_denoise_params* p, const std::string& who) {
   return KDPT_OK;
 }
 
-// The passes on stream st: pass k reads cv[k & 1] and writes cv[~k & 1]; *last: the buffer the result is in.
+// The passes on stream st: pass 0 reads `in` (which no pass writes unless it is cv[0]), pass k > 0 cv[k & 1]; pass
+// k writes cv[~k & 1]; *last: the buffer the result is in.
 int launch_denoise_passes(const kdpt_denoise_params& p, int W, int H, const float4* g0, const float4* g1,
-                          float4* const cv[2], hipStream_t st, const float4** last) {
+                          const float4* in, float4* const cv[2], hipStream_t st, const float4** last) {
   for (int k = 0; k < p.passes; k++) {
     const int s = 1 << k;
-    DenoisePass a{g0, g1, cv[k & 1], cv[(k & 1) ^ 1], W, H, s, std::min(s, W), std::min(s, H), p.normal_power_log2,
-                  p.sigma_l, p.sigma_z, p.eps_l};
+    DenoisePass a{g0, g1, k == 0 ? in : cv[k & 1], cv[(k & 1) ^ 1], W, H, s, std::min(s, W), std::min(s, H),
+                  p.normal_power_log2, p.sigma_l, p.sigma_z, p.eps_l};
     if (s <= DN_TILED_MAX_STEP) {  // a 32 x 8 tile of each lattice of pixels congruent mod s
       const int lw = (W + s - 1) / s, lh = (H + s - 1) / s;
       const dim3 grid(((lw + DN_TILE_W - 1) / DN_TILE_W) * a.nrx, ((lh + DN_TILE_H - 1) / DN_TILE_H) * a.nry);
@@ -48,8 +49,12 @@ int launch_denoise_passes(const kdpt_denoise_params& p, int W, int H, const floa
     }
     HIP_TRY(hipGetLastError());
   }
-  *last = cv[p.passes & 1];
+  *last = p.passes == 0 ? in : cv[p.passes & 1];
   return KDPT_OK;
+}
+int launch_denoise_passes(const kdpt_denoise_params& p, int W, int H, const float4* g0, const float4* g1,
+                          float4* const cv[2], hipStream_t st, const float4** last) {
+  return launch_denoise_passes(p, W, H, g0, g1, cv[0], cv, st, last);
 }
 
 // The context's denoising buffers, made on first use (nothing is queued on them: every call that uses them ends
@@ -70,6 +75,40 @@ int denoise_buffers(kdpt_ctx* c) {
   for (Event& e : c->den.ev)
     if (!e) HIP_TRY(e.create());
   b.npix = c->npix;
+  return KDPT_OK;
+}
+
+// The guides on the context's stream: the camera's pinhole rays through kdpt_cast_rays' kernels, one chunk of W*H
+// rays, flags = 0; the hit records land in den.b.hits_out.
+int launch_denoise_guides(kdpt_ctx* c) {
+  const hipStream_t st = c->stream;
+  const Denoiser::Buffers& b = c->den.b;
+  const int npix = c->npix;
+  const size_t m = (size_t)npix;
+  const dim3 lin((npix + 255) / 256);
+  HIP_TRY(hipMemsetAsync(b.cnt.get(), 0, sizeof(int) * 2, st));
+  HIP_TRY(hipMemsetAsync(b.tt.get(), 0, sizeof(unsigned long long) * 3, st));
+  hipLaunchKernelGGL(k_denoise_rays, lin, dim3(256), 0, st, c->cam, b.rays.get(), b.rays.get() + 3 * m);
+  HIP_TRY(hipGetLastError());
+  CastArgs a;
+  a.S = c->S;
+  a.o = b.rays.get();
+  a.d = b.rays.get() + 3 * m;
+  a.n = npix;
+  a.normalize = 0;
+  a.cray = b.cray.get();
+  a.hits = b.hits.get();
+  a.cand = b.cand.get();
+  a.cnt = b.cnt.get();
+  a.tt = b.tt.get();
+  a.out = b.hits_out.get();
+  const TraceArgs t{c->S, a.cand, a.cray, a.cnt + 1, a.hits, nullptr, 0, a.cnt, 0, c->counters, a.tt};
+  hipLaunchKernelGGL(k_cast_prep, dim3((npix + GEN_BLOCK - 1) / GEN_BLOCK), dim3(GEN_BLOCK), 0, st, a);
+  HIP_TRY(hipGetLastError());
+  launch_trace(c, t, false, c->trace_grid, st);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(hybrid_shading(c) ? k_cast_resolve<true> : k_cast_resolve<false>, lin, dim3(256), 0, st, a);
+  HIP_TRY(hipGetLastError());
   return KDPT_OK;
 }
 
@@ -166,29 +205,7 @@ int kdpt_denoise(kdpt_ctx* c, const kdpt_denoise_params* p, float* out_color, fl
   const dim3 lin((npix + 255) / 256);
   // ---- the guides: the pinhole rays through kdpt_cast_rays' kernels, one chunk of W*H rays, flags = 0 ----
   HIP_TRY(hipEventRecord(c->den.ev[0], st));
-  HIP_TRY(hipMemsetAsync(b.cnt.get(), 0, sizeof(int) * 2, st));
-  HIP_TRY(hipMemsetAsync(b.tt.get(), 0, sizeof(unsigned long long) * 3, st));
-  hipLaunchKernelGGL(k_denoise_rays, lin, dim3(256), 0, st, c->cam, b.rays.get(), b.rays.get() + 3 * m);
-  HIP_TRY(hipGetLastError());
-  CastArgs a;
-  a.S = c->S;
-  a.o = b.rays.get();
-  a.d = b.rays.get() + 3 * m;
-  a.n = npix;
-  a.normalize = 0;
-  a.cray = b.cray.get();
-  a.hits = b.hits.get();
-  a.cand = b.cand.get();
-  a.cnt = b.cnt.get();
-  a.tt = b.tt.get();
-  a.out = b.hits_out.get();
-  const TraceArgs t{c->S, a.cand, a.cray, a.cnt + 1, a.hits, nullptr, 0, a.cnt, 0, c->counters, a.tt};
-  hipLaunchKernelGGL(k_cast_prep, dim3((npix + GEN_BLOCK - 1) / GEN_BLOCK), dim3(GEN_BLOCK), 0, st, a);
-  HIP_TRY(hipGetLastError());
-  launch_trace(c, t, false, c->trace_grid, st);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(hybrid_shading(c) ? k_cast_resolve<true> : k_cast_resolve<false>, lin, dim3(256), 0, st, a);
-  HIP_TRY(hipGetLastError());
+  if ((rc = launch_denoise_guides(c))) return rc;
   HIP_TRY(hipEventRecord(c->den.ev[1], st));
   // ---- the filter ----
   hipLaunchKernelGGL(k_denoise_pack_render, lin, dim3(256), 0, st, (const float*)c->image,

@@ -62,6 +62,7 @@ using namespace kdpt;
 #include "kernels_frames.h"
 #include "kernels_adaptive.h"
 #include "kernels_denoise.h"
+#include "kernels_temporal.h"
 #include "kernels_moments.h"
 
 // The host code, one section per feature; a section uses what the sections before it define.
@@ -75,5 +76,6 @@ using namespace kdpt;
 #include "host_queries.h"
 #include "host_moments.h"
 #include "host_denoise.h"
+#include "host_temporal.h"
 #include "host_group.h"
 #include "host_selftest.h"

@@ -146,7 +146,21 @@ class DenoiseStats(NamedTuple):  # kdpt_denoise_stats: of the last kdpt_denoise
     filter_ms: float  # packing, the passes and the copy out
 
 
+class TemporalParams(C.Structure):  # kdpt_temporal_params: the temporal stage's knobs (kdpt_default_temporal_params)
+    _fields_ = [("alpha", C.c_float), ("sigma_z", C.c_float), ("normal_min", C.c_float), ("max_history", C.c_int),
+                ("pad_", C.c_float * 2)]
+
+
+class TemporalStats(NamedTuple):  # kdpt_temporal_stats: of the last kdpt_denoise_temporal
+    guide_ms: float      # the pinhole rays, their traversal and hit records
+    temporal_ms: float   # packing and the temporal stage
+    filter_ms: float     # the passes and the copy out
+    valid: int           # the frame's valid pixels
+    with_history: int    # ... of which found history
+
+
 assert C.sizeof(Noise) == 48 and C.sizeof(Adaptive) == 48 and C.sizeof(DenoiseParams) == 24
+assert C.sizeof(TemporalParams) == 24
 assert C.sizeof(Geom) == 236 and C.sizeof(Material) == 56 and C.sizeof(Camera) == 84
 assert C.sizeof(NodeBare) == 64 and C.sizeof(TriBare) == 76 and C.sizeof(PathSegment) == 56
 
@@ -169,6 +183,8 @@ EXPORTS = [
     "kdpt_group_active_pixels", "kdpt_group_trace_adaptive", "kdpt_group_set_camera", "kdpt_group_set_options",
     "kdpt_group_reset", "kdpt_group_destroy",
     "kdpt_default_denoise_params", "kdpt_denoise_buffers", "kdpt_denoise", "kdpt_denoise_stats",
+    "kdpt_default_temporal_params", "kdpt_temporal_buffers", "kdpt_denoise_temporal", "kdpt_temporal_reset",
+    "kdpt_temporal_stats",
 ]
 
 REDUCE_RCCL, REDUCE_COPY = 0, 1  # kdpt_render_sharded's reduce (KDPT_REDUCE_*)
@@ -311,6 +327,18 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                                              P(C.c_float)]
         lib.kdpt_denoise.argtypes = [C.c_void_p, P(DenoiseParams), C.c_void_p, C.c_void_p]
         lib.kdpt_denoise_stats.argtypes = [C.c_void_p, P(C.c_double), P(C.c_double)]
+    if hasattr(lib, "kdpt_denoise_temporal"):  # absent from older builds used in A/B runs
+        lib.kdpt_default_temporal_params.argtypes = [P(TemporalParams)]
+        lib.kdpt_default_temporal_params.restype = None
+        lib.kdpt_temporal_buffers.argtypes = (
+            [C.c_int, C.c_int, C.c_int] +
+            [P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_int)] +
+            [P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_int), P(C.c_float)] +
+            [P(Camera), P(TemporalParams), P(C.c_float), P(C.c_float), P(C.c_float)])
+        lib.kdpt_denoise_temporal.argtypes = [C.c_void_p, P(TemporalParams), P(DenoiseParams), C.c_void_p, C.c_void_p]
+        lib.kdpt_temporal_reset.argtypes = [C.c_void_p]
+        lib.kdpt_temporal_stats.argtypes = [C.c_void_p, P(C.c_double), P(C.c_double), P(C.c_double),
+                                            P(C.c_longlong), P(C.c_longlong)]
     _lib = lib
     return lib
 
@@ -538,6 +566,82 @@ def denoise_buffers(color, variance, normal, point, depth, ids, params: Optional
                                                _fptr(dep), _iptr(idv), C.byref(p), _fptr(out),
                                                _fptr(ov) if return_variance else None), "kdpt_denoise_buffers")
     return (out, ov) if return_variance else out
+
+
+def default_temporal_params(**overrides) -> TemporalParams:
+    """kdpt_default_temporal_params: alpha 0.2, sigma_z 0.02, normal_min 0.9, max_history 32."""
+    p = TemporalParams()
+    load_library().kdpt_default_temporal_params(C.byref(p))
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def _frame_arrays(what, color, variance, normal, point, depth, ids, shape=None):
+    col = np.ascontiguousarray(color, dtype=np.float32)
+    if col.ndim != 3 or col.shape[2] != 3:
+        raise ValueError(f"{what}color: expected (H, W, 3), got {col.shape}")
+    h, w = col.shape[:2]
+    if shape is not None and (h, w) != shape:
+        raise ValueError(f"{what}color: {w} x {h} beside a {shape[1]} x {shape[0]} frame")
+    var, dep = (np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in (variance, depth))
+    nrm, pnt = (np.ascontiguousarray(a, dtype=np.float32).reshape(-1) for a in (normal, point))
+    idv = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+    for name, a, n in (("variance", var, 1), ("depth", dep, 1), ("ids", idv, 1), ("normal", nrm, 3), ("point", pnt, 3)):
+        if a.size != n * w * h:
+            raise ValueError(f"{what}{name}: {a.size} values for a {w} x {h} image")
+    return (h, w), (col, var, nrm, pnt, dep, idv)
+
+
+def temporal_buffers(color, variance, normal, point, depth, ids, history=None, params: Optional[TemporalParams] = None,
+                     device: int = 0):
+    """kdpt_temporal_buffers: the temporal stage alone on caller data -- the current frame as denoise_buffers takes
+    it, and `history`, None or (color, variance, normal, point, depth, ids, length, camera): the previous frame's
+    arrays of the same shapes, its lengths (H, W) float32 and the Camera it was made under.  Returns (colour (H, W, 3),
+    variance (H, W), length (H, W)): the blended frame, which with the current guides and camera is the next call's
+    history."""
+    (h, w), cur = _frame_arrays("", color, variance, normal, point, depth, ids)
+    p = params if params is not None else default_temporal_params()
+    hist, cam = [None] * 7, None
+    if history is not None:
+        _, ha = _frame_arrays("history ", *history[:6], shape=(h, w))
+        ln = np.ascontiguousarray(history[6], dtype=np.float32).reshape(-1)
+        if ln.size != w * h:
+            raise ValueError(f"history length: {ln.size} values for a {w} x {h} image")
+        hist = [_fptr(a) for a in ha[:5]] + [_iptr(ha[5]), _fptr(ln)]
+        cam = C.byref(history[7])
+    out = np.empty((h, w, 3), dtype=np.float32)
+    ov, ol = np.empty((h, w), dtype=np.float32), np.empty((h, w), dtype=np.float32)
+    _check(load_library().kdpt_temporal_buffers(int(device), w, h, *[_fptr(a) for a in cur[:5]], _iptr(cur[5]), *hist,
+                                                cam, C.byref(p), _fptr(out), _fptr(ov), _fptr(ol)),
+           "kdpt_temporal_buffers")
+    return out, ov, ol
+
+
+def orbit_camera(camera: Camera, degrees: float) -> Camera:
+    """A copy of `camera` turned about its lookAt point around its `up` axis by `degrees` (a turntable step).  With
+    k = up / |up|, v = position - lookAt and t = radians(degrees), Rodrigues' formula in float32:
+        v' = v cos t + (k x v) sin t + k (k . v) (1 - cos t);   position' = lookAt + v'
+    then view' = normalize(lookAt - position') and right' = normalize(cross(view', up)), as the scene loader makes
+    them.  up, lookAt, resolution, fov and pixelLength are kept."""
+    f32 = np.float32
+    out = Camera.from_buffer_copy(bytes(camera))
+    pos, look, up = (np.array(a[:], f32) for a in (camera.position, camera.lookAt, camera.up))
+    k = up / f32(np.sqrt(np.dot(up, up)))
+    v = pos - look
+    t = np.deg2rad(f32(degrees)).astype(f32)
+    c, s = f32(np.cos(t)), f32(np.sin(t))
+    v2 = (v * c + np.cross(k, v).astype(f32) * s + k * (f32(np.dot(k, v)) * (f32(1) - c))).astype(f32)
+    pos2 = (look + v2).astype(f32)
+    view = look - pos2
+    view = (view / f32(np.sqrt(np.dot(view, view)))).astype(f32)
+    right = np.cross(view, up).astype(f32)
+    right = (right / f32(np.sqrt(np.dot(right, right)))).astype(f32)
+    for name, val in (("position", pos2), ("view", view), ("right", right)):
+        setattr(out, name, (C.c_float * 3)(*[float(x) for x in val]))
+    return out
 
 
 class PathTracer:
@@ -779,6 +883,43 @@ class PathTracer:
         _check(self.lib.kdpt_denoise_stats(self._ctx, C.byref(g), C.byref(f)), "kdpt_denoise_stats")
         return DenoiseStats(g.value, f.value)
 
+    def denoise_temporal(self, tparams: Optional[TemporalParams] = None, dparams: Optional[DenoiseParams] = None,
+                         variance: bool = False):
+        """kdpt_denoise_temporal: denoise() with the previous call's result reprojected into this frame first
+        (include/kdpt.h "Temporal accumulation"): (H, W, 3) float32, or (colour, variance) with variance=True.  The
+        call stores this frame as the next one's history; the history survives reset(), set_camera() and
+        set_options(), so a frame of a camera path is "set_camera, reset, trace, denoise_temporal"."""
+        tp = tparams if tparams is not None else default_temporal_params()
+        dp = dparams if dparams is not None else default_denoise_params()
+        col = np.empty((self.height, self.width, 3), dtype=np.float32)
+        var = np.empty((self.height, self.width), dtype=np.float32) if variance else None
+        _check(self.lib.kdpt_denoise_temporal(self._ctx, C.byref(tp), C.byref(dp), C.c_void_p(col.ctypes.data),
+                                              C.c_void_p(var.ctypes.data) if variance else None),
+               "kdpt_denoise_temporal")
+        return (col, var) if variance else col
+
+    def denoise_temporal_ptr(self, tparams: Optional[TemporalParams], dparams: Optional[DenoiseParams],
+                             color_ptr: int, variance_ptr: Optional[int] = None):
+        """kdpt_denoise_temporal into raw pointers (host memory or the context's device): 3*W*H floats, W*H floats."""
+        tp = tparams if tparams is not None else default_temporal_params()
+        dp = dparams if dparams is not None else default_denoise_params()
+        _check(self.lib.kdpt_denoise_temporal(self._ctx, C.byref(tp), C.byref(dp), C.c_void_p(int(color_ptr)),
+                                              C.c_void_p(int(variance_ptr)) if variance_ptr is not None else None),
+               "kdpt_denoise_temporal")
+
+    def temporal_reset(self):
+        """kdpt_temporal_reset: drop the history; the next denoise_temporal() equals denoise()."""
+        _check(self.lib.kdpt_temporal_reset(self._ctx), "kdpt_temporal_reset")
+
+    def temporal_stats(self) -> "TemporalStats":
+        """kdpt_temporal_stats: the last denoise_temporal's device times in ms (guides, temporal stage, filter) and
+        its counts of valid pixels and of those that found history."""
+        g, t, f = C.c_double(), C.c_double(), C.c_double()
+        v, w = C.c_longlong(), C.c_longlong()
+        _check(self.lib.kdpt_temporal_stats(self._ctx, C.byref(g), C.byref(t), C.byref(f), C.byref(v), C.byref(w)),
+               "kdpt_temporal_stats")
+        return TemporalStats(g.value, t.value, f.value, int(v.value), int(w.value))
+
     def trace_rays_ptr(self, origins_ptr: int, directions_ptr: int, n: int, radiance_ptr: int, first_iter: int = 1,
                        count: int = 1, normalize: bool = True):
         """kdpt_trace_rays on raw pointers, each host memory or memory of the context's device (e.g. a torch
@@ -972,7 +1113,7 @@ class RenderGroup:
     def context(self, rank: int = 0) -> PathTracer:
         """kdpt_group_context: rank's context as a PathTracer that does not own it, for reads and queries (image,
         moments, noise_map, noise_estimate, sample_counts, save_*, stats, cast_rays, trace_rays, camera_rays, and
-        denoise on rank 0 of a group with moments)."""
+        denoise, denoise_temporal and temporal_reset on rank 0 of a group with moments)."""
         h = C.c_void_p()
         _check(self.lib.kdpt_group_context(self._g, int(rank), C.byref(h)), "kdpt_group_context")
         return PathTracer.borrowed(self, self.scene, self.opt, h)
